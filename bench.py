@@ -6,9 +6,10 @@ A "step" is ONE simplex iteration (pricing -> FTRAN -> ratio test -> BTRAN -> ta
 basis-inverse update -> x_B/d/gamma/beta updates) of the device-resident solver.
 
 `value` (the driver-timed figure): W warm-up pivots from the slack basis, then exactly K timed pivots
-bracketed by barrier + synchronize.  That window is the cheapest stretch of a 1.09 M-pivot solve, so the
-same JSON line also carries (N = 1, rank 0, outside the timed region; every object says whether it was measured
-LIVE by this run or read from a COMMITTED file):
+bracketed by barrier + synchronize.  A plain run does only that (set-up, warm-up, the K timed pivots, --dump-outputs,
+the line).  That window is the cheapest stretch of a 1.09 M-pivot solve, so with --full the same JSON line also
+carries (N = 1, rank 0, outside the timed region; every object says whether it was measured LIVE by this run or
+read from a COMMITTED file; an event-bracketed sampling pass after the timed pivots gives `roofline`):
   * `windows.mid` / `windows.late` (live): a fixed number of pivots from the two committed MID-SOLVE bases of the same
     instance (tests/golden/cfg4_basis_p*.bin.gz, nucleus ~10 000 and ~20 000: where the solve spends its time),
     each with pivots/s, us per pivot and per-kernel bytes / GB/s / fraction of the HBM roofline;
@@ -17,11 +18,16 @@ LIVE by this run or read from a COMMITTED file):
     FTRAN-shaped solve that IS a stream: the dense-rhs x_B = B^-1 (b - N x_N) of the polish step
     (mlp_solution_recompute_basic_values), one read of the nucleus inverse through k_stream_w's tau side;
   * `full_solve` (live): BASELINE.json's "total solve wall-time" — the timed solve is continued to optimality in chunks
-    of 50 000 pivots under a wall guard, and the optimum is certified on the box by weak duality (scipy mat-vecs);
+    of 50 000 pivots under a wall guard (--wall-guard 1300 lets it finish), and the optimum is certified on the box by
+    weak duality (scipy mat-vecs);
   * `cpu_baseline` (live): the oracle timed on the host cores over the SAME pivots as `value` (and over pivots
     200..700, its fastest sustained stretch).
 N > 1: one process per GPU (torch.distributed, RCCL); ONE LP, pricing path sharded; a failure of
-the sharded set-up is an error, never a silent fall-back to replicas.
+the sharded set-up is an error, never a silent fall-back to replicas.  With --full the line also carries the sharded
+late window and the unsharded reference of the same run.
+
+--dump-outputs DIR writes what the timed pivots computed (rank 0, after the timed region) as float64 .npy files; the
+inputs are seeded, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -56,12 +62,20 @@ def parse():
     ap.add_argument("--window-steps", type=int, nargs=2, default=[512, 256], metavar=("MID", "LATE"))
     ap.add_argument("--samples", type=int, default=32, help="pivots of the event-bracketed sampling pass after a timed region")
     ap.add_argument("--no-full-solve", action="store_true", help="do not continue the timed solve to optimality (total solve wall time)")
-    ap.add_argument("--wall-guard", type=float, default=1300.0,
-                    help="full solve: stop (complete = false) once the whole bench run has lasted this many seconds")
+    ap.add_argument("--wall-guard", type=float, default=450.0,
+                    help="full solve: stop (complete = false) once the whole bench run has lasted this many seconds (the solve to the "
+                         "optimum takes ~760 s on one MI355X: pass 1300 for the certified total solve wall time)")
     ap.add_argument("--chunk", type=int, default=50000, help="full solve: pivots per continue call")
     ap.add_argument("--no-factor-transport", action="store_true", help="skip the 200 000-row transport solve on the compact factor (row f3)")
     ap.add_argument("--independent", action="store_true",
                     help="N > 1: one independent LP per rank (weak scaling) instead of column-block sharded pricing of ONE LP")
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline figure: sampling pass with per-kernel / roofline figures, mid / late windows, CPU "
+                         "baseline, full solve, transport solve (N > 1: sharded late window, unsharded reference); writes the full record")
+    ap.add_argument("--detail-dir", default=os.path.join(ROOT, "bench_out"), metavar="DIR",
+                    help="--full: directory of the full record bench_detail_n<N>.json")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what they computed (x, objective, basis, reduced costs) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -373,8 +387,8 @@ def factor_transport(a):
 
 def compact_line(out):
     """The ONE JSON line printed on stdout: every contract field, numbers rounded, free text kept short (the driver
-    reads the tail of stdout: the round-1 line was 2.7 KB).  The full record (kernel descriptions, sampling notes, every
-    per-kernel figure) is written next to it as gpurun_out/bench_detail_n<N>.json."""
+    reads the tail of stdout: the round-1 line was 2.7 KB).  Under --full the full record (kernel descriptions, sampling notes,
+    every per-kernel figure) is written next to it as <--detail-dir>/bench_detail_n<N>.json."""
     def r(x, n=4):
         return round(x, n) if isinstance(x, float) else x
 
@@ -457,6 +471,18 @@ def compact_line(out):
             line["factor_transport"]["sparse_bump_committed"] = {k_: (r(v_, 2) if isinstance(v_, float) else v_) for k_, v_ in sbc.items()
                                                                  if k_ in ("source", "gpu_wall_s", "oracle_wall_s", "gpu_over_oracle", "largest_bump")}
     return line
+
+
+def dump_outputs(s, path):
+    """What a caller of the timed path holds after its last pivot, as float64 .npy files (about 2.4 MB at config-4 size): x, the
+    objective, the basic variables by row and the reduced costs of the non-basic positions.  (x_B is left out: two runs of the
+    same build differ in its last bits, the F product sums through float atomics.)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(x=s.values(), objective=np.array([s.objective()]), basic_vars=s.state("basic_vars"),
+                  nb_var_obj_coeffs=s.state("nb_var_obj_coeffs"))
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def self_launch(a):
@@ -593,28 +619,32 @@ def main():
         total = float(c.item()) / world if sharded else float(c.item())   # sharded: every rank counts the same pivots
     else:
         total = float(done)
-    # event-bracketed sampling pass (outside the timed region, same solve, the pivots that follow): >= 8 samples
-    # of every kernel whatever K is; all ranks run it (the sharded exchange needs every rank)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(s, a.dump_outputs)
+    st = st_timed
     samples_in_region = int(st_timed["sweep_launches"])
-    s.set_sampling(True)
-    t0 = time.perf_counter()
-    s.continue_solve(a.samples)
-    solve_s += time.perf_counter() - t0
-    s.set_sampling(False)
-    st = s.stats()
+    if a.full:
+        # event-bracketed sampling pass (outside the timed region, same solve, the pivots that follow): >= 8 samples
+        # of every kernel whatever K is; all ranks run it (the sharded exchange needs every rank)
+        s.set_sampling(True)
+        t0 = time.perf_counter()
+        s.continue_solve(a.samples)
+        solve_s += time.perf_counter() - t0
+        s.set_sampling(False)
+        st = s.stats()
     if rank == 0:
-        kern = kernel_report(st)
+        kern = kernel_report(st) if a.full else {}
         dom = max((k for k in ("fused", "sweep") if k in kern), key=lambda k: kern[k]["total_ms"], default=None)
         # the pricing path that shards over column blocks = tableau-row sweep + d/gamma update + pricing scan
         pricing_us = None
         if "update" in kern and ("sweep" in kern or "row_sparse" in kern):
             pricing_us = kern["sweep" if "sweep" in kern else "row_sparse"]["avg_us"] + kern["update"]["avg_us"]
         roofline = None
-        try:
-            head_iters = int(s.state("primal_head_launches")[0])
-        except Exception:
-            head_iters = 0
         if dom:
+            try:
+                head_iters = int(s.state("primal_head_launches")[0])
+            except Exception:
+                head_iters = 0
             which = ("sweep_band" if st.get("banded_sweep") else "sweep") if dom == "sweep" else dom
             if dom == "fused" and head_iters > 0:
                 which = "primal_head"
@@ -655,10 +685,12 @@ def main():
             # line says whether the column-block sharding was live in the timed pivots (it is in the late window)
             ranks_info["sharding_live_in_timed_window"] = bool(live_timed) if live_timed is not None else None
             out["ranks"] = ranks_info
-        out["provenance"] = dict(value="live", roofline_achieved="live (HIP events stamped by the kernels, this run)",
-                                 roofline_traffic="committed (PMC passes cannot run inside the timed run)", windows="live",
-                                 full_solve="live", cpu_baseline="live")
-        if world == 1:
+        out["provenance"] = dict(value="live")
+        if a.full:
+            out["provenance"].update(roofline_achieved="live (HIP events stamped by the kernels, this run)",
+                                     roofline_traffic="committed (PMC passes cannot run inside the timed run)", windows="live",
+                                     full_solve="live", cpu_baseline="live")
+        if world == 1 and a.full:
             cfg4 = (a.rows, a.cols, a.nnz_per_row, a.seed) == (100000, 100000, 100, 4)
             if not a.no_windows:
                 windows = {}
@@ -738,7 +770,7 @@ def main():
         dist.barrier()
         if mailbox and rank == 0:
             mdist.remove_mailbox(mailbox)
-    if world > 1 and sharded and not a.no_windows and os.path.exists(LATE_BASIS) and \
+    if world > 1 and sharded and a.full and not a.no_windows and os.path.exists(LATE_BASIS) and \
             (a.rows, a.cols, a.nnz_per_row, a.seed) == (100000, 100000, 100, 4):
         def max_over_ranks(x):
             t = torch.tensor([x], dtype=torch.float64, device=red_dev)
@@ -753,7 +785,7 @@ def main():
     # N > 1: the same two windows UNSHARDED, measured by rank 0 in this very run (the other ranks wait at the barrier), so that
     # the line carries its own 1-GPU reference: value_vs_1gpu for the timed window, and the ratio of the pricing path
     # (tableau-row sweep + d / gamma update + pricing scan: what north_star's ">= 3x at 8 GPUs" is about) for the late window
-    if world > 1 and sharded:
+    if world > 1 and sharded and a.full:
         if rank == 0:
             try:
                 ref = {}
@@ -793,12 +825,13 @@ def main():
                 out["late_sharded"] = dict(us_per_pivot=late_sharded.get("us_per_pivot"), pivots_per_s=late_sharded.get("pivots_per_s"),
                                            pricing_path_us=late_sharded.get("pricing_path_us"), k=late_sharded.get("nucleus_size_at_start"),
                                            unsharded_us_per_pivot=(out.get("unsharded_same_run") or {}).get("late_us_per_pivot"))
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", f"bench_detail_n{world}.json"), "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError:
-            pass
+        if a.full:
+            try:
+                os.makedirs(a.detail_dir, exist_ok=True)
+                with open(os.path.join(a.detail_dir, f"bench_detail_n{world}.json"), "w") as f:
+                    json.dump(out, f, indent=1)
+            except OSError:
+                pass
         real_stdout.write(json.dumps(compact_line(out)) + "\n")
         real_stdout.flush()
     if world > 1:

@@ -230,7 +230,7 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
     MLP_OVERSUBSCRIBE=1 has to allow), and the line says what ran: n_gpus == 2 == ranks_seen, one device index per rank, the
     transport of the per-pivot exchanges, the size of the process group."""
     import json
-    r = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--no-full-solve", "--no-factor-transport"], {"MLP_OVERSUBSCRIBE": "1"})
+    r = _bench(["--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-full-solve", "--no-factor-transport"], {"MLP_OVERSUBSCRIBE": "1"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -3,7 +3,7 @@
 #   1. the sharded GPU tests (incl. the RCCL transport between two devices, which is skipped on a one-GPU box),
 #   2. the bitwise replica gate on all ranks (tools/shard_bitwise.py: SHA-1 digests of what every rank holds, every 500 pivots),
 #   3. bench.py --gpus N for N in NGPUS (default "1 2 4 8"; it starts its N ranks itself and refuses a mismatched world),
-#   4. ONE table from gpurun_out/bench_detail_n<N>.json (tools/scale_table.py): value, scaling label, late sharded us per pivot,
+#   4. ONE table from the bench lines in $OUT (tools/scale_table.py): value, scaling label, late sharded us per pivot,
 #      pricing path us per pivot, pricing speed-up against the unsharded run of the same invocation.
 # On a one-GPU test rig:  MLP_OVERSUBSCRIBE=1 NGPUS="1 2" GATE_RANKS=2 tools/first_8gpu_run.sh   (every figure is then time-slicing noise;
 # the point is that every step runs and the table has its columns).
@@ -12,7 +12,7 @@ cd "$(dirname "$0")/.."
 OUT=${OUT:-gpurun_out/first_multi_gpu}
 NGPUS=${NGPUS:-"1 2 4 8"}
 GATE_RANKS=${GATE_RANKS:-8}
-BENCH_ARGS=${BENCH_ARGS:-"--steps 20 --warmup 5 --no-full-solve --no-factor-transport"}
+BENCH_ARGS=${BENCH_ARGS:-"--steps 20 --warmup 5 --full --no-full-solve --no-factor-transport"}
 mkdir -p "$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 rc_all=0
@@ -29,10 +29,9 @@ if [ "${SKIP_GATE:-0}" != "1" ]; then
 fi
 echo "== 3. bench.py --gpus N" | tee -a "$OUT/steps.log"
 for n in $NGPUS; do
-  timeout 3000 python bench.py --gpus "$n" $BENCH_ARGS > "$OUT/bench_n$n.json" 2> "$OUT/bench_n$n.err"; rc=$?
+  timeout 3000 python bench.py --gpus "$n" $BENCH_ARGS --detail-dir "$OUT" > "$OUT/bench_n$n.json" 2> "$OUT/bench_n$n.err"; rc=$?
   echo "   N=$n rc=$rc $(head -c 160 "$OUT/bench_n$n.json")" | tee -a "$OUT/steps.log"
   [ $rc -ne 0 ] && rc_all=1
-  [ -f "gpurun_out/bench_detail_n$n.json" ] && cp "gpurun_out/bench_detail_n$n.json" "$OUT/"
 done
 echo "== 4. table" | tee -a "$OUT/steps.log"
 python tools/scale_table.py "$OUT" $NGPUS | tee "$OUT/scale_table.md"

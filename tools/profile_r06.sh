@@ -5,6 +5,7 @@
 export TAG=${TAG:-r06f}
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd $ROOT
+export OUT=${OUT:-$ROOT/bench_out}; mkdir -p "$OUT"   # bench line and its full record
 if [ "${SKIP_TESTS:-0}" != "1" ]; then
   timeout 2000 python -m pytest tests -x -q -m "gpu and not slow" > gpurun_out/${TAG}_tests.log 2>&1; grep -E "passed|failed" gpurun_out/${TAG}_tests.log | tail -3
 fi
@@ -21,11 +22,11 @@ python tools/prof_summary.py /tmp/prof_tr gpurun_out/${TAG}_transport_first60k_k
 timeout 200 python tools/experiments/factor_once.py mixed 100000 160000 4 0 20000 2>&1 | tail -1   # config-3 family at 100 000 rows on the compact factor (sparse LU of the bump)
 timeout 300 python tools/config_times.py 2>&1 | grep -v Warn | cut -c1-300
 timeout 200 python tools/hyper_profile.py 2>&1 | grep -v Warn | grep "MLP_HYPER=1:\|CPU restatement" | cut -c1-260
-timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 2> gpurun_out/${TAG}_bench.err | tail -1 > gpurun_out/${TAG}_bench_line.json
-cp gpurun_out/bench_detail_n1.json gpurun_out/${TAG}_bench_detail.json 2>/dev/null
+timeout 1700 python bench.py --gpus 1 --steps 20 --warmup 5 --full --detail-dir "$OUT" 2> $OUT/${TAG}_bench.err | tail -1 > $OUT/${TAG}_bench_line.json
+cp $OUT/bench_detail_n1.json $OUT/${TAG}_bench_detail.json 2>/dev/null
 python - <<'PY'
 import json, os
-d = json.load(open("gpurun_out/" + os.environ.get("TAG", "r06f") + "_bench_line.json"))
+d = json.load(open(os.environ["OUT"] + "/" + os.environ.get("TAG", "r06f") + "_bench_line.json"))
 print({k: d[k] for k in ("value", "ms_per_step")}, d["roofline"]["frac"], d["roofline"]["pivot_level"], {w: (d["windows"][w]["us_per_pivot"]) for w in d["windows"]}, d.get("full_solve"), d["cpu_baseline"].get("gpu_over_cpu_same_window"))
 print(d["roofline"].get("ftran"))
 print(d.get("factor_transport"))

@@ -1,8 +1,9 @@
 # Round-2 validation on the GPU box: full GPU suite, the bench line (all windows), per-window rocprofv3 kernel stats.
 TAG=${1:-r02k}
+OUT=${OUT:-$PWD/bench_out}; mkdir -p "$OUT"   # bench lines and their full records
 python -m pytest tests -x -q -m gpu 2>&1 | tail -4 > gpurun_out/${TAG}_gpu_tests.log
-python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/${TAG}_bench_driver_args.json 2>> gpurun_out/${TAG}_bench.err
+python bench.py --full --detail-dir "$OUT" > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+python bench.py --steps 20 --warmup 5 --no-cpu-baseline --full --detail-dir "$OUT" > $OUT/${TAG}_bench_driver_args.json 2>> $OUT/${TAG}_bench.err
 cd /tmp && export TMPDIR=/tmp
 for w in late mid early; do
   rm -rf /tmp/prof_$w
@@ -11,10 +12,10 @@ for w in late mid early; do
 done
 cd $GRAFT_REPO_ROOT
 cat gpurun_out/${TAG}_gpu_tests.log
-tail -3 gpurun_out/${TAG}_bench.err
+tail -3 $OUT/${TAG}_bench.err
 python - <<PY
 import json
-d = json.load(open("gpurun_out/${TAG}_bench.json"))
+d = json.load(open("$OUT/${TAG}_bench.json"))
 print("early", d["value"], d["ms_per_step"], "roofline", d["roofline"]["frac"], d["roofline"]["avg_launch_us"], d["roofline"]["launches"])
 for w in ("mid", "late"):
     x = d["windows"][w]
