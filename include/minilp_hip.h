@@ -37,7 +37,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * (fields are appended, never inserted or removed), so a host built against an older version-4+ header reads a valid
  * prefix; mlp_stats_size() is sizeof(mlp_stats) as the LIBRARY was built — a host checks it (and mlp_abi_version())
  * against its own header before trusting the layout. */
-#define MLP_ABI_VERSION 4u
+/* Version 5: the struct mlp_certificate was added, with the dual-value / reduced-cost entry points below; mlp_stats is unchanged. */
+#define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
 
@@ -203,6 +204,50 @@ void mlp_solution_trace_get(const mlp_solution* s, uint64_t i, int32_t* phase, i
 /* white-box state for the differential tests (names follow solver.rs:14-58): returns the length,
  * copies min(len, cap) doubles into out when out != NULL; (uint64_t)-1 for an unknown name. */
 uint64_t mlp_solution_state(const mlp_solution* s, const char* what, double* out, uint64_t cap);
+
+/* ---- Dual values, reduced costs and a KKT certificate (no counterpart in the reference: minilp 0.2.2 returns the primal point
+ *      only; these extend Solution::objective / var_value, lib.rs:334-348, to the other half of the solution) ----------------------
+ * Constraint index: 0 .. mlp_solution_num_constraints(s)-1 in the order the constraints were added — mlp_problem_add_constraint
+ * (MPS rows in file order), then the rows mlp_solution_add_constraint and mlp_solution_add_gomory_cut appended, in call order.
+ * Dual value: pi = B^-T c_B of the current basis, from the user's own objective coefficients (not the negated ones of a Maximize
+ * problem, not the artificial costs of the feasibility phase), so pi_c is d objective() / d rhs_c for the current basis, in the
+ * user's direction.  At an optimum of a Minimize problem a <= row has pi <= 0 and a >= row pi >= 0; Maximize reverses both; = rows
+ * take either sign.  A constraint whose slack is basic, or one without terms, returns exactly 0.0.
+ * Reduced cost: r_j = c_j - a_j . pi for every variable, in the user's sense; a basic variable returns exactly 0.0.
+ * Defined for any Solution the engine holds (optimum, budget-limited solve, solve_from_basis, after the mutators): at a basis that is
+ * not optimal they are the multipliers of that basis and the certificate says how far it is from optimal.  Computed on the device
+ * once per solution state and cached (the single-element getters are O(1) after that); every mutator, continue, engine stage and
+ * re-inversion drops the cache.  Reading is side-effect free: the Solution continues pivot for pivot, bit for bit, and its mode-2
+ * basis blob is unchanged.  Sharded solutions are refused with MLP_EINVAL (like the mutators); a wrong length => MLP_EINVAL. */
+uint64_t mlp_solution_num_constraints(const mlp_solution* s);                       /* extends Problem::add_constraint, lib.rs:276 */
+int mlp_solution_dual_values(mlp_solution* s, double* out, uint64_t m);   /* m = mlp_solution_num_constraints; bulk form like iter lib.rs:350 */
+int mlp_solution_dual_value(mlp_solution* s, uint64_t c, double* out);     /* like var_value lib.rs:344, by constraint */
+int mlp_solution_reduced_costs(mlp_solution* s, double* out, uint32_t n);  /* n = mlp_solution_num_vars; bulk form like iter lib.rs:350 */
+int mlp_solution_reduced_cost(mlp_solution* s, uint32_t var, double* out); /* like var_value lib.rs:344 */
+
+/* KKT certificate of the current point against the model as the user stated it (with fix_var's fixings), computed on the device from
+ * x, pi and r.  dual_objective is the Lagrangian bound b . pi + sum_j r_j l_j over every variable (the slacks included), where l_j
+ * is the bound of variable j that minimises r_j x_j in the minimisation sense (the fixed value for a fixed variable); where that
+ * bound is infinite the term takes the current x_j and |r_j| counts toward max_dual_infeasibility.  So when max_dual_infeasibility
+ * is 0, dual_objective is a valid weak-duality bound for any bounds.  Only grows at its end; mlp_certificate_size() is its size as
+ * the library was built. */
+typedef struct mlp_certificate {
+    double primal_objective;       /* c . x recomputed from x */
+    double dual_objective;         /* the Lagrangian bound above */
+    double relative_gap;           /* |primal - dual| / max(1, |primal|) */
+    double max_row_violation;      /* over the constraints: distance of a . x from its allowed side of rhs */
+    int64_t max_row_violation_at;  /* constraint index, -1 when none is violated */
+    double max_bound_violation;    /* over the variables */
+    int64_t max_bound_violation_at;
+    double max_dual_infeasibility; /* max |r_j| where the bound l_j is infinite */
+    int64_t max_dual_infeasibility_at; /* < num_vars: a variable; num_vars + i: the slack of row i; -1 when none */
+    double btran_residual;         /* max over basic columns of |c_j - a_j . pi| before it is zeroed: the accuracy of pi */
+    int64_t btran_residual_at;     /* same numbering as max_dual_infeasibility_at */
+    double bytes;                  /* algorithmic bytes of the certificate's own passes (transposed solve + reduced costs + rows) */
+    double device_ms;              /* their time on the device (HIP events around the launches) */
+} mlp_certificate;
+uint64_t mlp_certificate_size(void);
+int mlp_solution_certificate(mlp_solution* s, mlp_certificate* out);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

@@ -80,6 +80,14 @@ extern "C" {
     pub fn mlp_solution_fix_var(s: *mut *mut mlp_solution, var: u32, val: c_double) -> c_int;
     pub fn mlp_solution_unfix_var(s: *mut *mut mlp_solution, var: u32, was_fixed: *mut c_int) -> c_int;
     pub fn mlp_solution_add_gomory_cut(s: *mut *mut mlp_solution, var: u32) -> c_int;
+    // dual values, reduced costs, KKT certificate (ABI version 5; the certificate struct is read through its size only)
+    pub fn mlp_solution_num_constraints(s: *const mlp_solution) -> u64;
+    pub fn mlp_solution_dual_values(s: *mut mlp_solution, out: *mut c_double, m: u64) -> c_int;
+    pub fn mlp_solution_dual_value(s: *mut mlp_solution, c: u64, out: *mut c_double) -> c_int;
+    pub fn mlp_solution_reduced_costs(s: *mut mlp_solution, out: *mut c_double, n: u32) -> c_int;
+    pub fn mlp_solution_reduced_cost(s: *mut mlp_solution, var: u32, out: *mut c_double) -> c_int;
+    pub fn mlp_solution_certificate(s: *mut mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
+    pub fn mlp_certificate_size() -> u64;
     pub fn mlp_solution_continue(s: *mut mlp_solution, pivot_budget: i64) -> c_int;
     pub fn mlp_solution_budget_exhausted(s: *const mlp_solution) -> c_int;
     pub fn mlp_solution_reinvert(s: *mut mlp_solution, max_diff: *mut c_double) -> c_int;

@@ -352,6 +352,32 @@ impl Solution {
         &self.values()[var.0]
     }
 
+    /// Number of constraints: those of the `Problem` in the order they were added, then the ones `add_constraint` and
+    /// `add_gomory_cut` appended, in call order (extension: no counterpart in the reference).
+    pub fn num_constraints(&self) -> usize {
+        unsafe { sys::mlp_solution_num_constraints(self.raw) as usize }
+    }
+
+    /// Dual value (shadow price) of constraint `c` at the current basis: d objective / d rhs_c, in the problem's direction
+    /// (extension: no counterpart in the reference).
+    pub fn dual_value(&self, c: usize) -> f64 {
+        assert!(c < self.num_constraints());
+        let mut out = 0.0f64;
+        let st = unsafe { sys::mlp_solution_dual_value(self.raw, c as u64, &mut out) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        out
+    }
+
+    /// Reduced cost c_j - a_j . pi of a variable (0 for a basic one), in the problem's direction (extension: no counterpart in
+    /// the reference).
+    pub fn reduced_cost(&self, var: Variable) -> f64 {
+        assert!(var.0 < self.num_vars);
+        let mut out = 0.0f64;
+        let st = unsafe { sys::mlp_solution_reduced_cost(self.raw, var.0 as u32, &mut out) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        out
+    }
+
     /// Iterate over the variable-value pairs of the solution.
     pub fn iter(&self) -> SolutionIter {
         SolutionIter { solution: self, var_idx: 0 }

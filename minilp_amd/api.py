@@ -47,7 +47,16 @@ class MlpStats(C.Structure):
                    ("factor_switches", C.c_uint64), ("factor_bump", C.c_uint64), ("factor_bump_max", C.c_uint64)])  # appended in ABI version 4 (the struct only grows at its end from here on)
 
 
-ABI_VERSION = 4  # include/minilp_hip.h: MLP_ABI_VERSION
+class MlpCertificate(C.Structure):  # include/minilp_hip.h: mlp_certificate (only grows at its end)
+    _fields_ = [("primal_objective", C.c_double), ("dual_objective", C.c_double), ("relative_gap", C.c_double),
+                ("max_row_violation", C.c_double), ("max_row_violation_at", C.c_int64),
+                ("max_bound_violation", C.c_double), ("max_bound_violation_at", C.c_int64),
+                ("max_dual_infeasibility", C.c_double), ("max_dual_infeasibility_at", C.c_int64),
+                ("btran_residual", C.c_double), ("btran_residual_at", C.c_int64),
+                ("bytes", C.c_double), ("device_ms", C.c_double)]
+
+
+ABI_VERSION = 5  # include/minilp_hip.h: MLP_ABI_VERSION
 
 
 class MlpIterInfo(C.Structure):  # include/minilp_hip.h: mlp_iter_info
@@ -88,6 +97,9 @@ def lib():
     if L.mlp_abi_version() != ABI_VERSION or L.mlp_stats_size() != C.sizeof(MlpStats):
         raise ImportError(f"{_SO} was built from another version of include/minilp_hip.h (ABI {L.mlp_abi_version()}, mlp_stats "
                           f"{L.mlp_stats_size()} bytes; this binding: ABI {ABI_VERSION}, {C.sizeof(MlpStats)} bytes): rebuild it")
+    sig("mlp_certificate_size", u64)
+    if L.mlp_certificate_size() != C.sizeof(MlpCertificate):
+        raise ImportError(f"{_SO}: mlp_certificate is {L.mlp_certificate_size()} bytes, this binding {C.sizeof(MlpCertificate)}: rebuild it")
     sig("mlp_last_error", C.c_char_p)
     sig("mlp_device_count", i32)
     sig("mlp_set_device", i32, i32)
@@ -139,6 +151,12 @@ def lib():
     sig("mlp_mps_var_index", i64, vp, C.c_char_p)
     sig("mlp_mps_problem", vp, vp)
     sig("mlp_util_min_cut", C.c_double, u32, pdbl, C.POINTER(C.c_uint8))
+    sig("mlp_solution_num_constraints", u64, vp)
+    sig("mlp_solution_dual_values", i32, vp, pdbl, u64)
+    sig("mlp_solution_dual_value", i32, vp, u64, pdbl)
+    sig("mlp_solution_reduced_costs", i32, vp, pdbl, u32)
+    sig("mlp_solution_reduced_cost", i32, vp, u32, pdbl)
+    sig("mlp_solution_certificate", i32, vp, C.POINTER(MlpCertificate))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -347,6 +365,40 @@ class Solution:
 
     def __iter__(self):  # lib.rs:350 iter()
         return iter(enumerate(self.values()))
+
+    # ---- dual values, reduced costs, KKT certificate (include/minilp_hip.h: mlp_solution_dual_values ...; user's objective sense)
+    @property
+    def num_constraints(self):
+        """Constraints of the model: Problem.add_constraint order, then Solution.add_constraint / add_gomory_cut in call order."""
+        return lib().mlp_solution_num_constraints(self._h)
+
+    def dual_values(self):
+        """pi = B^-T c_B by constraint: d objective() / d rhs_c at the current basis (0.0 where the slack is basic)."""
+        a = np.zeros(self.num_constraints, dtype=np.float64)
+        _raise(lib().mlp_solution_dual_values(self._h, _p(a, C.c_double), len(a)))
+        return a
+
+    def dual_value(self, c):
+        out = C.c_double()
+        _raise(lib().mlp_solution_dual_value(self._h, int(c), C.byref(out)))
+        return out.value
+
+    def reduced_costs(self):
+        """r_j = c_j - a_j . pi by variable (0.0 for a basic variable)."""
+        a = np.zeros(self.num_vars, dtype=np.float64)
+        _raise(lib().mlp_solution_reduced_costs(self._h, _p(a, C.c_double), len(a)))
+        return a
+
+    def reduced_cost(self, var):
+        out = C.c_double()
+        _raise(lib().mlp_solution_reduced_cost(self._h, int(var), C.byref(out)))
+        return out.value
+
+    def certificate(self):
+        """KKT certificate of the current point (mlp_certificate) as a dict."""
+        c = MlpCertificate()
+        _raise(lib().mlp_solution_certificate(self._h, C.byref(c)))
+        return {n: getattr(c, n) for n, _ in MlpCertificate._fields_}
 
     def add_constraint(self, expr, cmp_op, rhs):
         idx, val = _terms(expr)

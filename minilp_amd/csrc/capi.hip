@@ -9,13 +9,31 @@
 
 using namespace mlp;
 
+
 struct mlp_problem {
     ProblemData pd;
 };
 struct mlp_solution {
     Engine* eng = nullptr;
+    // dual values / reduced costs / certificate of the current state (mlp_solution_dual_values ...), computed once per state
+    bool duals_valid = false;
+    Engine::Duals duals;
     ~mlp_solution() { delete eng; }
 };
+// every entry point that can change the state of a solution drops the cached duals
+static void stale(mlp_solution* s) {
+    if (s) s->duals_valid = false;
+}
+static const Engine::Duals& duals_of(mlp_solution* s) {
+    if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+    // (any solution sharding was enabled on, a one-rank pump included: its pivots belong to the collective)
+    if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "duals are not available on a sharded solution");
+    if (!s->duals_valid) {
+        s->eng->compute_duals(s->duals);
+        s->duals_valid = true;
+    }
+    return s->duals;
+}
 struct mlp_mps {
     MpsData d;
 };
@@ -166,6 +184,7 @@ int mlp_solution_set_sampling(mlp_solution* s, int every_iteration) {
     });
 }
 int mlp_solution_continue(mlp_solution* s, int64_t budget) {
+        stale(s);
     return guarded([&] {
         if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
         s->eng->pivot_budget = budget;
@@ -185,6 +204,7 @@ int mlp_engine_open(mlp_solution* s, mlp_iter_info* out) {
     int rc = guarded([&] {
         if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
         Engine::StepInfo si{};
+        stale(s);
         status = s->eng->step_open(&si);
         copy_info(si, out);
     });
@@ -195,6 +215,7 @@ int mlp_engine_stage(mlp_solution* s, int stage, mlp_iter_info* out) {
     int rc = guarded([&] {
         if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
         Engine::StepInfo si{};
+        stale(s);
         status = s->eng->step_stage(stage, &si);
         copy_info(si, out);
     });
@@ -204,6 +225,7 @@ int mlp_solution_budget_exhausted(const mlp_solution* s) { return (s && s->eng->
 int mlp_solution_reinvert(mlp_solution* s, double* max_diff) {
     return guarded([&] {
         if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
+        stale(s);
         double d = s->eng->reinvert(true);
         if (max_diff) *max_diff = d;
     });
@@ -216,16 +238,62 @@ int mlp_solution_recompute_basic_values(mlp_solution* s) {
         // mlp_solution_objective and the values agree afterwards
         // — except inside the artificial-objective feasibility phase of a budget-paused solve (d = +-1 / 0 there: initial_solve
         // itself never recomputes d on a budget resume); the basic values are recomputed, d and the objective are left alone
+        stale(s);
         s->eng->recalc_basic_vals();
         if (!s->eng->in_artificial_phase()) s->eng->refresh_objective();
     });
 }
 uint32_t mlp_abi_version(void) { return MLP_ABI_VERSION; }
+uint64_t mlp_certificate_size(void) { return (uint64_t)sizeof(mlp_certificate); }
+
+uint64_t mlp_solution_num_constraints(const mlp_solution* s) { return s ? (uint64_t)s->eng->num_constraints() : 0; }
+int mlp_solution_dual_values(mlp_solution* s, double* out, uint64_t m) {
+    return guarded([&] {
+        const Engine::Duals& d = duals_of(s);
+        if (!out || m != d.pi.size()) throw MlpError(MLP_EINVAL, "dual_values: length must be mlp_solution_num_constraints");
+        std::memcpy(out, d.pi.data(), sizeof(double) * d.pi.size());
+    });
+}
+int mlp_solution_dual_value(mlp_solution* s, uint64_t c, double* out) {
+    return guarded([&] {
+        const Engine::Duals& d = duals_of(s);
+        if (!out || c >= d.pi.size()) throw MlpError(MLP_EINVAL, "constraint out of range");
+        *out = d.pi[c];
+    });
+}
+int mlp_solution_reduced_costs(mlp_solution* s, double* out, uint32_t n) {
+    return guarded([&] {
+        const Engine::Duals& d = duals_of(s);
+        if (!out || n != d.r.size()) throw MlpError(MLP_EINVAL, "reduced_costs: length must be mlp_solution_num_vars");
+        std::memcpy(out, d.r.data(), sizeof(double) * d.r.size());
+    });
+}
+int mlp_solution_reduced_cost(mlp_solution* s, uint32_t var, double* out) {
+    return guarded([&] {
+        const Engine::Duals& d = duals_of(s);
+        if (!out || var >= d.r.size()) throw MlpError(MLP_EINVAL, "variable out of range");
+        *out = d.r[var];
+    });
+}
+int mlp_solution_certificate(mlp_solution* s, mlp_certificate* out) {
+    return guarded([&] {
+        const Engine::Duals& d = duals_of(s);
+        if (!out) throw MlpError(MLP_EINVAL, "NULL certificate");
+        std::memset(out, 0, sizeof(*out));
+        out->primal_objective = d.primal_obj; out->dual_objective = d.dual_obj; out->relative_gap = d.rel_gap;
+        out->max_row_violation = d.max_row_viol; out->max_row_violation_at = d.row_viol_at;
+        out->max_bound_violation = d.max_bound_viol; out->max_bound_violation_at = d.bound_viol_at;
+        out->max_dual_infeasibility = d.max_dual_inf; out->max_dual_infeasibility_at = d.dual_inf_at;
+        out->btran_residual = d.btran_residual; out->btran_residual_at = d.btran_residual_at;
+        out->bytes = d.bytes; out->device_ms = d.device_ms;
+    });
+}
 uint64_t mlp_stats_size(void) { return (uint64_t)sizeof(mlp_stats); }
 
 int mlp_solution_enable_sharding(mlp_solution* s, int rank, int world, const char* shm_name) {
     return guarded([&] {
         if (!s || !shm_name) throw MlpError(MLP_EINVAL, "NULL solution / rendezvous name");
+        stale(s);
         s->eng->enable_sharding(rank, world, shm_name);
     });
 }
@@ -233,6 +301,7 @@ int mlp_solution_enable_sharding(mlp_solution* s, int rank, int world, const cha
 int mlp_solution_enable_sharding_ex(mlp_solution* s, int rank, int world, const char* shm_name, const char* transport, const void* rccl_id) {
     return guarded([&] {
         if (!s || !shm_name) throw MlpError(MLP_EINVAL, "NULL solution / rendezvous name");
+        stale(s);
         s->eng->enable_sharding(rank, world, shm_name, transport, rccl_id);
     });
 }
@@ -283,6 +352,7 @@ int mlp_solution_add_constraint(mlp_solution** s, const uint32_t* vars, const do
         tmp.add_constraint(vars, coeffs, k, op, rhs);
         refuse_if_sharded(*s);
         (*s)->eng->pivot_budget = -1;
+        stale(*s);
         (*s)->eng->add_constraint(tmp.cons[0]);
     }));
 }
@@ -292,6 +362,7 @@ int mlp_solution_fix_var(mlp_solution** s, uint32_t var, double val) {
         if ((int)var >= (*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:391)");
         refuse_if_sharded(*s);
         (*s)->eng->pivot_budget = -1;
+        stale(*s);
         (*s)->eng->fix_var((int)var, val);
     }));
 }
@@ -301,6 +372,7 @@ int mlp_solution_unfix_var(mlp_solution** s, uint32_t var, int* was_fixed) {
         if ((int)var >= (*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:400)");
         refuse_if_sharded(*s);
         (*s)->eng->pivot_budget = -1;
+        stale(*s);
         *was_fixed = (*s)->eng->unfix_var((int)var) ? 1 : 0;
     }));
 }
@@ -310,6 +382,7 @@ int mlp_solution_add_gomory_cut(mlp_solution** s, uint32_t var) {
         if ((int)var >= (*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:420)");
         refuse_if_sharded(*s);
         (*s)->eng->pivot_budget = -1;
+        stale(*s);
         (*s)->eng->add_gomory_cut((int)var);
     }));
 }

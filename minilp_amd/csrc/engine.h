@@ -164,6 +164,18 @@ public:
     double cur_obj_val();                                                   // solver.rs:51
     Engine* clone();                                                        // #[derive(Clone)] solver.rs:14
     double reinvert(bool replace);  // from-scratch nucleus inversion; returns max |W - W_fresh|
+    // Dual values, reduced costs and the KKT certificate of the current basis (duals.inc; include/minilp_hip.h
+    // mlp_solution_dual_values ...): pi by CONSTRAINT (0 for a constraint without terms, which has no row), r by structural variable,
+    // both in the user's objective sense.  Reads the state only: the solve continues bit for bit as if nothing had been read.
+    struct Duals {
+        std::vector<double> pi, r;
+        double primal_obj = 0, dual_obj = 0, rel_gap = 0;
+        double max_row_viol = 0, max_bound_viol = 0, max_dual_inf = 0, btran_residual = 0;
+        int64_t row_viol_at = -1, bound_viol_at = -1, dual_inf_at = -1, btran_residual_at = -1;
+        double bytes = 0, device_ms = 0;
+    };
+    void compute_duals(Duals& out);
+    size_t num_constraints() const { return h_cons_row.size(); }
     double last_reinvert_scale = 0.0;  // max |W_fresh| of that comparison (state "reinvert_scale")
     // Basis checkpoint (include/minilp_hip.h: mlp_solution_save_basis / mlp_problem_solve_from_basis).
     // mode 0: basic / non-basic sets, flags and x_N; 1: + steepest-edge weights as f32; 2: + x_B, d, gamma,
@@ -199,6 +211,7 @@ private:
     // --- host mirror (integer bookkeeping + the matrix for rebuilds)
     int m_ = 0, N_ = 0, k_ = 0, cap_ = 0;
     std::vector<double> h_obj, h_lo, h_hi, h_rhs;
+    std::vector<int> h_cons_row;  // constraint (Problem / Solution::add_constraint order) -> row; -1 for one without terms (no row)
     std::vector<int> h_rptr, h_rcol;
     std::vector<double> h_rval;
     // Host view of the columns: only what the host logic needs — the length of every column and, for singleton

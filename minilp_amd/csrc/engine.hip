@@ -1276,12 +1276,15 @@ void Engine::try_new(const ProblemData& pd) {
     h_rhs.clear();
     std::vector<double> xB, loB, hiB;
     std::vector<const Constraint*> kept;
+    h_cons_row.clear();
     for (const Constraint& c : pd.cons) {
         if (c.idx.empty()) {
             bool taut = c.op == 0 ? (0.0 == c.rhs) : c.op == 1 ? (0.0 <= c.rhs) : (0.0 >= c.rhs);
+            h_cons_row.push_back(-1);
             if (taut) continue;
             throw LpFail{1};
         }
+        h_cons_row.push_back((int)kept.size());
         kept.push_back(&c);
     }
     m_ = (int)kept.size();
@@ -2820,11 +2823,15 @@ void Engine::add_constraint(Constraint c) {
     ensure_beta();
     if (c.idx.empty()) {
         bool taut = c.op == 0 ? (0.0 == c.rhs) : c.op == 1 ? (0.0 <= c.rhs) : (0.0 >= c.rhs);
-        if (taut) return;
+        if (taut) {
+            h_cons_row.push_back(-1);  // (a constraint without terms gets no row; its dual value is 0)
+            return;
+        }
         throw LpFail{1};
     }
     fetch_values();
     const int slack = N_, row = m_;
+    h_cons_row.push_back(row);
     double smin = c.op == 1 ? 0.0 : c.op == 2 ? -INF : 0.0;
     double smax = c.op == 1 ? INF : 0.0;
     double lhs = 0.0;  // solver.rs:587-595
@@ -3244,6 +3251,7 @@ Engine* Engine::clone() {
     e->num_vars = num_vars; e->direction = direction;
     e->m_ = m_; e->N_ = N_;
     e->h_obj = h_obj; e->h_lo = h_lo; e->h_hi = h_hi; e->h_rhs = h_rhs;
+    e->h_cons_row = h_cons_row;
     e->h_rptr = h_rptr; e->h_rcol = h_rcol; e->h_rval = h_rval;
     e->h_colnnz = h_colnnz; e->h_single_row = h_single_row; e->h_single_val = h_single_val;
     e->max_col_nnz_ = max_col_nnz_; e->max_row_nnz_ = max_row_nnz_; e->amax_ = amax_; e->fpull_on_ = fpull_on_;
@@ -3426,4 +3434,77 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
     return tmp.size();
 }
 
+}  // namespace mlp
+
+namespace mlp {
+// Dual values, reduced costs and the KKT certificate of the current basis (duals.inc).  Nothing here writes solver state: the
+// kernels write private buffers, the pending rank-1 terms are applied, not folded, and the compact factor is not re-peeled.
+void Engine::compute_duals(Duals& out) {
+    if (sharded()) throw MlpError(-1, "duals are not available on a sharded solution");
+    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    const DevView& dv = hview;
+    const Geom g = geom();
+    const int m = m_, N = N_, nv = num_vars, k = fac_on_ ? 0 : k_;
+    const int nbv = duals_var_blocks(g, N), nbr = duals_row_blocks(g);
+    DevBuf<double> y, cb, tK, part, lrh, r, pi, bpart, rpart, cert, rhs;
+    DevBuf<double2> rv;
+    y.ensure((size_t)m + 1, 0, st); cb.ensure((size_t)m + 1, 0, st); r.ensure((size_t)N + 1, 0, st); pi.ensure((size_t)m + 1, 0, st);
+    bpart.ensure((size_t)nbv * 8, 0, st); rpart.ensure((size_t)nbr * 8, 0, st); cert.ensure(16, 0, st);
+    lrh.ensure(LR_MAX, 0, st);
+    rhs.upload(h_rhs, st);
+    if (fac_on_) {
+        rv.ensure((size_t)m + 1, 0, st);
+        HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
+    }
+    if (k > 0) {
+        tK.ensure((size_t)k, 0, st);
+        part.ensure((size_t)duals_wt_stripes(k) * dv.ld, 0, st);
+    }
+    DualsBufs b{};
+    b.y = y.p; b.cb = cb.p; b.rv = rv.p; b.tK = tK.p; b.part = part.p; b.lrh = lrh.p; b.r = r.p; b.pi = pi.p;
+    b.bpart = bpart.p; b.rpart = rpart.p; b.cert = cert.p; b.rhs = rhs.p;
+    b.N = N; b.nv = nv; b.k = k; b.fac = fac_on_ ? 1 : 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHECK(hipEventCreate(&e0));
+    HIPCHECK(hipEventCreate(&e1));
+    HIPCHECK(hipEventRecord(e0, st));
+    launch_duals(dv, g, b, st);
+    HIPCHECK(hipEventRecord(e1, st));
+    HIPCHECK(hipGetLastError());
+    std::vector<double> hr((size_t)N), hpi((size_t)m), hc(16);
+    if (N) HIPCHECK(hipMemcpyAsync(hr.data(), r.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    if (m) HIPCHECK(hipMemcpyAsync(hpi.data(), pi.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(hc.data(), cert.p, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    // user's objective sense: a Maximize problem is solved as the minimisation of -c (lib.rs:235-238)
+    const double sg = direction == 1 ? -1.0 : 1.0;
+    out.r.resize((size_t)nv);
+    for (int j = 0; j < nv; ++j) out.r[j] = hr[j] == 0.0 ? 0.0 : sg * hr[j];
+    out.pi.assign(h_cons_row.size(), 0.0);
+    for (size_t c = 0; c < h_cons_row.size(); ++c)
+        if (h_cons_row[c] >= 0) out.pi[c] = hpi[h_cons_row[c]] == 0.0 ? 0.0 : sg * hpi[h_cons_row[c]];
+    const double primal = hc[0], lagr = hc[8] + hc[1];  // c.x ; b.y + sum_j r_j l_j (minimisation sense)
+    out.primal_obj = sg * primal;
+    out.dual_obj = sg * lagr;
+    out.rel_gap = std::fabs(primal - lagr) / std::max(1.0, std::fabs(primal));
+    out.max_bound_viol = hc[2]; out.bound_viol_at = (int64_t)hc[3];
+    out.max_dual_inf = hc[4]; out.dual_inf_at = (int64_t)hc[5];
+    out.btran_residual = hc[6]; out.btran_residual_at = (int64_t)hc[7];
+    out.max_row_viol = hc[10]; out.row_viol_at = -1;
+    if (hc[11] >= 0.0) {  // row -> constraint
+        for (size_t c = 0; c < h_cons_row.size(); ++c)
+            if (h_cons_row[c] == (int64_t)hc[11]) { out.row_viol_at = (int64_t)c; break; }
+    }
+    // algorithmic bytes: one read of W0 (8 k^2) and of the pending terms (16 J k), or the compact factor's solve (counted as its
+    // pending terms, 16 J m); two passes over A (12 bytes per entry + an 8-byte gather), the per-variable and per-row vectors
+    const double nz = (double)h_rcol.size();
+    const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
+    out.bytes = 8.0 * k * k + 16.0 * J * (fac_on_ ? m : k) + 2.0 * 20.0 * nz + 60.0 * N + 48.0 * m;
+    out.device_ms = ms;
+}
 }  // namespace mlp

@@ -525,6 +525,27 @@ void launch_str_reset(const DevView& dv, hipStream_t st);  // sparse tableau row
 void launch_checksum_w(const DevView& dv, unsigned long long* out, hipStream_t st);  // order-independent checksum of W[0:k, 0:k] and the slot maps (tests)
 void launch_fold_lowrank(const DevView& dv, const Geom& g, hipStream_t st);  // W0 += U^T V, nlow := 0 (host-requested flush)
 void launch_gauss_jordan(double* Kd, double* Winv, int k, int ld, int* d_flag, double* d_scratch, hipStream_t st);
+// dual values, reduced costs and the KKT certificate of the current basis (duals.inc): reads the solver state, writes only these buffers
+struct DualsBufs {
+    double* y;      // m: B^-T c_B by row (internal costs)
+    double* cb;     // m: c_B by position
+    double2* rv;    // m: private rv of the compact factor's solve (zeroed by the caller)
+    double* tK;     // cap: c_K - F^T y_S
+    double* part;   // duals_wt_stripes(k) x ld: partial column sums of W0^T t_K
+    double* lrh;    // LR_MAX: U_j . t_K of the pending terms
+    double* r;      // N: reduced costs by variable (basic: exactly 0)
+    double* pi;     // m: dual value by row (basic slack: exactly 0)
+    double* bpart;  // duals_var_blocks x 8: partials of the reduced-cost pass
+    double* rpart;  // duals_row_blocks x 8: partials of the row pass
+    double* cert;   // 16: [0..7] variable pass, [8..15] row pass (s0, s1, max0, idx0, max1, idx1, max2, idx2)
+    const double* rhs;  // m
+    int N, nv;      // total / structural variables
+    int k, fac;     // nucleus size (explicit inverse), compact factor active
+};
+void launch_duals(const DevView& dv, const Geom& g, const DualsBufs& b, hipStream_t st);
+int duals_var_blocks(const Geom& g, int N);
+int duals_row_blocks(const Geom& g);
+int duals_wt_stripes(int k);
 // blocked in-place Gauss-Jordan inversion of the nucleus held in dv.W (inverse.inc); *flag = 1: singular
 void launch_blocked_inverse(const DevView& dv, int k, double* rowbuf, int nrowbuf, int* piv, int* src, double* prow, double* ckey,
                             int* cidx, int* flag, hipStream_t st);

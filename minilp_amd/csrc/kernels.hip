@@ -5375,6 +5375,8 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
     (void)hipMemsetAsync(Kd, 0, sizeof(double) * (size_t)k * dv.ld, st);
     hipLaunchKernelGGL(k_build_nucleus<16>, dim3(blocks_for((long)k * 16)), dim3(BLK), 0, st, dv, Kd, k);
 }
+#include "duals.inc"  // dual values, reduced costs and the KKT certificate (side-effect free reads of the solver state)
+
 void launch_gauss_jordan(double* Kd, double* Winv, int k, int ld, int* d_flag, double* d_scratch, hipStream_t st) {
     if (k <= 0) return;
     size_t tot = (size_t)k * k;

@@ -3,8 +3,9 @@ a CPU without any LP solver: a primal point x and a dual point y with
     A x <= b, x >= 0        (primal feasible)
     A^T y >= c, y >= 0      (dual feasible)
     c.x == b.y              (no duality gap)
-Weak duality then proves both optimal.  y comes from the reduced costs of the non-basic slack columns
-(d_slack_i = -pi_i, solver.rs:1199-1231); basic slacks have y_i = 0.  Writes gpurun_out/cfg4_certificate.npz.
+Weak duality then proves both optimal.  y is the public dual vector of the solution (Solution.dual_values():
+pi = B^-T c_B in the user's objective sense, exactly 0 where a slack is basic); the engine's own KKT certificate
+(Solution.certificate()) is printed next to the host's check.  Writes the certificate as an .npz file.
 usage: [CERTIFY_CHUNK=25000] certify_cfg4.py [rows cols nnz_per_row seed]   (CERTIFY_CHUNK: also write the
 wall-time curve of the solve, one point per chunk, to gpurun_out/cfg4_solve_curve.json)"""
 import os, sys, time, json
@@ -35,11 +36,7 @@ else:
 wall = time.time() - t
 st = s.stats()
 x = np.asarray(s.values())
-nb_vars = s.state("nb_vars").astype(np.int64)
-d = s.state("nb_var_obj_coeffs")
-y = np.zeros(m)
-slack = nb_vars >= n
-y[nb_vars[slack] - n] = d[slack]
+y = s.dual_values()
 A = sp.csr_matrix((lp["data"], lp["indices"], lp["indptr"]), shape=(m, n))
 c, b = lp["obj"], lp["rhs"]
 cert = dict(rows=m, cols=n, nnz_per_row=k, seed=seed, pivots=int(st["iterations"]), solve_wall_s=wall,
@@ -48,6 +45,7 @@ cert = dict(rows=m, cols=n, nnz_per_row=k, seed=seed, pivots=int(st["iterations"
             max_dual_violation=float(max((c - A.T @ y).max(), (-y).max(), 0.0)),
             nucleus_size=int(st["nucleus_size"]), max_pivot_err=st["max_pivot_err"])
 cert["relative_gap"] = abs(cert["primal_objective"] - cert["dual_objective"]) / max(1.0, abs(cert["primal_objective"]))
+cert["device_certificate"] = s.certificate()
 print(json.dumps(cert, indent=1), flush=True)
 if curve:  # (pivots, wall seconds, nucleus size) at every chunk boundary, and the chunk's microseconds per pivot
     rows, prev = [], (0, 0.0, 0)
