@@ -3370,6 +3370,8 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
         tmp = {(double)n_, (double)p_};
     } else if (w == "fpull") {  // pulled F product: [in use now, builds of the packed copy, pivot count at the last build]
         tmp = {(double)(hview.fpk_on ? 1 : 0), (double)fpk_builds_, (double)fpk_built_at_, (double)(fpull_supported(hview, geom()) ? 1 : 0)};
+    } else if (w == "ratio_primal_form") {  // what launch_ratio_primal runs at this size: 0 one block, 1 the fused grid, 2 two launches with stride loops
+        tmp = {(double)ratio_primal_form(hview, geom())};
     } else if (w == "golive_checks") {  // fingerprint comparisons passed at the go-live point of the deferred sharding
         tmp = {(double)golive_checks_};
     } else if (w == "shard_live") {

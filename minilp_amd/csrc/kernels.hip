@@ -4886,9 +4886,13 @@ bool tk_rides_ratio_small(const DevView& dv, const Geom& g) {
     return nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m;
 }
 // Pulled F product (fpull.inc): two launches, neither with an in-kernel wait.  The first reduces over one block per 32 items (m rows + cap
-// slots): the partials travel through red_key / red_key2, which Engine::ensure_red sizes for it.
+// slots): its partials travel through a buffer of their own (DevView.fpk_part), which every block of the second launch folds for itself.
+// The second launch holds PT = 4 positions per thread of its grid_for(m) ratio blocks and has no stride loop: beyond 4 * BLK * 512 =
+// 524 288 rows pass 2 of the Harris test would not see the positions behind that bound (pass 1 does: a wrong leaving row, a spurious
+// flip or unbounded).  The pull is declined there — for the unsharded arm (tk_rides_ratio asks the same) and the sharded one alike —
+// and the pushed product with k_ratio_primal_p1 / _p2 runs, whose loops stride.
 bool fpull_supported(const DevView& dv, const Geom& g) {
-    return dv.fpk_on && dv.fpk_cnt && dv.rowinfo && dv.lrJ > 0;
+    return dv.fpk_on && dv.fpk_cnt && dv.rowinfo && dv.lrJ > 0 && (long)grid_for(g.m) * BLK * 4 >= (long)g.m;
 }
 void launch_fpull_ratio(const DevView& dv, const Geom& g, hipStream_t st, hipEvent_t ftran_done) {
     const long items = (long)g.m + (long)g.cap;
@@ -4902,6 +4906,19 @@ void launch_fpull_ratio(const DevView& dv, const Geom& g, hipStream_t st, hipEve
                  hipLaunchKernelGGL(k_fpull_p2<16>, dim3(nb + blocks_for((long)g.cap * 16) + 1), dim3(BLK), 0, st, dv, nb, n1),
                  hipLaunchKernelGGL(k_fpull_p2<64>, dim3(nb + blocks_for((long)g.cap * 64) + 1), dim3(BLK), 0, st, dv, nb, n1));
 }
+// The form of the primal Harris test without a t_K ride: 0 one block (small model), 1 the fused grid (both passes in one launch, PT = 4
+// positions per thread in registers), 2 pass 1 and pass 2 as two launches whose loops stride (also what state("ratio_primal_form") reports).
+int ratio_primal_form(const DevView& dv, const Geom& g) {
+    if (dv.world <= 1 && g.m <= 16384 && ratio_one_enabled()) return 0;
+    const int nb = grid_for(g.m);
+    // The fused kernel's blocks wait inside the launch for its last-arriving block, which is only safe while the
+    // WHOLE grid is co-resident: bound the grid by what this device (or partition: CPX mode, CU mask) can hold at
+    // once, per the occupancy calculator, with a 2x margin for kernels of other queues sharing the CUs.  The engine
+    // selects the two-launch form (Geom.ratio_two) when MLP_RATIO_TWO_KERNELS is set, when the ranks of a sharded solve
+    // share one device, and for good after a wait has ever timed out (ITER_STALL).
+    const int max_coresident = g.ratio_two ? 0 : coresident_half(reinterpret_cast<const void*>(k_ratio_primal_fused), 0);
+    return (nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m) ? 1 : 2;
+}
 void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride) {
     if (tk_ride) {  // (the caller asked tk_rides_ratio / tk_rides_ratio_small first); 2: small nucleus, y_S on the fly
         const int nb = grid_for(g.m);
@@ -4910,18 +4927,13 @@ void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStrea
                            tk_ride == 2 ? 1 : 0);
         return;
     }
-    if (dv.world <= 1 && g.m <= 16384 && ratio_one_enabled()) {  // small model: one block, no grid-wide reduction (RATIO_ONE_MAX)
+    const int form = ratio_primal_form(dv, g);
+    if (form == 0) {  // small model: one block, no grid-wide reduction (RATIO_ONE_MAX)
         hipLaunchKernelGGL(k_ratio_primal_one, dim3(1), dim3(BLK), 0, st, dv, use_pse);
         return;
     }
     const int nb = grid_for(g.m);
-    // The fused kernel's blocks wait inside the launch for its last-arriving block, which is only safe while the
-    // WHOLE grid is co-resident: bound the grid by what this device (or partition: CPX mode, CU mask) can hold at
-    // once, per the occupancy calculator, with a 2x margin for kernels of other queues sharing the CUs.  The engine
-    // selects the two-launch form (Geom.ratio_two) when MLP_RATIO_TWO_KERNELS is set, when the ranks of a sharded solve
-    // share one device, and for good after a wait has ever timed out (ITER_STALL).
-    const int max_coresident = g.ratio_two ? 0 : coresident_half(reinterpret_cast<const void*>(k_ratio_primal_fused), 0);
-    if (nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m) {  // every element fits the fused kernel's registers
+    if (form == 1) {  // every element fits the fused kernel's registers
         hipLaunchKernelGGL(k_ratio_primal_fused, dim3(nb), dim3(BLK), 0, st, dv, use_pse, 0, 0, 0);  // both passes + BTRAN head + plan
         return;
     }

@@ -36,9 +36,12 @@ def _close(name, it, got, want, mask=None):
     return err / scale
 
 
-def _step_and_compare(lp, max_iters):
-    sg = lpgen.build_problem(M.Problem, lp).solve(budget=0, trace=True)
-    so = lpgen.build_problem(O.Problem, lp).solve(budget=0, trace=True)
+def _step_and_compare(lp, max_iters, start=0):
+    """Step `max_iters` iterations on both sides after `start` iterations of an ordinary solve (tests/test_large_dims.py steps a
+    two-phase instance from behind its phase switch)."""
+    sg = lpgen.build_problem(M.Problem, lp).solve(budget=start, trace=True)
+    so = lpgen.build_problem(O.Problem, lp).solve(budget=start, trace=True)
+    assert [t[:5] for t in sg.trace()] == [t[:5] for t in so.trace()]
     so.set_capture(True)
     worst, it, phases = {}, 0, set()
     while it < max_iters:

@@ -51,7 +51,8 @@ def worker(rank, world, port, m, n, k, pivots, out, family="sparse"):
     dt = time.time() - t0
     tr = [t[:5] for t in s.trace()]
     transport = s.transport()
-    res = dict(rank=rank, n=len(tr), obj=s.objective(), dt=dt, trace=tr, done=not s.budget_exhausted, factor=int(s.stats()["factor_active"]))
+    res = dict(rank=rank, n=len(tr), obj=s.objective(), dt=dt, trace=tr, done=not s.budget_exhausted, factor=int(s.stats()["factor_active"]),
+               fpull=int(s.state("fpull")[3]))   # the pulled F product (csrc/fpull.inc) is supported at this size
     gathered = [None] * world
     dist.all_gather_object(gathered, res)
     if rank == 0:
@@ -67,6 +68,7 @@ def worker(rank, world, port, m, n, k, pivots, out, family="sparse"):
         print("go-live fingerprint checks passed on rank 0:", golive, flush=True)
         print("transport:", transport, "| devices visible:", ndev, "| factor active on rank 0:", int(ref.stats()["factor_active"]), flush=True)
         print("compact factor active on the sharded ranks:", [g["factor"] for g in gathered], flush=True)
+        print("pulled F product supported on the sharded ranks:", [g["fpull"] for g in gathered], flush=True)
         print("sharded world=%d: pivots=%s obj=%s dt=%s | unsharded pivots=%d obj=%.12g | traces identical: %s" % (
             world, [g["n"] for g in gathered], ["%.12g" % g["obj"] for g in gathered], ["%.3f" % g["dt"] for g in gathered],
             len(rtr), ref.objective(), ok), flush=True)
