@@ -38,6 +38,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * prefix; mlp_stats_size() is sizeof(mlp_stats) as the LIBRARY was built — a host checks it (and mlp_abi_version())
  * against its own header before trusting the layout. */
 /* Version 5: the struct mlp_certificate was added, with the dual-value / reduced-cost entry points below; mlp_stats is unchanged. */
+/* Still version 5: the basis-status / ranging entry points further down are purely additive — new functions and one new struct
+ * (mlp_ranging_info, with its own mlp_ranging_info_size()); mlp_stats and mlp_certificate are untouched, no existing layout moved. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -248,6 +250,48 @@ typedef struct mlp_certificate {
 } mlp_certificate;
 uint64_t mlp_certificate_size(void);
 int mlp_solution_certificate(mlp_solution* s, mlp_certificate* out);
+
+/* ---- Basis status, cost ranging and rhs ranging (the other half of a sensitivity report: how far may a cost coefficient or a
+ *      right-hand side move before the basis changes and the dual values / reduced costs above stop being valid?) -------------------
+ * All of it is stated in the engine's internal minimisation form  min c.x, A x + s = b  (slack s = rhs - activity, bounds by operator:
+ * <= [0, inf), >= (-inf, 0], = [0, 0]) at the CURRENT basis, whatever it is; the ranges are meaningful at an optimum and are the same
+ * formulas, never an error, on a budget-limited solve.
+ * Basis status, per structural variable and per constraint (= its slack): MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE
+ * (non-basic at neither bound), MLP_NB_FIXED (mlp_solution_fix_var, or lo == hi).  A constraint without terms has no row: MLP_BASIC.
+ * Cost range [lo_j, hi_j] of variable j, containing c_j: the values of c_j for which every reduced-cost sign condition the basis needs
+ * keeps holding.  With r the (internal) reduced costs:
+ *   non-basic j: at lower [c_j - r_j, +inf); at upper (-inf, c_j - r_j]; MLP_NB_FREE [c_j, c_j]; MLP_NB_FIXED (-inf, +inf);
+ *   basic j at position p: alpha_i = (e_p^T B^-1) a_i over ALL non-basic columns i (slack columns included),
+ *     delta+ = min r_i / alpha_i over {i at lower, alpha_i > 0} u {i at upper, alpha_i < 0} u {i MLP_NB_FREE, alpha_i != 0: 0},
+ *     delta- = max r_i / alpha_i over the mirrored sets; MLP_NB_FIXED columns impose nothing; an empty set gives -+inf;
+ *     the range is [c_j + delta-, c_j + delta+].
+ * Rhs range [lo_c, hi_c] of constraint c, containing rhs_c: the values for which x_B stays within [loB, hiB] with the non-basic
+ * variables where they are.
+ *   slack of the row basic at p: [rhs + (loB_p - xB_p), rhs + (hiB_p - xB_p)];
+ *   otherwise h = B^-1 e_row: delta+ = min of (hiB_p - xB_p) / h_p over h_p > 0 and (loB_p - xB_p) / h_p over h_p < 0, delta- mirrored;
+ *   a constraint without a row: (-inf, +inf).
+ * Tolerances: |alpha_i| <= 1e-8 and |h_p| <= 1e-8 count as zero; a numerator of the wrong sign (r_i = -1e-13 at a lower bound, xB a
+ * hair outside its bound) is clamped to 0, hence always lo <= current <= hi.
+ * User's sense: for a Maximize problem the internal cost is -c, so the cost range returned is [-hi, -lo]; rhs ranges have no sign turn.
+ * Within a rhs range the objective moves by dual_value(c) * delta, within a cost range by var_value(j) * delta.
+ * vars / cons == NULL asks for all of them (n must then be mlp_solution_num_vars / mlp_solution_num_constraints); otherwise n indices,
+ * duplicates allowed.  The two numbers of a request do not depend on what else is in the call (bit for bit).  Reading is side-effect
+ * free like the dual values; sharded solutions, a NULL handle, a wrong length or an index out of range => MLP_EINVAL. */
+enum { MLP_BASIC = 0, MLP_AT_LOWER = 1, MLP_AT_UPPER = 2, MLP_NB_FREE = 3, MLP_NB_FIXED = 4 };
+int mlp_solution_basis_status(const mlp_solution* s, int32_t* var_status, uint32_t n_vars, int32_t* cons_status, uint64_t n_cons);
+int mlp_solution_cost_ranging(const mlp_solution* s, const uint32_t* vars, uint64_t n, double* lo, double* hi);
+int mlp_solution_rhs_ranging(const mlp_solution* s, const uint64_t* cons, uint64_t n, double* lo, double* hi);
+/* of the last ranging call on this solution (zeros before the first).  Only grows at its end; mlp_ranging_info_size() is its size as
+ * the library was built. */
+typedef struct mlp_ranging_info {
+    uint64_t requests;   /* variables / constraints asked for */
+    uint64_t solves;     /* of them: requests that needed a row / a column of B^-1 (basic variables, rows whose slack is non-basic) */
+    uint64_t batches;    /* batches of 16 such requests: one pass over A (cost) / over the basic positions (rhs) each */
+    double bytes;        /* algorithmic bytes of the batches */
+    double device_ms;    /* their time on the device (HIP events around the launches) */
+} mlp_ranging_info;
+int mlp_solution_ranging_info(const mlp_solution* s, mlp_ranging_info* out);
+uint64_t mlp_ranging_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

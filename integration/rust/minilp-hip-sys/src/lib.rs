@@ -88,6 +88,12 @@ extern "C" {
     pub fn mlp_solution_reduced_cost(s: *mut mlp_solution, var: u32, out: *mut c_double) -> c_int;
     pub fn mlp_solution_certificate(s: *mut mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
     pub fn mlp_certificate_size() -> u64;
+    // basis status, cost / rhs ranging (additive: the ABI version stays 5)
+    pub fn mlp_solution_basis_status(s: *const mlp_solution, var_status: *mut i32, n_vars: u32, cons_status: *mut i32, n_cons: u64) -> c_int;
+    pub fn mlp_solution_cost_ranging(s: *const mlp_solution, vars: *const u32, n: u64, lo: *mut f64, hi: *mut f64) -> c_int;
+    pub fn mlp_solution_rhs_ranging(s: *const mlp_solution, cons: *const u64, n: u64, lo: *mut f64, hi: *mut f64) -> c_int;
+    pub fn mlp_solution_ranging_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
+    pub fn mlp_ranging_info_size() -> u64;
     pub fn mlp_solution_continue(s: *mut mlp_solution, pivot_budget: i64) -> c_int;
     pub fn mlp_solution_budget_exhausted(s: *const mlp_solution) -> c_int;
     pub fn mlp_solution_reinvert(s: *mut mlp_solution, max_diff: *mut c_double) -> c_int;

@@ -378,6 +378,36 @@ impl Solution {
         out
     }
 
+    /// Range `(lo, hi)` of the objective coefficient of a variable over which the current basis stays optimal, in the problem's
+    /// direction; within it the objective moves by `var_value * delta` (extension: no counterpart in the reference).
+    pub fn cost_range(&self, var: Variable) -> (f64, f64) {
+        assert!(var.0 < self.num_vars);
+        let (v, mut lo, mut hi) = (var.0 as u32, 0.0f64, 0.0f64);
+        let st = unsafe { sys::mlp_solution_cost_ranging(self.raw, &v, 1, &mut lo, &mut hi) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        (lo, hi)
+    }
+
+    /// Range `(lo, hi)` of the right-hand side of a constraint (by index, in the order the constraints were added) over which the
+    /// current basis stays feasible; within it the objective moves by `dual_value * delta` (extension).
+    pub fn rhs_range(&self, constraint: usize) -> (f64, f64) {
+        assert!(constraint < self.num_constraints());
+        let (c, mut lo, mut hi) = (constraint as u64, 0.0f64, 0.0f64);
+        let st = unsafe { sys::mlp_solution_rhs_ranging(self.raw, &c, 1, &mut lo, &mut hi) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        (lo, hi)
+    }
+
+    /// Whether a variable is basic at the current basis (extension).
+    pub fn is_basic(&self, var: Variable) -> bool {
+        assert!(var.0 < self.num_vars);
+        let mut vs = vec![0i32; self.num_vars];
+        let mut cs = vec![0i32; self.num_constraints()];
+        let st = unsafe { sys::mlp_solution_basis_status(self.raw, vs.as_mut_ptr(), vs.len() as u32, cs.as_mut_ptr(), cs.len() as u64) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        vs[var.0] == 0
+    }
+
     /// Iterate over the variable-value pairs of the solution.
     pub fn iter(&self) -> SolutionIter {
         SolutionIter { solution: self, var_idx: 0 }

@@ -56,6 +56,13 @@ class MlpCertificate(C.Structure):  # include/minilp_hip.h: mlp_certificate (onl
                 ("bytes", C.c_double), ("device_ms", C.c_double)]
 
 
+class MlpRangingInfo(C.Structure):  # include/minilp_hip.h: mlp_ranging_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("solves", C.c_uint64), ("batches", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
+
+
+# basis status of a variable / of a constraint's slack (include/minilp_hip.h)
+MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
+
 ABI_VERSION = 5  # include/minilp_hip.h: MLP_ABI_VERSION
 
 
@@ -157,6 +164,13 @@ def lib():
     sig("mlp_solution_reduced_costs", i32, vp, pdbl, u32)
     sig("mlp_solution_reduced_cost", i32, vp, u32, pdbl)
     sig("mlp_solution_certificate", i32, vp, C.POINTER(MlpCertificate))
+    sig("mlp_ranging_info_size", u64)
+    if L.mlp_ranging_info_size() != C.sizeof(MlpRangingInfo):
+        raise ImportError(f"{_SO}: mlp_ranging_info is {L.mlp_ranging_info_size()} bytes, this binding {C.sizeof(MlpRangingInfo)}: rebuild it")
+    sig("mlp_solution_basis_status", i32, vp, C.POINTER(C.c_int32), u32, C.POINTER(C.c_int32), u64)
+    sig("mlp_solution_cost_ranging", i32, vp, pu32, u64, pdbl, pdbl)
+    sig("mlp_solution_rhs_ranging", i32, vp, C.POINTER(C.c_uint64), u64, pdbl, pdbl)
+    sig("mlp_solution_ranging_info", i32, vp, C.POINTER(MlpRangingInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -399,6 +413,41 @@ class Solution:
         c = MlpCertificate()
         _raise(lib().mlp_solution_certificate(self._h, C.byref(c)))
         return {n: getattr(c, n) for n, _ in MlpCertificate._fields_}
+
+    # ---- basis status, cost / rhs ranging (include/minilp_hip.h: mlp_solution_basis_status ...; definitions there)
+    def basis_status(self):
+        """(variables, constraints): int32 arrays of MLP_BASIC / MLP_AT_LOWER / MLP_AT_UPPER / MLP_NB_FREE / MLP_NB_FIXED."""
+        v = np.zeros(self.num_vars, dtype=np.int32)
+        c = np.zeros(self.num_constraints, dtype=np.int32)
+        _raise(lib().mlp_solution_basis_status(self._h, _p(v, C.c_int32), len(v), _p(c, C.c_int32), len(c)))
+        return v, c
+
+    def _ranging(self, fn, which, n_all, ctype, dtype):
+        if which is None:
+            n, ptr = n_all, None
+        else:
+            w = np.ascontiguousarray(which, dtype=np.int64).reshape(-1)
+            if len(w) and (w.min() < 0 or w.max() > np.iinfo(dtype).max):
+                raise InternalError(-1, "ranging: index out of range")
+            w = w.astype(dtype)
+            n, ptr = len(w), _p(w, ctype)
+        lo, hi = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        _raise(fn(self._h, ptr, n, _p(lo, C.c_double), _p(hi, C.c_double)))
+        return lo, hi
+
+    def cost_ranging(self, vars=None):
+        """(lo, hi): the range of each objective coefficient (all variables, or the listed ones) over which the current basis stays optimal."""
+        return self._ranging(lib().mlp_solution_cost_ranging, vars, self.num_vars, C.c_uint32, np.uint32)
+
+    def rhs_ranging(self, constraints=None):
+        """(lo, hi): the range of each right-hand side (all constraints, or the listed ones) over which the current basis stays feasible."""
+        return self._ranging(lib().mlp_solution_rhs_ranging, constraints, self.num_constraints, C.c_uint64, np.uint64)
+
+    def ranging_info(self):
+        """Counters of the last cost_ranging / rhs_ranging call (mlp_ranging_info) as a dict."""
+        r = MlpRangingInfo()
+        _raise(lib().mlp_solution_ranging_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpRangingInfo._fields_}
 
     def add_constraint(self, expr, cmp_op, rhs):
         idx, val = _terms(expr)

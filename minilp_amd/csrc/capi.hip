@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "engine.h"
 
@@ -18,6 +19,7 @@ struct mlp_solution {
     // dual values / reduced costs / certificate of the current state (mlp_solution_dual_values ...), computed once per state
     bool duals_valid = false;
     Engine::Duals duals;
+    Engine::RangingInfo ranging;  // of the last mlp_solution_cost_ranging / mlp_solution_rhs_ranging call
     ~mlp_solution() { delete eng; }
 };
 // every entry point that can change the state of a solution drops the cached duals
@@ -67,6 +69,20 @@ static int consume_on_error(mlp_solution** s, int st) {  // lib.rs:359, 385
         *s = nullptr;
     }
     return st;
+}
+
+template <class I>
+static int ranging_call(const mlp_solution* cs, int kind, const I* which, uint64_t n, double* lo, double* hi) {
+    return guarded([&] {
+        mlp_solution* s = const_cast<mlp_solution*>(cs);
+        const Engine::Duals& d = duals_of(s);  // (refuses a NULL handle and a sharded solution; the reduced costs come from the cached read)
+        const uint64_t all = kind == 0 ? (uint64_t)s->eng->num_vars : (uint64_t)s->eng->num_constraints();
+        if (!which && n != all) throw MlpError(MLP_EINVAL, "ranging: without an index list the length must be the number of variables / constraints");
+        if (n && (!lo || !hi)) throw MlpError(MLP_EINVAL, "ranging: NULL output");
+        std::vector<uint64_t> idx((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) idx[i] = which ? (uint64_t)which[i] : i;
+        s->eng->ranging(kind, idx, d, lo, hi, s->ranging);
+    });
 }
 
 extern "C" {
@@ -288,6 +304,35 @@ int mlp_solution_certificate(mlp_solution* s, mlp_certificate* out) {
         out->bytes = d.bytes; out->device_ms = d.device_ms;
     });
 }
+// ---- basis status, cost / rhs ranging (ranging.inc)
+int mlp_solution_basis_status(const mlp_solution* cs, int32_t* var_status, uint32_t n_vars, int32_t* cons_status, uint64_t n_cons) {
+    return guarded([&] {
+        mlp_solution* s = const_cast<mlp_solution*>(cs);
+        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+        if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "the basis status is not available on a sharded solution");
+        if ((int)n_vars != s->eng->num_vars || n_cons != s->eng->num_constraints() || (n_vars && !var_status) || (n_cons && !cons_status))
+            throw MlpError(MLP_EINVAL, "basis_status: lengths must be mlp_solution_num_vars and mlp_solution_num_constraints");
+        std::vector<int32_t> v, c;
+        s->eng->basis_status(v, c);
+        if (n_vars) std::memcpy(var_status, v.data(), sizeof(int32_t) * v.size());
+        if (n_cons) std::memcpy(cons_status, c.data(), sizeof(int32_t) * c.size());
+    });
+}
+int mlp_solution_cost_ranging(const mlp_solution* s, const uint32_t* vars, uint64_t n, double* lo, double* hi) {
+    return ranging_call(s, 0, vars, n, lo, hi);
+}
+int mlp_solution_rhs_ranging(const mlp_solution* s, const uint64_t* cons, uint64_t n, double* lo, double* hi) {
+    return ranging_call(s, 1, cons, n, lo, hi);
+}
+int mlp_solution_ranging_info(const mlp_solution* s, mlp_ranging_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / ranging info");
+        std::memset(out, 0, sizeof(*out));
+        out->requests = s->ranging.requests; out->solves = s->ranging.solves; out->batches = s->ranging.batches;
+        out->bytes = s->ranging.bytes; out->device_ms = s->ranging.device_ms;
+    });
+}
+uint64_t mlp_ranging_info_size(void) { return (uint64_t)sizeof(mlp_ranging_info); }
 uint64_t mlp_stats_size(void) { return (uint64_t)sizeof(mlp_stats); }
 
 int mlp_solution_enable_sharding(mlp_solution* s, int rank, int world, const char* shm_name) {

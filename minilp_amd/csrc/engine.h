@@ -173,8 +173,19 @@ public:
         double max_row_viol = 0, max_bound_viol = 0, max_dual_inf = 0, btran_residual = 0;
         int64_t row_viol_at = -1, bound_viol_at = -1, dual_inf_at = -1, btran_residual_at = -1;
         double bytes = 0, device_ms = 0;
+        std::vector<double> r_int;  // reduced costs of ALL variables (slacks included) in the internal minimisation sense: the ranging's input
     };
     void compute_duals(Duals& out);
+    // Basis status and cost / rhs ranging of the current basis (ranging.inc; include/minilp_hip.h mlp_solution_basis_status ...).
+    // Status codes: 0 basic, 1 at lower, 2 at upper, 3 non-basic at neither bound, 4 non-basic fixed.  ranging(): kind 0 = cost ranges of
+    // the structural variables idx[], kind 1 = rhs ranges of the constraints idx[], both in the user's sense; du = the duals of the same
+    // state.  Reads the state only, like compute_duals.
+    struct RangingInfo {
+        uint64_t requests = 0, solves = 0, batches = 0;
+        double bytes = 0, device_ms = 0;
+    };
+    void basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons);
+    void ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du, double* lo, double* hi, RangingInfo& info);
     size_t num_constraints() const { return h_cons_row.size(); }
     double last_reinvert_scale = 0.0;  // max |W_fresh| of that comparison (state "reinvert_scale")
     // Basis checkpoint (include/minilp_hip.h: mlp_solution_save_basis / mlp_problem_solve_from_basis).

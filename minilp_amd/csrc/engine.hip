@@ -1225,6 +1225,9 @@ void Engine::enable_sharding(int rank, int world, const char* shm_name, const ch
         fac_leave();  // (ranks sharing a device, or a transport that cannot tell: back to the explicit inverse)
         view_dirty = true;
     }
+    // ranks that share a device and keep the factor all the same (MLP_FACTOR_SHARED_DEVICE): their persistent solve grids must fit on the
+    // device side by side, or their grid barriers wait for workgroups that cannot start (factor.inc: fac_solve_set_sharers)
+    if (world > 1 && ranks_share_device && fac_allowed_under_sharding()) fac_solve_set_sharers(world);
     {   // deferred sharding (engine.h): replicas until the tableau row becomes a pass over A; MLP_SHARD_DEFER=0 shards from the first pivot
         const char* sd = std::getenv("MLP_SHARD_DEFER");
         shard_defer_ = !(sd && sd[0] == '0');
@@ -3359,6 +3362,9 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
     else if (w == "orig_var_mins") tmp = h_lo;
     else if (w == "orig_var_maxs") tmp = h_hi;
     else if (w == "orig_rhs") tmp = h_rhs;
+    else if (w == "csr_indptr") tmp.assign(h_rptr.begin(), h_rptr.end());    // A with the slack identity, by row (the oracle's names)
+    else if (w == "csr_indices") tmp.assign(h_rcol.begin(), h_rcol.end());
+    else if (w == "csr_data") tmp = h_rval;
     else if (w == "flags") tmp = {(double)primal_feasible, (double)dual_feasible, (double)enable_pse, (double)enable_dse};
     else if (w == "small_basis_launches") {  // iterations that ran BTRAN + pass + v tail + touch as one launch (k_small_basis)
         pull_ctl();
@@ -3508,5 +3514,158 @@ void Engine::compute_duals(Duals& out) {
     const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
     out.bytes = 8.0 * k * k + 16.0 * J * (fac_on_ ? m : k) + 2.0 * 20.0 * nz + 60.0 * N + 48.0 * m;
     out.device_ms = ms;
+    out.r_int = std::move(hr);
+}
+
+// Basis status of every structural variable and every constraint (= its slack); a constraint without terms has no row: basic.
+static inline int32_t nb_status_of(uint8_t f) {
+    if ((f & NB_FIXED) || ((f & NB_AT_MIN) && (f & NB_AT_MAX))) return 4;
+    return (f & NB_AT_MIN) ? 1 : ((f & NB_AT_MAX) ? 2 : 3);
+}
+void Engine::basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons) {
+    if (sharded()) throw MlpError(-1, "the basis status is not available on a sharded solution");
+    pull_ctl();
+    std::vector<uint8_t> fl((size_t)num_vars);
+    if (num_vars) HIPCHECK(hipMemcpyAsync(fl.data(), d_nbflags.p, fl.size(), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    auto of = [&](int var) -> int32_t {
+        const int loc = h_var_loc[var];
+        return loc >= 0 ? 0 : nb_status_of(fl[-1 - loc]);
+    };
+    vars.resize((size_t)num_vars);
+    for (int j = 0; j < num_vars; ++j) vars[j] = of(j);
+    cons.resize(h_cons_row.size());
+    for (size_t c = 0; c < h_cons_row.size(); ++c) cons[c] = h_cons_row[c] < 0 ? 0 : of(num_vars + h_cons_row[c]);
+}
+
+// Cost / rhs ranging (ranging.inc).  The requests that need a row / a column of B^-1 are served in batches of RG_BATCH; the others
+// (non-basic variables, rows whose slack is basic, constraints without a row) are answered from the reduced costs / x_B directly.
+void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du, double* lo, double* hi, RangingInfo& info) {
+    if (sharded()) throw MlpError(-1, "ranging is not available on a sharded solution");
+    const double inf = std::numeric_limits<double>::infinity();
+    const size_t nreq = idx.size();
+    for (uint64_t id : idx)
+        if (id >= (kind == 0 ? (uint64_t)num_vars : (uint64_t)h_cons_row.size()))
+            throw MlpError(-1, kind == 0 ? "cost_ranging: variable out of range" : "rhs_ranging: constraint out of range");
+    if ((int)du.r_int.size() != N_) throw MlpError(-1, "ranging: the duals belong to another state");
+    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    const DevView& dv = hview;
+    const Geom g = geom();
+    const int m = m_, N = N_, k = fac_on_ ? 0 : k_;
+    std::vector<uint8_t> fl((size_t)num_vars);
+    if (num_vars) HIPCHECK(hipMemcpyAsync(fl.data(), d_nbflags.p, fl.size(), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    std::vector<double> L(nreq), H(nreq), cur(nreq, 0.0);
+    std::vector<std::pair<int, size_t>> solve;  // (basic position | row, request)
+    std::vector<double> xb, lb, hb;
+    for (size_t t = 0; t < nreq; ++t) {
+        if (kind == 0) {
+            const int j = (int)idx[t], loc = h_var_loc[j];
+            const double c = h_obj[j];
+            cur[t] = c;
+            if (loc >= 0) {
+                solve.emplace_back(loc, t);
+                continue;
+            }
+            const int stt = nb_status_of(fl[-1 - loc]);
+            const double r = du.r_int[j];
+            L[t] = stt == 1 ? c - std::max(r, 0.0) : (stt == 3 ? c : -inf);
+            H[t] = stt == 2 ? c - std::min(r, 0.0) : (stt == 3 ? c : inf);
+        } else {
+            const int row = h_cons_row[idx[t]];
+            if (row < 0) {
+                L[t] = -inf;
+                H[t] = inf;
+                continue;
+            }
+            cur[t] = h_rhs[row];
+            const int loc = h_var_loc[num_vars + row];
+            if (loc < 0) {
+                solve.emplace_back(row, t);
+                continue;
+            }
+            if (xb.empty()) {  // a basic slack absorbs the change alone: its own bounds are the range
+                xb.resize(m); lb.resize(m); hb.resize(m);
+                HIPCHECK(hipMemcpyAsync(xb.data(), d_xB.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+                HIPCHECK(hipMemcpyAsync(lb.data(), d_loB.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+                HIPCHECK(hipMemcpyAsync(hb.data(), d_hiB.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+                HIPCHECK(hipStreamSynchronize(st));
+            }
+            L[t] = cur[t] + std::min(lb[loc] - xb[loc], 0.0);
+            H[t] = cur[t] + std::max(hb[loc] - xb[loc], 0.0);
+        }
+    }
+    info = RangingInfo();
+    info.requests = nreq;
+    info.solves = solve.size();
+    if (!solve.empty()) {
+        constexpr int R = RG_BATCH;
+        if (kind == 1 && !fac_on_) {  // neighbouring columns of the row-major W share 64-byte sectors: by column slot
+            std::vector<int> ksr((size_t)m);
+            HIPCHECK(hipMemcpyAsync(ksr.data(), d_kslot_of_row.p, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipStreamSynchronize(st));
+            std::stable_sort(solve.begin(), solve.end(), [&](const std::pair<int, size_t>& a, const std::pair<int, size_t>& b) {
+                return ksr[a.first] < ksr[b.first];
+            });
+        }
+        const size_t nbat = (solve.size() + R - 1) / R;
+        std::vector<int> hreq(nbat * R, -1);
+        for (size_t q = 0; q < solve.size(); ++q) hreq[q] = solve[q].first;
+        const int nblk = ranging_blocks(g, kind, N);
+        const size_t rows = (kind == 0 || fac_on_) ? (size_t)m : (size_t)k;
+        DevBuf<double> blk, r, part, out, unit, tau;
+        DevBuf<double2> rv;
+        DevBuf<int> req;
+        blk.ensure(rows * R + R, 0, st); part.ensure((size_t)nblk * 2 * R, 0, st); out.ensure(nbat * 2 * R, 0, st);
+        req.upload(hreq, st);
+        if (kind == 0) r.upload(du.r_int, st);
+        if (fac_on_) {
+            unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
+            HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
+            HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
+        }
+        RangingBufs b{};
+        b.blk = blk.p; b.r = r.p; b.part = part.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
+        b.N = N; b.nv = num_vars; b.k = k; b.fac = fac_on_ ? 1 : 0;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        HIPCHECK(hipEventCreate(&e0));
+        HIPCHECK(hipEventCreate(&e1));
+        HIPCHECK(hipEventRecord(e0, st));
+        for (size_t q = 0; q < nbat; ++q) {
+            b.req = req.p + q * R;
+            b.out = out.p + q * 2 * R;
+            launch_ranging_batch(dv, g, b, kind, (int)std::min<size_t>(R, solve.size() - q * R), hreq.data() + q * R, st);
+        }
+        HIPCHECK(hipEventRecord(e1, st));
+        HIPCHECK(hipGetLastError());
+        std::vector<double> ho(nbat * 2 * R);
+        HIPCHECK(hipMemcpyAsync(ho.data(), out.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        float ms = 0.0f;
+        HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        for (size_t q = 0; q < solve.size(); ++q) {
+            const size_t t = solve[q].second;
+            L[t] = cur[t] + ho[2 * q];
+            H[t] = cur[t] + ho[2 * q + 1];
+        }
+        // algorithmic bytes per batch: the block (cleared, then written), the stored rows / columns it is made of with the pending
+        // terms, one pass over A (12 bytes per entry) with a gather of R doubles per entry, the per-position vectors of the rhs pull
+        const double nz = (double)h_rcol.size();
+        const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
+        info.batches = nbat;
+        info.bytes = (double)nbat * (16.0 * (double)rows * R + nz * (12.0 + 8.0 * R) + (kind == 1 ? 40.0 * m : 13.0 * N))
+                     + (double)solve.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k);
+        info.device_ms = ms;
+    }
+    // user's objective sense: a Maximize problem is solved as the minimisation of -c, so its cost range is [-hi, -lo]; rhs ranges keep their sign
+    const bool turn = kind == 0 && direction == 1;
+    for (size_t t = 0; t < nreq; ++t) {
+        const double a = turn ? -H[t] : L[t], c = turn ? -L[t] : H[t];
+        lo[t] = a == 0.0 ? 0.0 : a;
+        hi[t] = c == 0.0 ? 0.0 : c;
+    }
 }
 }  // namespace mlp

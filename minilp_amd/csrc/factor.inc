@@ -971,7 +971,21 @@ __global__ void __launch_bounds__(BLK) k_fac_solve(DevView v, int dir, int srcA,
         }
     }
 }
+// Processes that run this persistent grid on the SAME device (a sharded solve whose ranks share a GPU and keep the factor:
+// MLP_FACTOR_SHARED_DEVICE).  A workgroup takes a whole CU's LDS, so two full grids of two processes cannot be resident together: each
+// gets a part of the CUs, every grid barrier waits for workgroups that cannot start until the other grid leaves, and the waiters give up
+// at the spin bound with a half-done solve (both ranks of the 20-pivot test then found "no entering column" on a feasible model).  The
+// grids are therefore sized to fit side by side: CUs / sharers workgroups each (never fewer than the 64 pending terms need).
+static int g_fac_sharers = 1;
+void fac_solve_set_sharers(int n) { g_fac_sharers = n < 1 ? 1 : n; }
+static int fac_grid_blocks_full();
 static int fac_grid_blocks() {
+    const int full = fac_grid_blocks_full();
+    if (g_fac_sharers <= 1) return full;
+    const int part = full / g_fac_sharers;
+    return part >= 64 ? part : (full < 64 ? full : 64);
+}
+static int fac_grid_blocks_full() {
     static int n = 0;
     if (n == 0) {
         int dev = 0, cus = 0;

@@ -502,6 +502,7 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
 // partial sums of V_j . rho behind (MLP_FACTOR_RHO_PART=0: A/B, tests)
 void launch_fac_solve(const DevView& dv, const Geom& g, int dir, int src, int dst, const double* src_ptr, int always, hipStream_t st, int fuse = 0);
 void launch_fac_solve2(const DevView& dv, const Geom& g, int dir, int srcA, int dstA, int srcB, int dstB, hipStream_t st, int fuse = 0);  // two right-hand sides, one walk over the levels
+void fac_solve_set_sharers(int n);  // processes that run the solve grid on this device at the same time (ranks sharing a GPU): the grid shrinks to CUs / n
 int fac_solve_grid_blocks();  // workgroups of k_fac_solve's grid: workgroup j reduces the coefficient of pending term j, so fac_J must not exceed it
 void launch_fac_append(const DevView& dv, hipStream_t st);     // U_nlow, V_nlow from alpha_q / rho of this pivot; nlow += 1
 void launch_fac_gather_cb(const DevView& dv, hipStream_t st);  // alpha_q[p] = c[basic_vars[p]]
@@ -547,6 +548,25 @@ void launch_duals(const DevView& dv, const Geom& g, const DualsBufs& b, hipStrea
 int duals_var_blocks(const Geom& g, int N);
 int duals_row_blocks(const Geom& g);
 int duals_wt_stripes(int k);
+// cost / rhs ranging of the current basis (ranging.inc): batches of RG_BATCH rows / columns of B^-1 and one ratio-test pass per batch;
+// reads the solver state, writes only these buffers
+constexpr int RG_BATCH = 16;  // requests per batch (the sweep kernels take it as a template parameter)
+struct RangingBufs {
+    double* blk;        // cost: rho[m][RG_BATCH] by row; rhs: H[k][RG_BATCH] by nucleus slot (compact factor: H[m][RG_BATCH] by position)
+    const int* req;     // RG_BATCH per batch: cost: basic position of a request; rhs: its row (-1: empty place of the batch)
+    const double* r;    // N: reduced costs of the duals read (internal minimisation sense; basic: exactly 0)
+    double* part;       // blocks x 2 RG_BATCH: per-block (max of the lower ratios, min of the upper ratios) per request
+    double* out;        // 2 RG_BATCH per batch: (delta-, delta+) per request
+    double* unit;       // m: compact factor: right-hand side e_p / e_row of one solve
+    double* tau;        // m: compact factor: private result of the FTRAN
+    double2* rv;        // m: compact factor: private rv of the BTRAN
+    int N, nv;          // total / structural variables
+    int k, fac;         // nucleus size (explicit inverse), compact factor active
+};
+// one batch of at most RG_BATCH requests (nreq of them; req / out already point at the batch); kind 0: cost ranging, 1: rhs ranging;
+// h_req: the batch's requests as the host holds them (the compact factor runs one solve per request)
+void launch_ranging_batch(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st);
+int ranging_blocks(const Geom& g, int kind, int N);  // workgroups of the batch's sweep (= rows of RangingBufs.part)
 // blocked in-place Gauss-Jordan inversion of the nucleus held in dv.W (inverse.inc); *flag = 1: singular
 void launch_blocked_inverse(const DevView& dv, int k, double* rowbuf, int nrowbuf, int* piv, int* src, double* prow, double* ckey,
                             int* cidx, int* flag, hipStream_t st);

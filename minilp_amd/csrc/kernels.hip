@@ -5388,6 +5388,7 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
     hipLaunchKernelGGL(k_build_nucleus<16>, dim3(blocks_for((long)k * 16)), dim3(BLK), 0, st, dv, Kd, k);
 }
 #include "duals.inc"  // dual values, reduced costs and the KKT certificate (side-effect free reads of the solver state)
+#include "ranging.inc"  // cost / rhs ranging: batched rows / columns of B^-1 and one ratio-test pass per batch (side-effect free)
 
 void launch_gauss_jordan(double* Kd, double* Winv, int k, int ld, int* d_flag, double* d_scratch, hipStream_t st) {
     if (k <= 0) return;
