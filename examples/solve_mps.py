@@ -2,10 +2,11 @@
 """solve_mps — counterpart of the reference's examples/solve_mps.rs (19-43): read a free-format MPS file,
 minimise, print the objective and the non-zero variables.
 
-    python examples/solve_mps.py model.mps [--max] [--all] [--ranging]
+    python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--gomory-rounds K]
 
 --ranging adds a sensitivity table: per variable its value, basis status, reduced cost and cost range; per row its dual value and
-rhs range (rows in file order).
+rhs range (rows in file order).  --gomory-rounds K adds K rounds of Gomory cuts, each over all basic structural variables with a
+fractional value (|x - round x| > 1e-6) in one add_gomory_cuts call, and prints the bound and the call's counters after each round.
 
 Runs on the MI355X engine (libminilp_hip.so); there is no CPU back end.  `run(B, ...)` takes the module that
 provides the reference's API so that the tests can drive the same code with their checker."""
@@ -17,7 +18,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(B, path, maximize=False, show_all=False, ranging=False):
+def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -48,6 +49,19 @@ def run(B, path, maximize=False, show_all=False, ranging=False):
         print("%-12s %-6s %14s   %s" % ("row", "status", "dual value", "rhs range"))
         for c in range(sol.num_constraints):
             print("%-12d %-6s %14.8g   [%.8g, %.8g]" % (c, tag[cs[c]], pi[c], rlo[c], rhi[c]))
+    for k in range(gomory_rounds):
+        x = sol.values()
+        vs, _ = sol.basis_status()
+        frac = [v for v in range(len(x)) if vs[v] == 0 and abs(x[v] - round(x[v])) > 1e-6]
+        if not frac:
+            print("gomory round %d: no fractional basic variable" % (k + 1))
+            break
+        try:
+            sol = sol.add_gomory_cuts(frac)
+        except B.Infeasible:
+            print("gomory round %d: infeasible" % (k + 1))
+            return 1
+        print("gomory round %d: %d cuts, bound %.12g, %s" % (k + 1, len(frac), sol.objective(), sol.cut_info()))
     return 0
 
 
@@ -57,9 +71,11 @@ def main():
     ap.add_argument("--max", action="store_true", help="maximise instead of minimise (solve_mps.rs:32 minimises)")
     ap.add_argument("--all", action="store_true", help="print zero-valued variables too")
     ap.add_argument("--ranging", action="store_true", help="print the sensitivity table (status, reduced costs, duals, cost and rhs ranges)")
+    ap.add_argument("--gomory-rounds", type=int, default=0, metavar="K",
+                    help="K rounds of Gomory cuts over the fractional basic variables (one add_gomory_cuts call per round)")
     a = ap.parse_args()
     import minilp_amd as B
-    return run(B, a.file, a.max, a.all, a.ranging)
+    return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds)
 
 
 if __name__ == "__main__":

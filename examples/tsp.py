@@ -80,8 +80,9 @@ def stoer_wagner_py(w):
 
 
 class TspSolver:
-    def __init__(self, backend, pts, log=None):
+    def __init__(self, backend, pts, log=None, batch_cuts=False):
         self.B = backend
+        self.batch_cuts = batch_cuts  # separate ALL violated subtour constraints of an LP solution and add them with one call
         self.pts = pts
         self.n = len(pts)
         self.log = log or (lambda *a: None)
@@ -106,7 +107,43 @@ class TspSolver:
         w[self.iu] = x[self.edge_var[self.iu]]
         return w + w.T
 
+    def violated_subtour_sets(self, w):
+        """City masks S whose cut x(delta(S)) is below 2: every connected component of the support graph when it is disconnected
+        (one of a pair of complementary sets), the Stoer-Wagner minimum cut when it is connected."""
+        n = self.n
+        comp = -np.ones(n, dtype=np.int64)
+        nc = 0
+        for r in range(n):
+            if comp[r] >= 0:
+                continue
+            comp[r] = nc
+            stack = [r]
+            while stack:
+                i = stack.pop()
+                for j in np.flatnonzero((w[i] > 1e-9) & (comp < 0)):
+                    comp[j] = nc
+                    stack.append(int(j))
+            nc += 1
+        if nc > 1:
+            return [comp == c for c in range(nc if nc > 2 else 1)]
+        cut_w, mask = stoer_wagner(w)
+        return [] if cut_w > 2.0 - 1e-8 else [np.asarray(mask, dtype=bool)]
+
+    def add_subtour_constraints_batched(self, sol):
+        n = self.n
+        while True:
+            sets = self.violated_subtour_sets(self.weights(sol))
+            if not sets:
+                return sol
+            rows = [([(int(self.edge_var[i, j]), 1.0) for i in range(n) for j in range(i) if mask[i] != mask[j]], self.B.GE, 2.0)
+                    for mask in sets]
+            sol = sol.add_constraints(rows)
+            self.stats["cuts"] += len(rows)
+            self.stats["lp_solves"] += 1
+
     def add_subtour_constraints(self, sol):  # tsp.rs:398-434
+        if self.batch_cuts:
+            return self.add_subtour_constraints_batched(sol)
         n = self.n
         while True:
             cut_w, mask = stoer_wagner(self.weights(sol))
@@ -232,13 +269,15 @@ def main():
     ap.add_argument("--nodes", type=int, default=None, help="use only the first N cities")
     ap.add_argument("--max-bb-nodes", type=int, default=None)
     ap.add_argument("--svg", default=None, help="write the tour as an SVG drawing (tsp.rs:169-208)")
+    ap.add_argument("--batch-cuts", action="store_true",
+                    help="separate all violated subtour constraints of an LP solution and add them with one add_constraints call")
     a = ap.parse_args()
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import minilp_amd as backend  # the MI355X engine; there is no CPU back end (tests pass their checker to TspSolver)
     name, pts = read_tsplib(a.file, a.nodes)
     t0 = time.time()
-    s = TspSolver(backend, pts, log=lambda m: print("[%.1fs] %s" % (time.time() - t0, m), flush=True))
+    s = TspSolver(backend, pts, log=lambda m: print("[%.1fs] %s" % (time.time() - t0, m), flush=True), batch_cuts=a.batch_cuts)
     cost, tour = s.solve(a.max_bb_nodes)
     print("problem %s (%d cities): tour cost %.10f, %s, %.1fs" % (name, len(pts), cost, s.stats, time.time() - t0))
     print("tour:", " ".join(str(int(t) + 1) for t in tour))  # Tour::to_string (tsp.rs:161-167): 1-based city numbers

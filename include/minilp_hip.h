@@ -40,6 +40,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
 /* Version 5: the struct mlp_certificate was added, with the dual-value / reduced-cost entry points below; mlp_stats is unchanged. */
 /* Still version 5: the basis-status / ranging entry points further down are purely additive — new functions and one new struct
  * (mlp_ranging_info, with its own mlp_ranging_info_size()); mlp_stats and mlp_certificate are untouched, no existing layout moved. */
+/* Still version 5: the cut-round entry points (mlp_solution_add_constraints_csr, mlp_solution_add_gomory_cuts, mlp_cut_info) are
+ * additive in the same way. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -292,6 +294,42 @@ typedef struct mlp_ranging_info {
 } mlp_ranging_info;
 int mlp_solution_ranging_info(const mlp_solution* s, mlp_ranging_info* out);
 uint64_t mlp_ranging_info_size(void);
+
+/* ---- A round of cuts in one call (no counterpart in the reference: solver.rs:440-460 and 549-634 take one row at a time) ------------
+ * mlp_solution_add_constraints_csr: m x mlp_solution_add_constraint in one call (rows in CSR, same argument meaning as
+ *   mlp_problem_add_constraints_csr): all rows are appended to the model, then feasibility is restored ONCE.  The model left behind is
+ *   what m calls of mlp_solution_add_constraint in the same order would have left: constraint numbering (dual values, rhs ranging,
+ *   mlp_solution_num_constraints), the rows the engine holds, slack bounds by operator; a row without terms gets no row and must be a
+ *   tautology (otherwise MLP_INFEASIBLE).  The slack of every new row starts at rhs - a.x at the point the call finds; only the pivot
+ *   path of the re-solve differs from the sequential form, so the optimum value is the same.
+ * mlp_solution_add_gomory_cuts: one round of Gomory cuts.  For every listed variable (each must be basic; a duplicate, a non-basic or
+ *   an out-of-range variable is MLP_EINVAL) the cut of solver.rs:440-460,
+ *       sum_j (floor(alpha_pj) - alpha_pj) x_nb(j) <= floor(xB_p) - xB_p,
+ *   ALL taken from the basis the call finds, built on the device, appended together, feasibility restored once.  Stored as
+ *   mlp_solution_add_gomory_cut stores it: terms on all non-basic columns (slacks included) in variable order, coefficients that are
+ *   exactly 0.0 dropped, operator <=.  The row of a variable does not depend on what else is in the round (bit for bit).
+ * Both: the solution must be solved (MLP_EINVAL otherwise); MLP_INFEASIBLE => status 1; on every non-zero status the solution is
+ *   freed and *s = NULL, as the single forms do.  m == 0 / n == 0 is a successful no-op that leaves the solution untouched.  Sharded
+ *   solutions and NULL handles => MLP_EINVAL.  The dual-value / ranging cache is dropped.
+ * mlp_cut_info: what the last of these two calls on this solution did (zeros before the first).  Only grows at its end;
+ *   mlp_cut_info_size() is its size as the library was built. */
+int mlp_solution_add_constraints_csr(mlp_solution** s, uint64_t m, const uint64_t* indptr, const uint32_t* vars,
+                                     const double* coeffs, const int32_t* cmp_ops, const double* rhs);
+int mlp_solution_add_gomory_cuts(mlp_solution** s, const uint32_t* vars, uint64_t n);
+typedef struct mlp_cut_info {
+    uint64_t rows;                /* rows appended to the matrix */
+    uint64_t rows_without_terms;  /* constraints of the call that have no terms (tautologies): numbered, but no row */
+    uint64_t nnz;                 /* terms of the appended rows (slack entries not counted) */
+    uint64_t batches;             /* Gomory rounds: batches of 16 cuts, one pass over A each; 0 for add_constraints_csr */
+    uint64_t relayouts;           /* re-layouts of the column-major copy of A: 1 for any call that appends a row */
+    uint64_t reinversions;        /* from-scratch inversions / refactorisations the call needed: 0 or 1 */
+    uint64_t pivots;              /* iterations of the one re-solve */
+    double bytes;                 /* algorithmic bytes of the cut generation (0 for add_constraints_csr) */
+    double device_ms;             /* its time on the device (HIP events around the generation launches) */
+    double wall_ms;               /* the whole call */
+} mlp_cut_info;
+int mlp_solution_cut_info(const mlp_solution* s, mlp_cut_info* out);
+uint64_t mlp_cut_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

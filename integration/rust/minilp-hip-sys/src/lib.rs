@@ -94,6 +94,11 @@ extern "C" {
     pub fn mlp_solution_rhs_ranging(s: *const mlp_solution, cons: *const u64, n: u64, lo: *mut f64, hi: *mut f64) -> c_int;
     pub fn mlp_solution_ranging_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
     pub fn mlp_ranging_info_size() -> u64;
+    // a round of cuts in one call (additive: the ABI version stays 5)
+    pub fn mlp_solution_add_constraints_csr(s: *mut *mut mlp_solution, m: u64, indptr: *const u64, vars: *const u32, coeffs: *const f64, cmp_ops: *const i32, rhs: *const f64) -> c_int;
+    pub fn mlp_solution_add_gomory_cuts(s: *mut *mut mlp_solution, vars: *const u32, n: u64) -> c_int;
+    pub fn mlp_solution_cut_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
+    pub fn mlp_cut_info_size() -> u64;
     pub fn mlp_solution_continue(s: *mut mlp_solution, pivot_budget: i64) -> c_int;
     pub fn mlp_solution_budget_exhausted(s: *const mlp_solution) -> c_int;
     pub fn mlp_solution_reinvert(s: *mut mlp_solution, max_diff: *mut c_double) -> c_int;

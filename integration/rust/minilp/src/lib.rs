@@ -471,6 +471,48 @@ impl Solution {
         self.consume(|s| unsafe { sys::mlp_solution_add_gomory_cut(s, var.0 as u32) })
     }
 
+    /// Add a whole round of constraints in one call and return the solution to the updated problem: every row is
+    /// appended to the model, then feasibility is restored once.  The model left behind is that of
+    /// [`add_constraint`](Self::add_constraint) called row by row in the same order (extension: no counterpart in the
+    /// reference).
+    ///
+    /// # Errors
+    ///
+    /// Will return an error if the problem becomes infeasible with the additional constraints.
+    pub fn add_constraints(self, rows: Vec<(LinearExpr, ComparisonOp, f64)>) -> Result<Self, Error> {
+        let mut indptr: Vec<u64> = vec![0];
+        let mut vars: Vec<u32> = Vec::new();
+        let mut coeffs: Vec<f64> = Vec::new();
+        let mut ops: Vec<i32> = Vec::new();
+        let mut rhs: Vec<f64> = Vec::new();
+        for (expr, op, r) in &rows {
+            vars.extend(expr.vars.iter().map(|&v| v as u32));
+            coeffs.extend_from_slice(&expr.coeffs);
+            indptr.push(vars.len() as u64);
+            ops.push(op.to_c() as i32);
+            rhs.push(*r);
+        }
+        self.consume(|s| unsafe {
+            sys::mlp_solution_add_constraints_csr(s, rhs.len() as u64, indptr.as_ptr(), vars.as_ptr(), coeffs.as_ptr(), ops.as_ptr(), rhs.as_ptr())
+        })
+    }
+
+    /// Add one round of Gomory cuts, one per listed variable, all taken from the current basis, and return the
+    /// solution (extension: the reference adds one cut per call, `lib.rs:419-423`).
+    ///
+    /// # Errors
+    ///
+    /// Will return an error if the problem becomes infeasible with the additional constraints.
+    ///
+    /// # Panics
+    ///
+    /// Will panic if a variable is listed twice or is not basic.
+    pub fn add_gomory_cuts(self, vars: &[Variable]) -> Result<Self, Error> {
+        let v: Vec<u32> = vars.iter().map(|x| x.0 as u32).collect();
+        assert!(vars.iter().all(|x| x.0 < self.num_vars));
+        self.consume(|s| unsafe { sys::mlp_solution_add_gomory_cuts(s, v.as_ptr(), v.len() as u64) })
+    }
+
     /// The raw handle, for the engine-level stepping API and the diagnostics of `minilp-hip-sys`
     /// (not part of the reference's API).
     pub fn as_raw(&self) -> *mut sys::mlp_solution {

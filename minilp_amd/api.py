@@ -60,6 +60,12 @@ class MlpRangingInfo(C.Structure):  # include/minilp_hip.h: mlp_ranging_info (on
     _fields_ = [("requests", C.c_uint64), ("solves", C.c_uint64), ("batches", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
 
 
+class MlpCutInfo(C.Structure):  # include/minilp_hip.h: mlp_cut_info (only grows at its end)
+    _fields_ = [("rows", C.c_uint64), ("rows_without_terms", C.c_uint64), ("nnz", C.c_uint64), ("batches", C.c_uint64),
+                ("relayouts", C.c_uint64), ("reinversions", C.c_uint64), ("pivots", C.c_uint64),
+                ("bytes", C.c_double), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -171,6 +177,12 @@ def lib():
     sig("mlp_solution_cost_ranging", i32, vp, pu32, u64, pdbl, pdbl)
     sig("mlp_solution_rhs_ranging", i32, vp, C.POINTER(C.c_uint64), u64, pdbl, pdbl)
     sig("mlp_solution_ranging_info", i32, vp, C.POINTER(MlpRangingInfo))
+    sig("mlp_cut_info_size", u64)
+    if L.mlp_cut_info_size() != C.sizeof(MlpCutInfo):
+        raise ImportError(f"{_SO}: mlp_cut_info is {L.mlp_cut_info_size()} bytes, this binding {C.sizeof(MlpCutInfo)}: rebuild it")
+    sig("mlp_solution_add_constraints_csr", i32, C.POINTER(vp), u64, C.POINTER(C.c_uint64), pu32, pdbl, C.POINTER(C.c_int32), pdbl)
+    sig("mlp_solution_add_gomory_cuts", i32, C.POINTER(vp), pu32, u64)
+    sig("mlp_solution_cut_info", i32, vp, C.POINTER(MlpCutInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -470,6 +482,49 @@ class Solution:
         h = self._take()
         _raise(lib().mlp_solution_add_gomory_cut(C.byref(h), int(var)))
         return Solution(h)
+
+    # ---- a round of cuts in one call (include/minilp_hip.h: mlp_solution_add_constraints_csr ...; semantics there)
+    def add_constraints_csr(self, indptr, indices, data, cmp_ops, rhs):
+        """m x add_constraint in one call (rows in CSR form): all rows appended, feasibility restored once."""
+        ip = np.ascontiguousarray(indptr, dtype=np.uint64)
+        ix = np.ascontiguousarray(indices, dtype=np.uint32)
+        dv = np.ascontiguousarray(data, dtype=np.float64)
+        ops = np.ascontiguousarray(cmp_ops, dtype=np.int32)
+        rh = np.ascontiguousarray(rhs, dtype=np.float64)
+        if len(ip) != len(rh) + 1 or len(ops) != len(rh) or len(ix) != len(dv) or (len(rh) and int(ip[-1]) != len(ix)):
+            raise InternalError(-1, "add_constraints_csr: array lengths do not fit")
+        h = self._take()
+        _raise(lib().mlp_solution_add_constraints_csr(C.byref(h), len(rh), _p(ip, C.c_uint64), _p(ix, C.c_uint32), _p(dv, C.c_double),
+                                                      _p(ops, C.c_int32), _p(rh, C.c_double)))
+        return Solution(h)
+
+    def add_constraints(self, rows):
+        """add_constraint for every (expr, cmp_op, rhs) of `rows`, in one call."""
+        ip, ix, dv, ops, rh = [0], [], [], [], []
+        for expr, cmp_op, rhs in rows:
+            idx, val = _terms(expr)
+            ix.extend(int(i) for i in idx)
+            dv.extend(float(v) for v in val)
+            ip.append(len(ix))
+            ops.append(int(cmp_op))
+            rh.append(float(rhs))
+        return self.add_constraints_csr(ip, ix, dv, ops, rh)
+
+    def add_gomory_cuts(self, vars):
+        """One round of Gomory cuts, one per listed basic variable, all from the current basis; feasibility restored once."""
+        v = np.ascontiguousarray(list(vars), dtype=np.int64)
+        if len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+            raise InternalError(-1, "add_gomory_cuts: variable out of range")
+        v = v.astype(np.uint32)
+        h = self._take()
+        _raise(lib().mlp_solution_add_gomory_cuts(C.byref(h), _p(v, C.c_uint32), len(v)))
+        return Solution(h)
+
+    def cut_info(self):
+        """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""
+        r = MlpCutInfo()
+        _raise(lib().mlp_solution_cut_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpCutInfo._fields_}
 
     def save_basis(self, mode=2):
         """Basis checkpoint as bytes (include/minilp_hip.h): 0 sets + flags + x_N, 1 + f32 weights, 2 full f64 state."""

@@ -20,6 +20,7 @@ struct mlp_solution {
     bool duals_valid = false;
     Engine::Duals duals;
     Engine::RangingInfo ranging;  // of the last mlp_solution_cost_ranging / mlp_solution_rhs_ranging call
+    Engine::CutInfo cuts;         // of the last mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts call
     ~mlp_solution() { delete eng; }
 };
 // every entry point that can change the state of a solution drops the cached duals
@@ -431,6 +432,55 @@ int mlp_solution_add_gomory_cut(mlp_solution** s, uint32_t var) {
         (*s)->eng->add_gomory_cut((int)var);
     }));
 }
+
+// ---- a round of cuts in one call (cuts.inc)
+int mlp_solution_add_constraints_csr(mlp_solution** s, uint64_t m, const uint64_t* indptr, const uint32_t* vars, const double* coeffs,
+                                     const int32_t* cmp_ops, const double* rhs) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        if (m && (!indptr || !cmp_ops || !rhs)) throw MlpError(MLP_EINVAL, "add_constraints_csr: NULL array");
+        ProblemData tmp;
+        tmp.obj.resize((*s)->eng->num_vars);  // lib.rs:376: dimension = num_vars
+        for (uint64_t i = 0; i < m; ++i) {
+            if (indptr[i + 1] < indptr[i]) throw MlpError(MLP_EINVAL, "add_constraints_csr: indptr must not decrease");
+            if (indptr[i + 1] > indptr[i] && (!vars || !coeffs)) throw MlpError(MLP_EINVAL, "add_constraints_csr: NULL array");
+            tmp.add_constraint(vars + indptr[i], coeffs + indptr[i], indptr[i + 1] - indptr[i], cmp_ops[i], rhs[i]);
+        }
+        (*s)->cuts = Engine::CutInfo();
+        if (m == 0) return;
+        (*s)->eng->pivot_budget = -1;
+        stale(*s);
+        (*s)->eng->add_constraints(std::move(tmp.cons), (*s)->cuts);
+    }));
+}
+int mlp_solution_add_gomory_cuts(mlp_solution** s, const uint32_t* vars, uint64_t n) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        if (n && !vars) throw MlpError(MLP_EINVAL, "add_gomory_cuts: NULL variable list");
+        std::vector<int> v((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (vars[i] >= (uint32_t)(*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:420)");
+            v[i] = (int)vars[i];
+        }
+        (*s)->cuts = Engine::CutInfo();
+        if (n == 0) return;
+        (*s)->eng->pivot_budget = -1;
+        stale(*s);
+        (*s)->eng->add_gomory_cuts(v, (*s)->cuts);
+    }));
+}
+int mlp_solution_cut_info(const mlp_solution* s, mlp_cut_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / cut info");
+        const Engine::CutInfo& c = s->cuts;
+        out->rows = c.rows; out->rows_without_terms = c.rows_without_terms; out->nnz = c.nnz; out->batches = c.batches;
+        out->relayouts = c.relayouts; out->reinversions = c.reinversions; out->pivots = c.pivots;
+        out->bytes = c.bytes; out->device_ms = c.device_ms; out->wall_ms = c.wall_ms;
+    });
+}
+uint64_t mlp_cut_info_size(void) { return (uint64_t)sizeof(mlp_cut_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

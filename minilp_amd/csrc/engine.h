@@ -159,6 +159,15 @@ public:
     void fix_var(int var, double val);                                      // solver.rs:378-415
     bool unfix_var(int var);                                                // solver.rs:418-438
     void add_gomory_cut(int var);                                           // solver.rs:440-460
+    // A round of cuts in one call (cuts.inc; include/minilp_hip.h mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts): all
+    // rows appended with ONE re-layout of the CSC, at most one re-inversion, the edge norms of every new row, ONE re-solve.  The model
+    // left behind is that of the single forms called in the same order; only the pivot path of the re-solve differs.
+    struct CutInfo {
+        uint64_t rows = 0, rows_without_terms = 0, nnz = 0, batches = 0, relayouts = 0, reinversions = 0, pivots = 0;
+        double bytes = 0, device_ms = 0, wall_ms = 0;
+    };
+    void add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gomory = false);
+    void add_gomory_cuts(const std::vector<int>& vars, CutInfo& info);  // the cut of add_gomory_cut for every listed (basic) variable
     double get_value(int var);                                              // solver.rs:371-376
     void get_values(double* out, int n);
     double cur_obj_val();                                                   // solver.rs:51
@@ -493,6 +502,7 @@ private:
     DevBuf<int> d_cptr_alt, d_crow_alt, d_row_idx, d_scan_tmp;  // second CSC buffer set of the device-side append, staging
     DevBuf<double> d_cval_alt, d_row_val;
     void append_row_on_device(const Constraint& c, int slack, int row);
+    void append_rows_on_device(const std::vector<Constraint>& cs, size_t old_nnz);  // R rows, one CSC re-layout
 
     void record_iteration(int phase, bool with_events);  // enqueue the kernel sequence of ONE iteration
     void launch_stage(int phase, int stage, bool with_events);

@@ -2904,6 +2904,292 @@ void Engine::add_constraint(Constraint c) {
     stats.solve_wall_s += now_s() - t0;
 }
 
+// ------------------------------------------------------------------ a round of cuts in one call (cuts.inc)
+// R rows on the device at once: the host mirror already holds them (CSR tail, slack bounds); here the CSR tail and the slack
+// entries of the per-variable arrays go up with one copy each, and the CSC is re-laid out ONCE for the whole batch.
+void Engine::append_rows_on_device(const std::vector<Constraint>& cs, size_t old_nnz) {
+    const size_t R = cs.size();
+    const size_t add = h_rcol.size() - old_nnz;
+    d_rcol.ensure(old_nnz + add, old_nnz, st);
+    d_rval.ensure(old_nnz + add, old_nnz, st);
+    d_rptr.ensure((size_t)m_ + R + 1, (size_t)m_ + 1, st);
+    HIPCHECK(hipMemcpyAsync(d_rcol.p + old_nnz, h_rcol.data() + old_nnz, add * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_rval.p + old_nnz, h_rval.data() + old_nnz, add * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_rptr.p + m_ + 1, &h_rptr[m_ + 1], R * sizeof(int), hipMemcpyHostToDevice, st));
+    d_lo.ensure((size_t)N_ + R, (size_t)N_, st); d_hi.ensure((size_t)N_ + R, (size_t)N_, st); d_obj.ensure((size_t)N_ + R, (size_t)N_, st);
+    HIPCHECK(hipMemcpyAsync(d_lo.p + N_, &h_lo[N_], R * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_hi.p + N_, &h_hi[N_], R * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_obj.p + N_, &h_obj[N_], R * sizeof(double), hipMemcpyHostToDevice, st));
+    // --- CSC: per-column counts from the R sorted rows, their scan, one copy kernel into the second buffer set, then swap
+    d_row_idx.ensure((size_t)N_ + 2, 0, st);
+    d_scan_tmp.ensure((size_t)(N_ + 1) / 4096 + 8, 0, st);
+    d_cptr_alt.ensure((size_t)N_ + R + 1, 0, st);
+    d_crow_alt.ensure(old_nnz + add, 0, st);
+    d_cval_alt.ensure(old_nnz + add, 0, st);
+    launch_csc_append_rows(d_cptr.p, d_crow.p, d_cval.p, N_, m_, (int)R, d_rptr.p + m_, d_rcol.p, d_rval.p, d_row_idx.p, d_scan_tmp.p,
+                           d_cptr_alt.p, d_crow_alt.p, d_cval_alt.p, st);
+    HIPCHECK(hipStreamSynchronize(st));  // the old buffers become the spare set
+    d_cptr.swap(d_cptr_alt); d_crow.swap(d_crow_alt); d_cval.swap(d_cval_alt);
+    // --- host column summaries, row by row as the single form leaves them
+    for (size_t i = 0; i < R; ++i) {
+        const Constraint& c = cs[i];
+        const int row = m_ + (int)i;
+        for (size_t p = 0; p < c.idx.size(); ++p) {
+            const int var = c.idx[p];
+            h_colnnz[var] += 1;
+            if (h_colnnz[var] == 1) {
+                h_single_row[var] = row;
+                h_single_val[var] = c.val[p];
+            }
+            max_col_nnz_ = std::max(max_col_nnz_, h_colnnz[var]);
+            amax_ = std::max(amax_, std::fabs(c.val[p]));
+        }
+        max_row_nnz_ = std::max(max_row_nnz_, (int)c.idx.size() + 1);
+        h_colnnz.push_back(1);
+        h_single_row.push_back(row);
+        h_single_val.push_back(1.0);
+    }
+    amax_ = std::max(amax_, 1.0);  // (the slack entries)
+    if (!h_cptr.empty()) {  // the host CSC of the initial build is stale from here on
+        std::vector<int>().swap(h_cptr); std::vector<int>().swap(h_crow); std::vector<double>().swap(h_cval);
+    }
+    colblk_dirty = true;
+    banded_dirty = true;
+    fpk_valid_ = false;
+    view_dirty = true;
+}
+
+void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gomory) {
+    cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
+    const double t0 = now_s();
+    if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_constraints: model not solved (solver.rs:555-556)");
+    const bool on_factor = fac_on_;
+    ensure_beta();
+    // constraints without terms get no row (their dual value is 0); one that is not a tautology makes the model infeasible
+    std::vector<Constraint> rows;
+    std::vector<int> cons_row;
+    for (Constraint& c : cs) {
+        if (c.idx.empty()) {
+            const bool taut = c.op == 0 ? (0.0 == c.rhs) : c.op == 1 ? (0.0 <= c.rhs) : (0.0 >= c.rhs);
+            if (!taut) throw LpFail{1};
+            cons_row.push_back(-1);
+            info.rows_without_terms += 1;
+        } else {
+            cons_row.push_back(m_ + (int)rows.size());
+            rows.push_back(std::move(c));
+        }
+    }
+    h_cons_row.insert(h_cons_row.end(), cons_row.begin(), cons_row.end());
+    const int R = (int)rows.size();
+    if (R == 0) {
+        info.wall_ms += (now_s() - t0) * 1e3;
+        return;
+    }
+    fetch_values();
+    const int row0 = m_, slack0 = N_;
+    const size_t old_nnz = h_rcol.size();
+    std::vector<double> xnew(R), smin(R), smax(R);
+    bool touches_basic_singleton = false;
+    size_t nb_terms = 0;
+    for (int i = 0; i < R; ++i) {
+        const Constraint& c = rows[i];
+        smin[i] = c.op == 2 ? -INF : 0.0;
+        smax[i] = c.op == 1 ? INF : 0.0;
+        double lhs = 0.0;  // solver.rs:587-595, at the point the call finds
+        for (size_t p = 0; p < c.idx.size(); ++p) {
+            const int var = c.idx[p];
+            const int loc = h_var_loc[var];
+            lhs += (loc >= 0 ? h_xB[loc] : h_xN[-1 - loc]) * c.val[p];
+            if (loc >= 0 && col_nnz(var) == 1) touches_basic_singleton = true;  // that column stops being a singleton
+            if (loc < 0) nb_terms += 1;
+        }
+        xnew[i] = c.rhs - lhs;
+        for (size_t p = 0; p < c.idx.size(); ++p) {
+            h_rcol.push_back(c.idx[p]);
+            h_rval.push_back(c.val[p]);
+        }
+        h_rcol.push_back(slack0 + i);
+        h_rval.push_back(1.0);
+        h_rptr.push_back((int)h_rcol.size());
+        h_rhs.push_back(c.rhs);
+        h_obj.push_back(0.0);
+        h_lo.push_back(smin[i]);
+        h_hi.push_back(smax[i]);
+        info.nnz += c.idx.size();
+    }
+    HIPCHECK(hipStreamSynchronize(st));
+    alloc_row_buffers(m_ + R);
+    append_rows_on_device(rows, old_nnz);
+    info.relayouts += 1;
+    m_ += R;
+    N_ += R;
+    ensure_red();
+    nnz_nonbasic += nb_terms;
+    // the R new basic positions hold the slacks (singletons on the new rows): one copy per array
+    std::vector<int> slk(R), rws(R), neg(R, -1);
+    std::vector<double> ones(R, 1.0);
+    std::vector<RowInfo> ri(R);
+    for (int i = 0; i < R; ++i) {
+        slk[i] = slack0 + i;
+        rws[i] = row0 + i;
+        ri[i] = RowInfo{1.0, row0 + i, -1};
+        h_basic_vars.push_back(slack0 + i);
+        h_var_loc.push_back(row0 + i);
+    }
+    const size_t bi = (size_t)R * sizeof(int), bd = (size_t)R * sizeof(double);
+    HIPCHECK(hipMemcpyAsync(d_basic_vars.p + row0, slk.data(), bi, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_var_loc.p + slack0, rws.data(), bi, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_xB.p + row0, xnew.data(), bd, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_loB.p + row0, smin.data(), bd, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_hiB.p + row0, smax.data(), bd, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_beta.p + row0, ones.data(), bd, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_kslot_of_pos.p + row0, neg.data(), bi, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_srow_of_pos.p + row0, rws.data(), bi, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_sdiag_of_pos.p + row0, ones.data(), bd, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_kslot_of_row.p + row0, neg.data(), bi, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_pos_of_srow.p + row0, rws.data(), bi, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_rowinfo.p + row0, ri.data(), (size_t)R * sizeof(RowInfo), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    values_dirty = true;
+    view_dirty = true;
+    sync_view();
+    launch_init_nb_rng(hview, geom(), st);
+    if (on_factor) {
+        if (!fac_refactor()) fac_leave();  // (the extended basis no longer peels within the bump limit: explicit inverse, as before)
+        info.reinversions += 1;
+    } else if (touches_basic_singleton) {
+        rebuild_inverse();  // some singleton column just gained an entry
+        info.reinversions += 1;
+    }
+    // Edge norms.  The tableau row of new row i in the extended basis does not depend on the other new rows
+    // (B_ext^-1 = [[B^-1, 0], [-a_B^T B^-1, I]]).  A Gomory cut's row IS its coefficient row (beta = 1, set above; gamma was fed
+    // from the emitted block by launch_cut_fill); a general row takes the path of the single form.
+    if (!gomory && (enable_pse || enable_dse)) {
+        for (int i = 0; i < R; ++i) {
+            calc_row_coeffs(row0 + i, enable_pse);
+            if (enable_pse) launch_sq_norms_add_row(hview, geom(), st);
+            if (enable_dse) launch_copy_rho_sq_to_beta(hview, row0 + i, st);
+        }
+    }
+    info.rows += (uint64_t)R;
+    primal_feasible = false;
+    budget_exhausted = false;
+    const uint64_t it0 = stats.iterations;
+    restore_feasibility();
+    info.pivots += stats.iterations - it0;
+    stats.solve_wall_s += now_s() - t0;
+    info.wall_ms += (now_s() - t0) * 1e3;
+}
+
+// One round of Gomory cuts (solver.rs:440-460 per cut), ALL taken from the basis the call finds: RG_BATCH rows of B^-1 per block,
+// one pass over A per block, the cuts emitted as sparse rows on the device (cuts.inc).  The host reads back the row lengths and the
+// sparse rows (O(nnz of the cuts)); no dense tableau row crosses.
+void Engine::add_gomory_cuts(const std::vector<int>& vars, CutInfo& info) {
+    const double t0 = now_s();
+    if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_gomory_cuts: model not solved (solver.rs:555-556)");
+    std::vector<int> pos(vars.size());
+    {
+        std::vector<int> sorted(vars);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "add_gomory_cuts: duplicate variable");
+    }
+    for (size_t t = 0; t < vars.size(); ++t) {
+        if (vars[t] < 0 || vars[t] >= num_vars) throw MlpError(-1, "add_gomory_cuts: variable out of range (lib.rs:420)");
+        if (h_var_loc[vars[t]] < 0) throw MlpError(-1, "add_gomory_cuts: variable is not basic (solver.rs:458)");
+        pos[t] = h_var_loc[vars[t]];
+    }
+    ensure_beta();  // (before the edge norms are fed)
+    pull_ctl();     // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    const DevView& dv = hview;
+    const Geom g = geom();
+    constexpr int R = RG_BATCH;
+    const int m = m_, N = N_;
+    const size_t nbat = (vars.size() + R - 1) / R;
+    std::vector<int> hreq(nbat * R, -1);
+    for (size_t t = 0; t < pos.size(); ++t) hreq[t] = pos[t];
+    const int nseg = cut_segments(N);
+    const size_t ncnt = (size_t)R * nseg;
+    DevBuf<double> blk, fd, rhs, oval, unit, tau;
+    DevBuf<double2> rv;
+    DevBuf<int> req, cnt, off, len, ocol;
+    blk.ensure((size_t)m * R + R, 0, st); fd.ensure((size_t)N * R + R, 0, st); rhs.ensure(R, 0, st); len.ensure(R, 0, st);
+    cnt.ensure(ncnt + 8, 0, st); off.ensure(ncnt + 8, 0, st);
+    d_scan_tmp.ensure(ncnt / 4096 + 8, 0, st);
+    req.upload(hreq, st);
+    if (fac_on_) {
+        unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
+        HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
+        HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
+    }
+    RangingBufs b{};
+    b.blk = blk.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
+    b.N = N; b.nv = num_vars; b.k = fac_on_ ? 0 : k_; b.fac = fac_on_ ? 1 : 0;
+    struct Events {  // (destroyed on every way out, a throwing HIPCHECK included)
+        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+        ~Events() {
+            for (auto& x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+        hipEvent_t& operator[](int i) { return e[i]; }
+    } e;
+    for (auto& x : e.e) HIPCHECK(hipEventCreate(&x));
+    std::vector<Constraint> cuts(vars.size());
+    double ms_total = 0.0, cut_nnz = 0.0;
+    for (size_t q = 0; q < nbat; ++q) {
+        const int nreq = (int)std::min<size_t>(R, vars.size() - q * R);
+        b.req = req.p + q * R;
+        HIPCHECK(hipEventRecord(e[0], st));
+        launch_cut_generate(dv, g, b, nreq, hreq.data() + q * R, fd.p, cnt.p, off.p, d_scan_tmp.p, len.p, rhs.p, st);
+        HIPCHECK(hipEventRecord(e[1], st));
+        HIPCHECK(hipGetLastError());
+        int hlen[R];
+        double hrhs[R];
+        HIPCHECK(hipMemcpyAsync(hlen, len.p, sizeof(hlen), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(hrhs, rhs.p, sizeof(hrhs), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        size_t total = 0;
+        for (int r = 0; r < R; ++r) total += (size_t)hlen[r];
+        ocol.ensure(total + 8, 0, st); oval.ensure(total + 8, 0, st);
+        HIPCHECK(hipEventRecord(e[2], st));
+        launch_cut_fill(dv, fd.p, N, off.p, ocol.p, oval.p, enable_pse, st);
+        HIPCHECK(hipEventRecord(e[3], st));
+        HIPCHECK(hipGetLastError());
+        std::vector<int> hc(total);
+        std::vector<double> hv(total);
+        if (total) {
+            HIPCHECK(hipMemcpyAsync(hc.data(), ocol.p, total * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipMemcpyAsync(hv.data(), oval.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHECK(hipStreamSynchronize(st));
+        float ms0 = 0.f, ms1 = 0.f;
+        HIPCHECK(hipEventElapsedTime(&ms0, e[0], e[1]));
+        HIPCHECK(hipEventElapsedTime(&ms1, e[2], e[3]));
+        ms_total += (double)ms0 + (double)ms1;
+        size_t at = 0;
+        for (int r = 0; r < nreq; ++r) {  // rows are request-major, each sorted by variable
+            Constraint& c = cuts[q * R + r];
+            c.op = 1;
+            c.rhs = hrhs[r];
+            c.idx.assign(hc.begin() + at, hc.begin() + at + hlen[r]);
+            c.val.assign(hv.begin() + at, hv.begin() + at + hlen[r]);
+            at += (size_t)hlen[r];
+        }
+        cut_nnz += (double)total;
+    }
+    // algorithmic bytes of the generation, per batch: the block (cleared, then written), one pass over A (12 bytes per entry) with
+    // a gather of R doubles per entry, the dense block of f (written once, read by the count and by the fill), the per-variable
+    // flags, the counts and offsets; per request the stored rows the block is made of; and the emitted rows (12 bytes per term)
+    const double nz = (double)h_rcol.size();
+    const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
+    info.batches = nbat;
+    info.bytes = (double)nbat * (16.0 * (double)m * R + nz * (12.0 + 8.0 * R) + 24.0 * (double)N * R + 4.0 * N + 12.0 * (double)ncnt)
+                 + (double)vars.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * cut_nnz;
+    info.device_ms = ms_total;
+    info.wall_ms += (now_s() - t0) * 1e3;
+    add_constraints(std::move(cuts), info, true);
+}
+
 // ------------------------------------------------------------------ from-scratch nucleus inverse
 // Counterpart of BasisSolver::reset (solver.rs:1286-1303): classify the basic columns (singleton vs
 // nucleus), build K = B[R_K, P_K] densely from the CSC and invert it on the device.
@@ -3435,6 +3721,11 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
         HIPCHECK(hipStreamSynchronize(st));
         tmp = {(double)(h & 0xffffffffull), (double)(h >> 32), (double)k_};
     } else if (w == "reinvert_scale") tmp = {last_reinvert_scale};  // max |entry| of the fresh nucleus inverse of the last reinvert()
+    else if (w == "lowrank_pending") {  // delayed-update mode: [pending rank-1 terms of the inverse as the device holds them, capacity J]
+        pull_ctl();
+        sync_view();
+        tmp = {(double)(fac_on_ || hview.lrJ ? h_ctl->nlow : 0), (double)hview.lrJ};
+    }
     else if (w == "host_basic_vars") tmp.assign(h_basic_vars.begin(), h_basic_vars.end());
     else if (w == "host_nb_vars") tmp.assign(h_nb_vars.begin(), h_nb_vars.end());
     else return (uint64_t)-1;

@@ -567,6 +567,17 @@ struct RangingBufs {
 // h_req: the batch's requests as the host holds them (the compact factor runs one solve per request)
 void launch_ranging_batch(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st);
 int ranging_blocks(const Geom& g, int kind, int N);  // workgroups of the batch's sweep (= rows of RangingBufs.part)
+// the block of one batch alone (rows / nucleus columns of B^-1 of its requests), without the ratio-test pass
+void launch_ranging_block(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st);
+// a round of Gomory cuts (cuts.inc), one batch of at most RG_BATCH basic positions: launch_cut_generate forms the rows of B^-1
+// (b.blk, b.req, compact factor: b.unit / b.tau / b.rv as for ranging), the dense block fd[N][RG_BATCH] of f = floor(alpha) - alpha by
+// variable, the scanned offsets off[RG_BATCH * cut_segments(N)] (cnt: same size, sums: the scan's scratch), the row lengths len and the
+// right-hand sides rhs (RG_BATCH each); launch_cut_fill writes the rows (request-major, sorted by variable) into ocol / oval and, if
+// asked, adds f^2 to the primal edge norms.  Reads the solver state; writes only these buffers (and gamma).
+int cut_segments(int N);
+void launch_cut_generate(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* fd, int* cnt,
+                         int* off, int* sums, int* len, double* rhs, hipStream_t st);
+void launch_cut_fill(const DevView& dv, const double* fd, int N, const int* off, int* ocol, double* oval, bool gamma, hipStream_t st);
 // blocked in-place Gauss-Jordan inversion of the nucleus held in dv.W (inverse.inc); *flag = 1: singular
 void launch_blocked_inverse(const DevView& dv, int k, double* rowbuf, int nrowbuf, int* piv, int* src, double* prow, double* ckey,
                             int* cidx, int* flag, hipStream_t st);
@@ -574,6 +585,11 @@ void launch_blocked_inverse(const DevView& dv, int k, double* rowbuf, int nrowbu
 // device-side matrix maintenance (add_constraint without a host pass over the non-zeros; also the initial builds)
 void launch_csc_append_row(const int* optr, const int* orow, const double* oval, int n_old, int new_row, const int* ncols,
                            const double* nvals, int kn, int* nptr, int* nrow, double* nval, hipStream_t st);
+// R rows at once: rptr[0..R] / rcol / rval are the new rows as the CSR holds them (sorted terms on old columns, then the slack);
+// cnt: n_old + 1 ints (per-column counts, then their scan), sums: the scan's scratch
+void launch_csc_append_rows(const int* optr, const int* orow, const double* oval, int n_old, int row0, int R, const int* rptr,
+                            const int* rcol, const double* rval, int* cnt, int* sums, int* nptr, int* nrow, double* nval,
+                            hipStream_t st);
 void launch_exclusive_scan(const int* in, int* out, long n, int* sums, hipStream_t st);  // sums: ceil(n / 4096) + 1 ints; sums[last] = total
 void launch_band_count(const int* cptr, const int* crow, int N, int nbands, int* cnt, hipStream_t st);
 // packed non-basic copy of the banded sweep: segment lengths by index of the pass (then an exclusive scan), then the copy

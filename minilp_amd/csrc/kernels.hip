@@ -5389,6 +5389,7 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
 }
 #include "duals.inc"  // dual values, reduced costs and the KKT certificate (side-effect free reads of the solver state)
 #include "ranging.inc"  // cost / rhs ranging: batched rows / columns of B^-1 and one ratio-test pass per batch (side-effect free)
+#include "cuts.inc"  // a round of cuts: 16 Gomory rows per pass over A as sparse rows, and the CSC re-layout for R appended rows
 
 void launch_gauss_jordan(double* Kd, double* Winv, int k, int ld, int* d_flag, double* d_scratch, hipStream_t st) {
     if (k <= 0) return;

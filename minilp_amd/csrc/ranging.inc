@@ -246,7 +246,8 @@ __global__ void __launch_bounds__(BLK) k_rg_final(RangingBufs b, int nb) {
 static inline int rg_lanes(const Geom& g) { return g.lanes <= 4 ? 4 : g.lanes <= 16 ? 16 : 64; }
 int ranging_blocks(const Geom& g, int kind, int N) { return blocks_for((long)(kind == 0 ? N : g.m) * rg_lanes(g)); }
 
-void launch_ranging_batch(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st) {
+// the block of one batch: rows (kind 0) / nucleus columns (kind 1) of B^-1 of its requests (cuts.inc takes its rows here too)
+void launch_ranging_block(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st) {
     constexpr int R = RG_BATCH;
     const int m = g.m;
     const size_t rows = (kind == 0 || b.fac) ? (size_t)m : (size_t)b.k;
@@ -265,6 +266,10 @@ void launch_ranging_batch(const DevView& dv, const Geom& g, const RangingBufs& b
     } else if (b.k > 0) {
         hipLaunchKernelGGL(k_rg_cols<R>, dim3(blocks_for(b.k)), dim3(BLK), 0, st, dv, b);
     }
+}
+void launch_ranging_batch(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st) {
+    constexpr int R = RG_BATCH;
+    launch_ranging_block(dv, g, b, kind, nreq, h_req, st);
     const int nb = ranging_blocks(g, kind, b.N);
     if (kind == 0)
         LANES_SWITCH(g.lanes,
