@@ -1,5 +1,7 @@
 """Differential fuzz on medium instances of the generator families (every back-end feature on by env
-rotation): objective parity with the oracle and feasibility; pivot-for-pivot on the non-degenerate families."""
+rotation): objective parity with the oracle and feasibility; pivot-for-pivot on the non-degenerate families.
+The degenerate integer-data families of tests/degenerate_lp.py (assignment, unit_transport, unit_cover,
+two_matching) are in the rotation too: objective and feasibility only, their ties are broken differently by design."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -7,6 +9,7 @@ import minilp_amd as M
 from minilp_amd import lpgen
 from oracle import minilp_oracle as O
 from tests.common import check_feasible, obj_close
+from tests import degenerate_lp as D
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 rng = np.random.default_rng(12345)
@@ -38,10 +41,12 @@ if os.environ.get("FUZZ_ENVS") == "factor":   # round 5, second session: the com
     ENVS = [{"MLP_FACTOR": "1"}, {"MLP_FACTOR": "1", "MLP_FACTOR_SB_FROM": "2"}, {"MLP_FACTOR": "1", "MLP_FACTOR_SB_FROM": "2", "MLP_FACTOR_J": "5"},
             {"MLP_FACTOR": "1", "MLP_FACTOR_BUMP": "16"},
             {"MLP_FACTOR": "1", "MLP_FACTOR_SB": "0"}, {"MLP_FACTOR": "1", "MLP_FACTOR_SB_FROM": "2", "MLP_FACTOR_J": "64", "MLP_NO_GRAPH": "1"}]
+FAMILIES = ["sparse", "cover", "mixed", "dense", "twophase", "assignment", "unit_transport", "unit_cover", "two_matching"]
+DEGENERATE = ("mixed", "assignment", "unit_transport", "unit_cover", "two_matching")   # ties: no pivot-for-pivot comparison
 bad = 0
 t0 = time.time()
 for case in range(n_cases):
-    fam = ["sparse", "cover", "mixed", "dense", "twophase"][case % 5]
+    fam = FAMILIES[case % len(FAMILIES)]
     m = int(rng.integers(40, 500)); n = int(rng.integers(40, 500)); k = int(rng.integers(3, min(n, 25)))
     seed = int(rng.integers(1, 10**6))
     if fam == "sparse":
@@ -53,9 +58,17 @@ for case in range(n_cases):
         lp = lpgen.gen_twophase_lp(m, n, k, seed)
     elif fam == "mixed":
         lp = lpgen.gen_mixed_lp(m, n, min(k, 8), seed)
+    elif fam == "assignment":
+        lp = D.assignment(8 + m % 40, seed)
+    elif fam == "unit_transport":
+        lp = D.unit_transport(max(10, m // 4), max(m, n), min(k, 6), seed)     # (D >= 4 S: every supply node gets an arc)
+    elif fam == "unit_cover":
+        lp = D.unit_cover(m, n, min(k, 8), seed)
+    elif fam == "two_matching":
+        lp = D.two_matching(D.grid_points(4 + m % 6, 4 + n % 6), nearest=8 + k % 5)
     else:
         lp = lpgen.gen_dense_lp(min(m, 150), min(n, 150), seed)
-    env = ENVS[case % len(ENVS)]
+    env = ENVS[(case // len(FAMILIES)) % len(ENVS)]   # (a rotation of its own: every family meets every set, whatever the two lengths share)
     for kk in ("MLP_LOWRANK", "MLP_BIGTILE", "MLP_LDPAD", "MLP_BANDED", "MLP_GRAPH_ITERS", "MLP_NO_GRAPH", "MLP_DETERMINISTIC", "MLP_HYPER",
                "MLP_HEAD_APPLY", "MLP_PULL_INSIDE", "MLP_PRIMAL_HEAD_K", "MLP_RATIO_ONE", "MLP_STREAM_BALANCED", "MLP_ORDER_FROM", "MLP_ORDER_EVERY",
                "MLP_SWEEP_PACKED", "MLP_FACTOR", "MLP_FACTOR_SB_FROM", "MLP_FACTOR_J", "MLP_FACTOR_BUMP", "MLP_FACTOR_SB", "MLP_STR_K", "MLP_FPULL"):
@@ -84,7 +97,7 @@ for case in range(n_cases):
             except AssertionError:
                 ok = False
                 why = "feasibility"
-        if ok and fam != "mixed":
+        if ok and fam not in DEGENERATE:
             a, b = [t[:5] for t in sg.trace()], [t[:5] for t in so.trace()]
             ok = a == b
             if not ok:
