@@ -2,10 +2,11 @@
 """solve_mps — counterpart of the reference's examples/solve_mps.rs (19-43): read a free-format MPS file,
 minimise, print the objective and the non-zero variables.
 
-    python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--gomory-rounds K]
+    python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--tableau VAR] [--gomory-rounds K]
 
 --ranging adds a sensitivity table: per variable its value, basis status, reduced cost and cost range; per row its dual value and
-rhs range (rows in file order).  --gomory-rounds K adds K rounds of Gomory cuts, each over all basic structural variables with a
+rhs range (rows in file order).  --tableau VAR prints the tableau row of the basic variable VAR (by name): its non-zero coefficients on the
+non-basic variables and on the slacks of the rows, the raw material of a mixed-integer cut.  --gomory-rounds K adds K rounds of Gomory cuts, each over all basic structural variables with a
 fractional value (|x - round x| > 1e-6) in one add_gomory_cuts call, and prints the bound and the call's counters after each round.
 
 Runs on the MI355X engine (libminilp_hip.so); there is no CPU back end.  `run(B, ...)` takes the module that
@@ -18,7 +19,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0):
+def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -49,6 +50,19 @@ def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0)
         print("%-12s %-6s %14s   %s" % ("row", "status", "dual value", "rhs range"))
         for c in range(sol.num_constraints):
             print("%-12d %-6s %14.8g   [%.8g, %.8g]" % (c, tag[cs[c]], pi[c], rlo[c], rhi[c]))
+    if tableau is not None:
+        if tableau not in f.variables:
+            print("tableau: no variable named %s" % tableau)
+            return 1
+        var = f.variables[tableau]
+        if var not in sol.basis_head():
+            print("tableau: %s is not basic (value %.12g)" % (tableau, x[var]))
+            return 1
+        names = {v: n for n, v in f.variables.items()}
+        ip, ix, dv = sol.tableau_rows([var])
+        print("tableau row of %s (= %.12g):" % (tableau, x[var]))
+        for col, a in zip(ix, dv):
+            print("  %-12s %.12g" % (names[col] if col < len(x) else "slack(row %d)" % (col - len(x)), a))
     for k in range(gomory_rounds):
         x = sol.values()
         vs, _ = sol.basis_status()
@@ -73,9 +87,10 @@ def main():
     ap.add_argument("--ranging", action="store_true", help="print the sensitivity table (status, reduced costs, duals, cost and rhs ranges)")
     ap.add_argument("--gomory-rounds", type=int, default=0, metavar="K",
                     help="K rounds of Gomory cuts over the fractional basic variables (one add_gomory_cuts call per round)")
+    ap.add_argument("--tableau", metavar="VAR", help="print the tableau row of the basic variable VAR (by name)")
     a = ap.parse_args()
     import minilp_amd as B
-    return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds)
+    return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau)
 
 
 if __name__ == "__main__":

@@ -42,6 +42,9 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * (mlp_ranging_info, with its own mlp_ranging_info_size()); mlp_stats and mlp_certificate are untouched, no existing layout moved. */
 /* Still version 5: the cut-round entry points (mlp_solution_add_constraints_csr, mlp_solution_add_gomory_cuts, mlp_cut_info) are
  * additive in the same way. */
+/* Still version 5: the tableau entry points (mlp_solution_num_rows, mlp_solution_basis_head, mlp_solution_binv_rows / _binv_cols,
+ * mlp_solution_tableau_rows / _tableau_cols, mlp_solution_basis_solve, mlp_tableau_info with its own mlp_tableau_info_size()) are
+ * additive in the same way. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -330,6 +333,60 @@ typedef struct mlp_cut_info {
 } mlp_cut_info;
 int mlp_solution_cut_info(const mlp_solution* s, mlp_cut_info* out);
 uint64_t mlp_cut_info_size(void);
+
+/* ---- Reading the simplex tableau: rows and columns of B^-1 A, of B^-1, solves with the basis (what GLPK calls glp_eval_tab_row / _col
+ *      and glp_ftran / glp_btran; the raw material of mixed-integer cuts, custom ranging and post-optimal analysis) ------------------------
+ * Internal form, as for the ranging above: A x + s = b, Abar = [A | I], B = the basic columns of Abar at the CURRENT basis, whatever it is
+ * (optimum, budget-limited solve, solve_from_basis, after any mutator).  Nothing here depends on the optimisation direction: there is no
+ * sign turn for Maximize.
+ * Columns: j < num_vars is structural variable j; num_vars + c is the slack of constraint c, in the constraint numbering of
+ *   mlp_solution_dual_values.  A constraint without terms has no row and no slack column: asking for it is MLP_EINVAL, and it never
+ *   appears in an output.
+ * Vectors "by row" are exchanged BY CONSTRAINT and have length mlp_solution_num_constraints: a constraint without a row reads 0.0 on
+ *   output and is ignored on input.
+ * Basis positions run 0 .. num_rows - 1, num_rows = mlp_solution_num_rows = the constraints that have a row; basis_head[p] is the column
+ *   (numbering above) basic at position p, in the engine's own position order (mlp_solution_state "host_basic_vars").  Vectors "by
+ *   position" have length num_rows.
+ * mlp_solution_binv_rows:    for each listed BASIC column, rho_p = e_p^T B^-1 of its position p, by constraint: out[n][num_constraints].
+ * mlp_solution_binv_cols:    for each listed constraint (it must have a row), h = B^-1 e_row by position: out[n][num_rows].
+ * mlp_solution_tableau_rows: for each listed BASIC column, alpha_p = rho_p^T Abar as a sparse row in CSR (indptr[n + 1], indices, values)
+ *   over the column numbering: sorted by column, exact zeros dropped (as the Gomory generation drops them), the entry of the requested
+ *   column itself exactly 1.0, the other basic columns omitted (they are 0 by definition and are not computed).  The three arrays are
+ *   owned by the library and stay valid until the next tableau call, mutator, continue, engine stage, re-inversion or free of that
+ *   solution.
+ * mlp_solution_tableau_cols: for each listed column j (basic or not), B^-1 abar_j by position: out[n][num_rows]; a basic column gives the
+ *   exact unit vector of its position.
+ * mlp_solution_basis_solve:  transpose == 0: rhs[n][num_constraints] by constraint -> out[n][num_rows] = B^-1 rhs by position (FTRAN);
+ *   transpose != 0: rhs[n][num_rows] by position -> out[n][num_constraints] = B^-T rhs by constraint (BTRAN).
+ * The dense forms write into caller buffers; rhs_len / out_len are their lengths in doubles and must be exactly n times the row length
+ * stated above.  Lists may hold duplicates, in any order.
+ * Guarantees: (1) reading is side-effect free like the dual values — the solution continues pivot for pivot and bit for bit as if nothing
+ * had been read, and its mode-2 basis blob is unchanged; (2) the numbers of one request are bit-identical whatever else is in the call, in
+ * whatever order, and from run to run (requests are served in batches of 16 that share one pass over the inverse / over A; no sum
+ * depends on its place in a batch, no float atomics).
+ * Errors, all MLP_EINVAL with the solution still usable: a NULL handle, a sharded solution, a wrong length, an index out of range, the
+ * slack of a constraint without terms, a non-basic column given to binv_rows / tableau_rows.  n == 0 is a successful no-op.
+ * mlp_tableau_info: counters of the last of these calls on this solution (zeros before the first).  Only grows at its end;
+ *   mlp_tableau_info_size() is its size as the library was built. */
+uint64_t mlp_solution_num_rows(const mlp_solution* s);
+int mlp_solution_basis_head(const mlp_solution* s, uint64_t* head, uint64_t num_rows);
+int mlp_solution_binv_rows(const mlp_solution* s, const uint64_t* cols, uint64_t n, double* out, uint64_t out_len);
+int mlp_solution_binv_cols(const mlp_solution* s, const uint64_t* constraints, uint64_t n, double* out, uint64_t out_len);
+int mlp_solution_tableau_rows(const mlp_solution* s, const uint64_t* cols, uint64_t n, const uint64_t** indptr, const uint32_t** indices,
+                              const double** values);
+int mlp_solution_tableau_cols(const mlp_solution* s, const uint64_t* cols, uint64_t n, double* out, uint64_t out_len);
+int mlp_solution_basis_solve(const mlp_solution* s, int transpose, const double* rhs, uint64_t rhs_len, uint64_t n, double* out,
+                             uint64_t out_len);
+typedef struct mlp_tableau_info {
+    uint64_t requests;   /* rows / columns / right-hand sides asked for */
+    uint64_t solves;     /* of them: right-hand sides that needed the device (all but basic columns given to tableau_cols) */
+    uint64_t batches;    /* batches of 16 of them: one pass over the inverse (solves) / the rows' block and one pass over A (tableau rows) each */
+    uint64_t nnz;        /* terms emitted by tableau_rows (0 for the dense forms) */
+    double bytes;        /* algorithmic bytes of the batches */
+    double device_ms;    /* their time on the device (HIP events around the launches) */
+} mlp_tableau_info;
+int mlp_solution_tableau_info(const mlp_solution* s, mlp_tableau_info* out);
+uint64_t mlp_tableau_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

@@ -47,6 +47,18 @@ pub struct mlp_iter_info {
     pub nucleus_size: u64,
 }
 
+/// Counters of the last tableau call on a solution (only grows at its end; `mlp_tableau_info_size()` is the library's size).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct mlp_tableau_info {
+    pub requests: u64,
+    pub solves: u64,
+    pub batches: u64,
+    pub nnz: u64,
+    pub bytes: c_double,
+    pub device_ms: c_double,
+}
+
 extern "C" {
     pub fn mlp_last_error() -> *const c_char;
     pub fn mlp_device_count() -> c_int;
@@ -99,6 +111,16 @@ extern "C" {
     pub fn mlp_solution_add_gomory_cuts(s: *mut *mut mlp_solution, vars: *const u32, n: u64) -> c_int;
     pub fn mlp_solution_cut_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
     pub fn mlp_cut_info_size() -> u64;
+    // reading the tableau: rows / columns of B^-1 A and of B^-1, solves with the basis (additive: the ABI version stays 5)
+    pub fn mlp_solution_num_rows(s: *const mlp_solution) -> u64;
+    pub fn mlp_solution_basis_head(s: *const mlp_solution, head: *mut u64, num_rows: u64) -> c_int;
+    pub fn mlp_solution_binv_rows(s: *const mlp_solution, cols: *const u64, n: u64, out: *mut f64, out_len: u64) -> c_int;
+    pub fn mlp_solution_binv_cols(s: *const mlp_solution, constraints: *const u64, n: u64, out: *mut f64, out_len: u64) -> c_int;
+    pub fn mlp_solution_tableau_rows(s: *const mlp_solution, cols: *const u64, n: u64, indptr: *mut *const u64, indices: *mut *const u32, values: *mut *const f64) -> c_int;
+    pub fn mlp_solution_tableau_cols(s: *const mlp_solution, cols: *const u64, n: u64, out: *mut f64, out_len: u64) -> c_int;
+    pub fn mlp_solution_basis_solve(s: *const mlp_solution, transpose: c_int, rhs: *const f64, rhs_len: u64, n: u64, out: *mut f64, out_len: u64) -> c_int;
+    pub fn mlp_solution_tableau_info(s: *const mlp_solution, out: *mut mlp_tableau_info) -> c_int;
+    pub fn mlp_tableau_info_size() -> u64;
     pub fn mlp_solution_continue(s: *mut mlp_solution, pivot_budget: i64) -> c_int;
     pub fn mlp_solution_budget_exhausted(s: *const mlp_solution) -> c_int;
     pub fn mlp_solution_reinvert(s: *mut mlp_solution, max_diff: *mut c_double) -> c_int;

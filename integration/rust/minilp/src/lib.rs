@@ -408,6 +408,75 @@ impl Solution {
         vs[var.0] == 0
     }
 
+    // ---- reading the tableau (extension: no counterpart in the reference; numbering and definitions in include/minilp_hip.h).
+    // Columns: j < num_vars is variable j, num_vars + c the slack of constraint c.  Vectors by row are exchanged by constraint
+    // (length num_constraints), vectors by position have length num_rows.  Internal form A x + s = b: no sign turn for Maximize.
+
+    /// Number of constraints that have a row (= basis positions).
+    pub fn num_rows(&self) -> usize {
+        unsafe { sys::mlp_solution_num_rows(self.raw) as usize }
+    }
+
+    /// The column basic at each position.
+    pub fn basis_head(&self) -> Vec<usize> {
+        let mut h = vec![0u64; self.num_rows()];
+        let st = unsafe { sys::mlp_solution_basis_head(self.raw, h.as_mut_ptr(), h.len() as u64) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        h.into_iter().map(|c| c as usize).collect()
+    }
+
+    /// Row e_p^T B^-1 (by constraint) of the position p at which the given column is basic.
+    pub fn binv_row(&self, basic_col: usize) -> Vec<f64> {
+        let (c, mut out) = (basic_col as u64, vec![0.0f64; self.num_constraints()]);
+        let st = unsafe { sys::mlp_solution_binv_rows(self.raw, &c, 1, out.as_mut_ptr(), out.len() as u64) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        out
+    }
+
+    /// Column B^-1 e_row (by position) of the row of the given constraint.
+    pub fn binv_col(&self, constraint: usize) -> Vec<f64> {
+        let (c, mut out) = (constraint as u64, vec![0.0f64; self.num_rows()]);
+        let st = unsafe { sys::mlp_solution_binv_cols(self.raw, &c, 1, out.as_mut_ptr(), out.len() as u64) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        out
+    }
+
+    /// Tableau row e_p^T B^-1 [A | I] of a basic column as `(column, coefficient)` pairs sorted by column: exact zeros and the
+    /// other basic columns are left out, the column's own coefficient is exactly 1.
+    pub fn tableau_row(&self, basic_col: usize) -> Vec<(usize, f64)> {
+        let c = basic_col as u64;
+        let (mut ip, mut ix, mut dv): (*const u64, *const u32, *const f64) = (ptr::null(), ptr::null(), ptr::null());
+        let st = unsafe { sys::mlp_solution_tableau_rows(self.raw, &c, 1, &mut ip, &mut ix, &mut dv) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        // (the three arrays belong to the library until the next tableau call: copied here)
+        let n = unsafe { *ip.add(1) } as usize;
+        (0..n).map(|e| unsafe { (*ix.add(e) as usize, *dv.add(e)) }).collect()
+    }
+
+    /// Tableau column B^-1 a_j (by position) of any column; a basic one gives the unit vector of its position.
+    pub fn tableau_col(&self, col: usize) -> Vec<f64> {
+        let (c, mut out) = (col as u64, vec![0.0f64; self.num_rows()]);
+        let st = unsafe { sys::mlp_solution_tableau_cols(self.raw, &c, 1, out.as_mut_ptr(), out.len() as u64) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        out
+    }
+
+    /// B^-1 rhs: `rhs` by constraint, the result by position.
+    pub fn ftran(&self, rhs: &[f64]) -> Vec<f64> {
+        let mut out = vec![0.0f64; self.num_rows()];
+        let st = unsafe { sys::mlp_solution_basis_solve(self.raw, 0, rhs.as_ptr(), rhs.len() as u64, 1, out.as_mut_ptr(), out.len() as u64) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        out
+    }
+
+    /// B^-T rhs: `rhs` by position, the result by constraint.
+    pub fn btran(&self, rhs: &[f64]) -> Vec<f64> {
+        let mut out = vec![0.0f64; self.num_constraints()];
+        let st = unsafe { sys::mlp_solution_basis_solve(self.raw, 1, rhs.as_ptr(), rhs.len() as u64, 1, out.as_mut_ptr(), out.len() as u64) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        out
+    }
+
     /// Iterate over the variable-value pairs of the solution.
     pub fn iter(&self) -> SolutionIter {
         SolutionIter { solution: self, var_idx: 0 }

@@ -66,6 +66,11 @@ class MlpCutInfo(C.Structure):  # include/minilp_hip.h: mlp_cut_info (only grows
                 ("bytes", C.c_double), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class MlpTableauInfo(C.Structure):  # include/minilp_hip.h: mlp_tableau_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("solves", C.c_uint64), ("batches", C.c_uint64), ("nnz", C.c_uint64),
+                ("bytes", C.c_double), ("device_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -183,6 +188,18 @@ def lib():
     sig("mlp_solution_add_constraints_csr", i32, C.POINTER(vp), u64, C.POINTER(C.c_uint64), pu32, pdbl, C.POINTER(C.c_int32), pdbl)
     sig("mlp_solution_add_gomory_cuts", i32, C.POINTER(vp), pu32, u64)
     sig("mlp_solution_cut_info", i32, vp, C.POINTER(MlpCutInfo))
+    sig("mlp_tableau_info_size", u64)
+    if L.mlp_tableau_info_size() != C.sizeof(MlpTableauInfo):
+        raise ImportError(f"{_SO}: mlp_tableau_info is {L.mlp_tableau_info_size()} bytes, this binding {C.sizeof(MlpTableauInfo)}: rebuild it")
+    pu64 = C.POINTER(C.c_uint64)
+    sig("mlp_solution_num_rows", u64, vp)
+    sig("mlp_solution_basis_head", i32, vp, pu64, u64)
+    sig("mlp_solution_binv_rows", i32, vp, pu64, u64, pdbl, u64)
+    sig("mlp_solution_binv_cols", i32, vp, pu64, u64, pdbl, u64)
+    sig("mlp_solution_tableau_rows", i32, vp, pu64, u64, C.POINTER(pu64), C.POINTER(pu32), C.POINTER(pdbl))
+    sig("mlp_solution_tableau_cols", i32, vp, pu64, u64, pdbl, u64)
+    sig("mlp_solution_basis_solve", i32, vp, i32, pdbl, u64, u64, pdbl, u64)
+    sig("mlp_solution_tableau_info", i32, vp, C.POINTER(MlpTableauInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -460,6 +477,81 @@ class Solution:
         r = MlpRangingInfo()
         _raise(lib().mlp_solution_ranging_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in MlpRangingInfo._fields_}
+
+    # ---- reading the tableau (include/minilp_hip.h: mlp_solution_binv_rows ...; numbering and definitions there): columns are
+    #      j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by constraint; internal
+    #      form A x + s = b, no sign turn for Maximize
+    @property
+    def num_rows(self):
+        """Constraints that have a row (= basis positions)."""
+        return lib().mlp_solution_num_rows(self._h)
+
+    def basis_head(self):
+        """int64[num_rows]: the column basic at each position."""
+        a = np.zeros(self.num_rows, dtype=np.uint64)
+        _raise(lib().mlp_solution_basis_head(self._h, _p(a, C.c_uint64), len(a)))
+        return a.astype(np.int64)
+
+    @staticmethod
+    def _tab_list(which):
+        w = np.asarray(which)
+        if w.ndim != 1 and w.size:
+            raise InternalError(-1, "tableau: the index list must be one-dimensional")
+        w = np.ascontiguousarray(w, dtype=np.int64).reshape(-1)
+        if len(w) and w.min() < 0:
+            raise InternalError(-1, "tableau: index out of range")
+        return w.astype(np.uint64)
+
+    def _tab_dense(self, fn, which, row_len):
+        w = self._tab_list(which)
+        out = np.zeros((len(w), row_len), dtype=np.float64)
+        _raise(fn(self._h, _p(w, C.c_uint64), len(w), _p(out, C.c_double), out.size))
+        return out
+
+    def binv_rows(self, cols):
+        """float64[n, num_constraints]: e_p^T B^-1 by constraint, p the position of each listed basic column."""
+        return self._tab_dense(lib().mlp_solution_binv_rows, cols, self.num_constraints)
+
+    def binv_cols(self, constraints):
+        """float64[n, num_rows]: B^-1 e_row by position, for each listed constraint."""
+        return self._tab_dense(lib().mlp_solution_binv_cols, constraints, self.num_rows)
+
+    def tableau_cols(self, cols):
+        """float64[n, num_rows]: B^-1 abar_j by position, for each listed column (a basic one: the unit vector of its position)."""
+        return self._tab_dense(lib().mlp_solution_tableau_cols, cols, self.num_rows)
+
+    def tableau_rows(self, cols):
+        """CSR (indptr, indices, data) over the column numbering: alpha_p = e_p^T B^-1 [A | I] for each listed basic column, sorted by
+        column, exact zeros and the other basic columns dropped, the column's own entry exactly 1.0."""
+        w = self._tab_list(cols)
+        ip, ix, dv = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint32)(), C.POINTER(C.c_double)()
+        _raise(lib().mlp_solution_tableau_rows(self._h, _p(w, C.c_uint64), len(w), C.byref(ip), C.byref(ix), C.byref(dv)))
+        indptr = np.ctypeslib.as_array(ip, shape=(len(w) + 1,)).astype(np.int64)  # (copies: the buffers belong to the library)
+        nnz = int(indptr[-1])
+        if nnz == 0:
+            return indptr, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64)
+        return indptr, np.ctypeslib.as_array(ix, shape=(nnz,)).astype(np.int64), np.ctypeslib.as_array(dv, shape=(nnz,)).copy()
+
+    def basis_solve(self, rhs, transpose=False):
+        """rhs [n, num_constraints] by constraint -> B^-1 rhs [n, num_rows] by position; transpose=True: rhs [n, num_rows] by position
+        -> B^-T rhs [n, num_constraints] by constraint.  A one-dimensional rhs is one right-hand side and gives a one-dimensional result."""
+        r = np.ascontiguousarray(rhs, dtype=np.float64)
+        one = r.ndim == 1
+        if one:
+            r = r.reshape(1, -1)
+        n_in, n_out = (self.num_rows, self.num_constraints) if transpose else (self.num_constraints, self.num_rows)
+        if r.ndim != 2 or r.shape[1] != n_in:
+            raise InternalError(-1, f"basis_solve: rhs must be [n, {n_in}]")
+        out = np.zeros((r.shape[0], n_out), dtype=np.float64)
+        _raise(lib().mlp_solution_basis_solve(self._h, 1 if transpose else 0, _p(r, C.c_double), r.size, r.shape[0], _p(out, C.c_double),
+                                              out.size))
+        return out[0] if one else out
+
+    def tableau_info(self):
+        """Counters of the last tableau call (mlp_tableau_info) as a dict."""
+        r = MlpTableauInfo()
+        _raise(lib().mlp_solution_tableau_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpTableauInfo._fields_}
 
     def add_constraint(self, expr, cmp_op, rhs):
         idx, val = _terms(expr)

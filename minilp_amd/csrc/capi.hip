@@ -21,6 +21,10 @@ struct mlp_solution {
     Engine::Duals duals;
     Engine::RangingInfo ranging;  // of the last mlp_solution_cost_ranging / mlp_solution_rhs_ranging call
     Engine::CutInfo cuts;         // of the last mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts call
+    Engine::TableauInfo tableau;  // of the last tableau call
+    std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
+    std::vector<uint32_t> tab_indices;
+    std::vector<double> tab_values;
     ~mlp_solution() { delete eng; }
 };
 // every entry point that can change the state of a solution drops the cached duals
@@ -84,6 +88,19 @@ static int ranging_call(const mlp_solution* cs, int kind, const I* which, uint64
         for (uint64_t i = 0; i < n; ++i) idx[i] = which ? (uint64_t)which[i] : i;
         s->eng->ranging(kind, idx, d, lo, hi, s->ranging);
     });
+}
+
+// the tableau reads: refuse a NULL handle and a sharded solution (a one-rank pump included), check the list and the caller's buffer
+static mlp_solution* tableau_handle(const mlp_solution* cs) {
+    mlp_solution* s = const_cast<mlp_solution*>(cs);
+    if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+    if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "the tableau is not available on a sharded solution");
+    return s;
+}
+static std::vector<uint64_t> tableau_list(const uint64_t* idx, uint64_t n, const double* out, uint64_t out_len, uint64_t row_len) {
+    if (n && !idx) throw MlpError(MLP_EINVAL, "tableau: NULL index list");
+    if (out_len != n * row_len || (out_len && !out)) throw MlpError(MLP_EINVAL, "tableau: the output length must be n times the row length");
+    return std::vector<uint64_t>(idx, idx + n);
 }
 
 extern "C" {
@@ -481,6 +498,83 @@ int mlp_solution_cut_info(const mlp_solution* s, mlp_cut_info* out) {
     });
 }
 uint64_t mlp_cut_info_size(void) { return (uint64_t)sizeof(mlp_cut_info); }
+
+// ---- reading the tableau (tableau.inc)
+uint64_t mlp_solution_num_rows(const mlp_solution* s) { return s ? (uint64_t)s->eng->num_rows() : 0; }
+int mlp_solution_basis_head(const mlp_solution* cs, uint64_t* head, uint64_t num_rows) {
+    return guarded([&] {
+        mlp_solution* s = tableau_handle(cs);
+        if (num_rows != (uint64_t)s->eng->num_rows() || (num_rows && !head)) throw MlpError(MLP_EINVAL, "basis_head: length must be mlp_solution_num_rows");
+        std::vector<uint64_t> h;
+        s->eng->basis_head(h);
+        if (num_rows) std::memcpy(head, h.data(), sizeof(uint64_t) * h.size());
+    });
+}
+int mlp_solution_binv_rows(const mlp_solution* cs, const uint64_t* cols, uint64_t n, double* out, uint64_t out_len) {
+    return guarded([&] {
+        mlp_solution* s = tableau_handle(cs);
+        const std::vector<uint64_t> idx = tableau_list(cols, n, out, out_len, s->eng->num_constraints());
+        s->eng->binv_rows(idx, out, s->tableau);
+    });
+}
+int mlp_solution_binv_cols(const mlp_solution* cs, const uint64_t* constraints, uint64_t n, double* out, uint64_t out_len) {
+    return guarded([&] {
+        mlp_solution* s = tableau_handle(cs);
+        const std::vector<uint64_t> idx = tableau_list(constraints, n, out, out_len, (uint64_t)s->eng->num_rows());
+        s->eng->binv_cols(idx, out, s->tableau);
+    });
+}
+int mlp_solution_tableau_cols(const mlp_solution* cs, const uint64_t* cols, uint64_t n, double* out, uint64_t out_len) {
+    return guarded([&] {
+        mlp_solution* s = tableau_handle(cs);
+        const std::vector<uint64_t> idx = tableau_list(cols, n, out, out_len, (uint64_t)s->eng->num_rows());
+        s->eng->tableau_cols(idx, out, s->tableau);
+    });
+}
+int mlp_solution_tableau_rows(const mlp_solution* cs, const uint64_t* cols, uint64_t n, const uint64_t** indptr, const uint32_t** indices,
+                              const double** values) {
+    return guarded([&] {
+        mlp_solution* s = tableau_handle(cs);
+        if ((n && !cols) || !indptr || !indices || !values) throw MlpError(MLP_EINVAL, "tableau_rows: NULL argument");
+        // (each index is checked as it is read, nothing is sized by n: a garbage n ends at the first index out of range, not far past
+        // the caller's array)
+        const uint64_t ncol = (uint64_t)s->eng->num_vars + s->eng->num_constraints();
+        std::vector<uint64_t> req;
+        for (uint64_t t = 0; t < n; ++t) {
+            if (cols[t] >= ncol) throw MlpError(MLP_EINVAL, "tableau_rows: column out of range");
+            req.push_back(cols[t]);
+        }
+        std::vector<uint64_t> ip;
+        std::vector<uint32_t> ix;
+        std::vector<double> vv;
+        s->eng->tableau_rows(req, ip, ix, vv, s->tableau);  // (a refusal leaves the previous rows in place)
+        ix.reserve(ix.size() + 1);  // (never a NULL data pointer, also for rows without terms)
+        vv.reserve(vv.size() + 1);
+        s->tab_indptr.swap(ip); s->tab_indices.swap(ix); s->tab_values.swap(vv);
+        *indptr = s->tab_indptr.data(); *indices = s->tab_indices.data(); *values = s->tab_values.data();
+    });
+}
+int mlp_solution_basis_solve(const mlp_solution* cs, int transpose, const double* rhs, uint64_t rhs_len, uint64_t n, double* out,
+                             uint64_t out_len) {
+    return guarded([&] {
+        mlp_solution* s = tableau_handle(cs);
+        const uint64_t by_cons = s->eng->num_constraints(), by_pos = (uint64_t)s->eng->num_rows();
+        const uint64_t in_row = transpose ? by_pos : by_cons, out_row = transpose ? by_cons : by_pos;
+        if (rhs_len != n * in_row || out_len != n * out_row || (rhs_len && !rhs) || (out_len && !out))
+            throw MlpError(MLP_EINVAL, "basis_solve: the lengths must be n times num_constraints / num_rows");
+        s->eng->basis_solve(transpose != 0, rhs, (size_t)n, out, s->tableau);
+    });
+}
+int mlp_solution_tableau_info(const mlp_solution* s, mlp_tableau_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / tableau info");
+        std::memset(out, 0, sizeof(*out));
+        const Engine::TableauInfo& t = s->tableau;
+        out->requests = t.requests; out->solves = t.solves; out->batches = t.batches; out->nnz = t.nnz;
+        out->bytes = t.bytes; out->device_ms = t.device_ms;
+    });
+}
+uint64_t mlp_tableau_info_size(void) { return (uint64_t)sizeof(mlp_tableau_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

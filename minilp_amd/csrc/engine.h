@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <utility>
 #include <stdexcept>
 #include <string>
@@ -195,6 +196,23 @@ public:
     };
     void basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons);
     void ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du, double* lo, double* hi, RangingInfo& info);
+    // Reading the tableau of the current basis (tableau.inc; include/minilp_hip.h mlp_solution_binv_rows ...).  Columns:
+    // j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by CONSTRAINT (0 / ignored for one
+    // without a row), vectors by position have length num_rows().  Internal form A x + s = b: no sign turn for Maximize.  Requests are
+    // served in batches of RG_BATCH.  Reads the state only, like compute_duals.
+    struct TableauInfo {
+        uint64_t requests = 0, solves = 0, batches = 0, nnz = 0;
+        double bytes = 0, device_ms = 0;
+    };
+    int num_rows() const { return m_; }
+    void basis_head(std::vector<uint64_t>& out);  // column basic at each position
+    void binv_rows(const std::vector<uint64_t>& cols, double* out, TableauInfo& info);  // out[t][constraint] = (e_p^T B^-1), p = position of the basic column
+    void binv_cols(const std::vector<uint64_t>& cons, double* out, TableauInfo& info);  // out[t][position] = B^-1 e_row
+    void tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_t>& indptr, std::vector<uint32_t>& indices, std::vector<double>& values,
+                      TableauInfo& info);  // sparse rows e_p^T B^-1 [A | I], sorted by column, exact zeros and the other basic columns dropped
+    void tableau_cols(const std::vector<uint64_t>& cols, double* out, TableauInfo& info);  // out[t][position] = B^-1 a_j
+    // transpose = false: rhs[n][constraints] -> out[n][positions] = B^-1 rhs; true: rhs[n][positions] -> out[n][constraints] = B^-T rhs
+    void basis_solve(bool transpose, const double* rhs, size_t n, double* out, TableauInfo& info);
     size_t num_constraints() const { return h_cons_row.size(); }
     double last_reinvert_scale = 0.0;  // max |W_fresh| of that comparison (state "reinvert_scale")
     // Basis checkpoint (include/minilp_hip.h: mlp_solution_save_basis / mlp_problem_solve_from_basis).
@@ -536,6 +554,24 @@ private:
     void calc_row_coeffs(int row, bool with_sweep);         // solver.rs:680-693
     void fetch_values();
     void rebuild_inverse();       // BasisSolver::reset counterpart (solver.rs:1286-1303)
+    // the dense tableau reads: op 0 rows of B^-1 (req: positions), 1 columns of B^-1 (rows), 2 columns of the tableau (variables), 3 / 4
+    // FTRAN / BTRAN of rhs; a request with req < 0 is answered by the caller
+    void tab_dense(int op, const std::vector<int>& req, const double* rhs, double* out, TableauInfo& info);
+    int tab_internal_col(uint64_t col, const char* what) const;
+    // sparse rows out of dense blocks [N][RG_BATCH] for the basic positions pos, RG_BATCH at a time (gomory: f = floor(alpha) - alpha with
+    // right-hand sides and, if kept, the primal edge norms; else alpha itself); emit gets each batch as the host read it back
+    struct RowBatch {
+        int nreq;           // rows of this batch
+        const int* len;     // [RG_BATCH] terms of each row
+        const double* rhs;  // [RG_BATCH] right-hand sides (gomory)
+        const int* col;     // the rows, request-major, each sorted by variable of [A | I]
+        const double* val;
+    };
+    struct RowBatches {
+        size_t nbat = 0, ncnt = 0, nnz = 0;  // batches, counters per batch (RG_BATCH * cut_segments(N)), terms emitted
+        double device_ms = 0;                // HIP events around the launches
+    };
+    RowBatches sparse_row_batches(const std::vector<int>& pos, bool gomory, const std::function<void(size_t, const RowBatch&)>& emit);
 };
 
 // ---- MPS (mps.rs) on the host side of the product

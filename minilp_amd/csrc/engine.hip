@@ -3081,6 +3081,88 @@ void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gom
     info.wall_ms += (now_s() - t0) * 1e3;
 }
 
+namespace {
+struct TabEvents {  // (destroyed on every way out, a throwing HIPCHECK included)
+    hipEvent_t e[2] = {nullptr, nullptr};
+    TabEvents() {
+        for (auto& x : e) HIPCHECK(hipEventCreate(&x));
+    }
+    ~TabEvents() {
+        for (auto& x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+};
+}  // namespace
+// Sparse rows out of dense blocks [N][RG_BATCH], batch by batch: the host side that add_gomory_cuts and tableau_rows share.  Per batch of at
+// most RG_BATCH basic positions: phase 1 (gomory: launch_cut_generate, else launch_tab_rows) forms the rows of B^-1, the dense block, the
+// scanned offsets, the row lengths and the right-hand sides; the host reads back the lengths; launch_cut_fill writes the rows
+// (request-major, each sorted by variable), and the host reads back O(nnz of the rows).  The caller has called pull_ctl() and sync_view().
+Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, bool gomory,
+                                              const std::function<void(size_t, const RowBatch&)>& emit) {
+    const DevView& dv = hview;
+    const Geom g = geom();
+    constexpr int R = RG_BATCH;
+    const int m = m_, N = N_;
+    RowBatches out;
+    out.nbat = (pos.size() + R - 1) / R;
+    std::vector<int> hreq(out.nbat * R, -1);
+    for (size_t t = 0; t < pos.size(); ++t) hreq[t] = pos[t];
+    const int nseg = cut_segments(N);
+    out.ncnt = (size_t)R * nseg;
+    DevBuf<double> blk, dense, rhs, oval, unit, tau;
+    DevBuf<double2> rv;
+    DevBuf<int> req, cnt, off, len, ocol, scan;
+    blk.ensure((size_t)m * R + R, 0, st); dense.ensure((size_t)N * R + R, 0, st); rhs.ensure(R, 0, st); len.ensure(R, 0, st);
+    cnt.ensure(out.ncnt + 8, 0, st); off.ensure(out.ncnt + 8, 0, st);
+    scan.ensure(out.ncnt / 4096 + 8, 0, st);  // (private: d_scan_tmp is the appends' scratch)
+    req.upload(hreq, st);
+    if (fac_on_) {
+        unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
+        HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
+        HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
+    }
+    RangingBufs b{};
+    b.blk = blk.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
+    b.N = N; b.nv = num_vars; b.k = fac_on_ ? 0 : k_; b.fac = fac_on_ ? 1 : 0;
+    TabEvents e0, e1;
+    std::vector<int> hc;
+    std::vector<double> hv;
+    for (size_t q = 0; q < out.nbat; ++q) {
+        const int nreq = (int)std::min<size_t>(R, pos.size() - q * R);
+        b.req = req.p + q * R;
+        HIPCHECK(hipEventRecord(e0.e[0], st));
+        (gomory ? launch_cut_generate : launch_tab_rows)(dv, g, b, nreq, hreq.data() + q * R, dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
+        HIPCHECK(hipEventRecord(e0.e[1], st));
+        HIPCHECK(hipGetLastError());
+        int hlen[R];
+        double hrhs[R];
+        HIPCHECK(hipMemcpyAsync(hlen, len.p, sizeof(hlen), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(hrhs, rhs.p, sizeof(hrhs), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        size_t total = 0;
+        for (int r = 0; r < R; ++r) total += (size_t)hlen[r];
+        ocol.ensure(total + 8, 0, st); oval.ensure(total + 8, 0, st);
+        HIPCHECK(hipEventRecord(e1.e[0], st));
+        launch_cut_fill(dv, dense.p, N, off.p, ocol.p, oval.p, gomory && enable_pse, st);
+        HIPCHECK(hipEventRecord(e1.e[1], st));
+        HIPCHECK(hipGetLastError());
+        hc.resize(total);
+        hv.resize(total);
+        if (total) {
+            HIPCHECK(hipMemcpyAsync(hc.data(), ocol.p, total * sizeof(int), hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipMemcpyAsync(hv.data(), oval.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHECK(hipStreamSynchronize(st));
+        float ms0 = 0.f, ms1 = 0.f;
+        HIPCHECK(hipEventElapsedTime(&ms0, e0.e[0], e0.e[1]));
+        HIPCHECK(hipEventElapsedTime(&ms1, e1.e[0], e1.e[1]));
+        out.device_ms += (double)ms0 + (double)ms1;
+        out.nnz += total;
+        emit(q, RowBatch{nreq, hlen, hrhs, hc.data(), hv.data()});
+    }
+    return out;
+}
+
 // One round of Gomory cuts (solver.rs:440-460 per cut), ALL taken from the basis the call finds: RG_BATCH rows of B^-1 per block,
 // one pass over A per block, the cuts emitted as sparse rows on the device (cuts.inc).  The host reads back the row lengths and the
 // sparse rows (O(nnz of the cuts)); no dense tableau row crosses.
@@ -3101,87 +3183,27 @@ void Engine::add_gomory_cuts(const std::vector<int>& vars, CutInfo& info) {
     ensure_beta();  // (before the edge norms are fed)
     pull_ctl();     // (k_ and the count of pending terms as the device holds them)
     sync_view();
-    const DevView& dv = hview;
-    const Geom g = geom();
     constexpr int R = RG_BATCH;
     const int m = m_, N = N_;
-    const size_t nbat = (vars.size() + R - 1) / R;
-    std::vector<int> hreq(nbat * R, -1);
-    for (size_t t = 0; t < pos.size(); ++t) hreq[t] = pos[t];
-    const int nseg = cut_segments(N);
-    const size_t ncnt = (size_t)R * nseg;
-    DevBuf<double> blk, fd, rhs, oval, unit, tau;
-    DevBuf<double2> rv;
-    DevBuf<int> req, cnt, off, len, ocol;
-    blk.ensure((size_t)m * R + R, 0, st); fd.ensure((size_t)N * R + R, 0, st); rhs.ensure(R, 0, st); len.ensure(R, 0, st);
-    cnt.ensure(ncnt + 8, 0, st); off.ensure(ncnt + 8, 0, st);
-    d_scan_tmp.ensure(ncnt / 4096 + 8, 0, st);
-    req.upload(hreq, st);
-    if (fac_on_) {
-        unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
-        HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
-        HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
-    }
-    RangingBufs b{};
-    b.blk = blk.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
-    b.N = N; b.nv = num_vars; b.k = fac_on_ ? 0 : k_; b.fac = fac_on_ ? 1 : 0;
-    struct Events {  // (destroyed on every way out, a throwing HIPCHECK included)
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Events() {
-            for (auto& x : e)
-                if (x) (void)hipEventDestroy(x);
-        }
-        hipEvent_t& operator[](int i) { return e[i]; }
-    } e;
-    for (auto& x : e.e) HIPCHECK(hipEventCreate(&x));
     std::vector<Constraint> cuts(vars.size());
-    double ms_total = 0.0, cut_nnz = 0.0;
-    for (size_t q = 0; q < nbat; ++q) {
-        const int nreq = (int)std::min<size_t>(R, vars.size() - q * R);
-        b.req = req.p + q * R;
-        HIPCHECK(hipEventRecord(e[0], st));
-        launch_cut_generate(dv, g, b, nreq, hreq.data() + q * R, fd.p, cnt.p, off.p, d_scan_tmp.p, len.p, rhs.p, st);
-        HIPCHECK(hipEventRecord(e[1], st));
-        HIPCHECK(hipGetLastError());
-        int hlen[R];
-        double hrhs[R];
-        HIPCHECK(hipMemcpyAsync(hlen, len.p, sizeof(hlen), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(hrhs, rhs.p, sizeof(hrhs), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        size_t total = 0;
-        for (int r = 0; r < R; ++r) total += (size_t)hlen[r];
-        ocol.ensure(total + 8, 0, st); oval.ensure(total + 8, 0, st);
-        HIPCHECK(hipEventRecord(e[2], st));
-        launch_cut_fill(dv, fd.p, N, off.p, ocol.p, oval.p, enable_pse, st);
-        HIPCHECK(hipEventRecord(e[3], st));
-        HIPCHECK(hipGetLastError());
-        std::vector<int> hc(total);
-        std::vector<double> hv(total);
-        if (total) {
-            HIPCHECK(hipMemcpyAsync(hc.data(), ocol.p, total * sizeof(int), hipMemcpyDeviceToHost, st));
-            HIPCHECK(hipMemcpyAsync(hv.data(), oval.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
-        }
-        HIPCHECK(hipStreamSynchronize(st));
-        float ms0 = 0.f, ms1 = 0.f;
-        HIPCHECK(hipEventElapsedTime(&ms0, e[0], e[1]));
-        HIPCHECK(hipEventElapsedTime(&ms1, e[2], e[3]));
-        ms_total += (double)ms0 + (double)ms1;
+    const RowBatches rb = sparse_row_batches(pos, true, [&](size_t q, const RowBatch& bt) {
         size_t at = 0;
-        for (int r = 0; r < nreq; ++r) {  // rows are request-major, each sorted by variable
+        for (int r = 0; r < bt.nreq; ++r) {  // rows are request-major, each sorted by variable
             Constraint& c = cuts[q * R + r];
             c.op = 1;
-            c.rhs = hrhs[r];
-            c.idx.assign(hc.begin() + at, hc.begin() + at + hlen[r]);
-            c.val.assign(hv.begin() + at, hv.begin() + at + hlen[r]);
-            at += (size_t)hlen[r];
+            c.rhs = bt.rhs[r];
+            c.idx.assign(bt.col + at, bt.col + at + bt.len[r]);
+            c.val.assign(bt.val + at, bt.val + at + bt.len[r]);
+            at += (size_t)bt.len[r];
         }
-        cut_nnz += (double)total;
-    }
+    });
+    const size_t nbat = rb.nbat, ncnt = rb.ncnt;
+    const double ms_total = rb.device_ms, cut_nnz = (double)rb.nnz;
     // algorithmic bytes of the generation, per batch: the block (cleared, then written), one pass over A (12 bytes per entry) with
     // a gather of R doubles per entry, the dense block of f (written once, read by the count and by the fill), the per-variable
     // flags, the counts and offsets; per request the stored rows the block is made of; and the emitted rows (12 bytes per term)
     const double nz = (double)h_rcol.size();
-    const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
+    const int J = fac_on_ || hview.lrJ ? h_ctl->nlow : 0;
     info.batches = nbat;
     info.bytes = (double)nbat * (16.0 * (double)m * R + nz * (12.0 + 8.0 * R) + 24.0 * (double)N * R + 4.0 * N + 12.0 * (double)ncnt)
                  + (double)vars.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * cut_nnz;
@@ -3958,5 +3980,226 @@ void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du
         lo[t] = a == 0.0 ? 0.0 : a;
         hi[t] = c == 0.0 ? 0.0 : c;
     }
+}
+
+// ------------------------------------------------------------------ reading the tableau (tableau.inc)
+// Nothing here writes solver state: the kernels write private buffers, the pending rank-1 terms are applied, not folded, the compact
+// factor is not re-peeled; Ctl, d, rv and the work vectors are untouched.
+// user column -> variable of [A | I]
+int Engine::tab_internal_col(uint64_t col, const char* what) const {
+    if (col < (uint64_t)num_vars) return (int)col;
+    const uint64_t c = col - (uint64_t)num_vars;
+    if (c >= h_cons_row.size()) throw MlpError(-1, std::string(what) + ": column out of range");
+    if (h_cons_row[c] < 0) throw MlpError(-1, std::string(what) + ": the constraint has no terms, hence no row and no slack column");
+    return num_vars + h_cons_row[c];
+}
+void Engine::basis_head(std::vector<uint64_t>& out) {
+    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
+    pull_ctl();
+    std::vector<uint64_t> cons_of_row((size_t)m_, 0);
+    for (size_t c = 0; c < h_cons_row.size(); ++c)
+        if (h_cons_row[c] >= 0) cons_of_row[h_cons_row[c]] = c;
+    out.resize((size_t)m_);
+    for (int p = 0; p < m_; ++p) {
+        const int v = h_basic_vars[p];
+        out[p] = v < num_vars ? (uint64_t)v : (uint64_t)num_vars + cons_of_row[v - num_vars];
+    }
+}
+void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, double* out, TableauInfo& info) {
+    constexpr int R = RG_BATCH;
+    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    const DevView& dv = hview;
+    const Geom g = geom();
+    const int m = m_, k = fac_on_ ? 0 : k_;
+    const size_t ncons = h_cons_row.size();
+    const bool by_cons_out = op == 0 || op == 4;  // result by row -> by constraint
+    const size_t out_stride = by_cons_out ? ncons : (size_t)m, in_stride = op == 3 ? ncons : (size_t)m;
+    std::vector<size_t> solve;  // requests that need the device
+    for (size_t t = 0; t < req.size(); ++t)
+        if (req[t] >= 0 || op >= 3) solve.push_back(t);
+    info.solves = solve.size();
+    if (solve.empty() || m == 0) return;
+    const size_t nbat = (solve.size() + R - 1) / R;
+    std::vector<int> hreq(nbat * R, -1);
+    if (op < 3)
+        for (size_t q = 0; q < solve.size(); ++q) hreq[q] = req[solve[q]];
+    DevBuf<double> X, Y, XK, YK, part, lrh, unit, tau;
+    DevBuf<double2> rv;
+    DevBuf<int> dreq;
+    const size_t blk = (size_t)m * R + R;
+    Y.ensure(blk, 0, st);
+    if (op != 0) X.ensure(blk, 0, st);
+    if (op < 3) dreq.upload(hreq, st);
+    if (fac_on_) {
+        unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
+        HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
+        HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
+    } else if (k > 0 && op != 0) {
+        XK.ensure((size_t)k * R + R, 0, st); YK.ensure((size_t)k * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
+        if (op == 4) part.ensure((size_t)tab_wt_stripes(k) * k * R + R, 0, st);
+    }
+    TabBufs b{};
+    b.X = X.p; b.Y = Y.p; b.XK = XK.p; b.YK = YK.p; b.part = part.p; b.lrh = lrh.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
+    b.k = k; b.fac = fac_on_ ? 1 : 0;
+    RangingBufs rb{};  // op 0: the block of rows IS the result
+    rb.blk = Y.p; rb.unit = unit.p; rb.tau = tau.p; rb.rv = rv.p;
+    rb.N = N_; rb.nv = num_vars; rb.k = k; rb.fac = b.fac;
+    std::vector<int> row_of_cons(h_cons_row);
+    std::vector<double> hX, hY(blk);
+    if (op >= 3) hX.resize(blk);
+    TabEvents ev;
+    double ms_total = 0.0;
+    for (size_t q = 0; q < nbat; ++q) {
+        const int nreq = (int)std::min<size_t>(R, solve.size() - q * R);
+        if (op >= 3) {  // the right-hand sides of the batch, interleaved
+            std::fill(hX.begin(), hX.end(), 0.0);
+            for (int r = 0; r < nreq; ++r) {
+                const double* src = rhs + solve[q * R + r] * in_stride;
+                if (op == 3) {
+                    for (size_t c = 0; c < ncons; ++c)
+                        if (row_of_cons[c] >= 0) hX[(size_t)row_of_cons[c] * R + r] = src[c];
+                } else {
+                    for (int p = 0; p < m; ++p) hX[(size_t)p * R + r] = src[p];
+                }
+            }
+            HIPCHECK(hipMemcpyAsync(X.p, hX.data(), sizeof(double) * (size_t)m * R, hipMemcpyHostToDevice, st));
+        }
+        HIPCHECK(hipEventRecord(ev.e[0], st));
+        if (op == 0) {
+            rb.req = dreq.p + q * R;
+            launch_ranging_block(dv, g, rb, 0, nreq, hreq.data() + q * R, st);
+        } else {
+            if (op < 3) launch_tab_rhs(dv, b, dreq.p + q * R, nreq, op, st);
+            launch_tab_solve(dv, g, b, op == 4 ? 1 : 0, nreq, st);
+        }
+        HIPCHECK(hipEventRecord(ev.e[1], st));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(hY.data(), Y.p, sizeof(double) * (size_t)m * R, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        float ms = 0.0f;
+        HIPCHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+        ms_total += (double)ms;
+        for (int r = 0; r < nreq; ++r) {
+            double* dst = out + solve[q * R + r] * out_stride;
+            if (by_cons_out) {
+                for (size_t c = 0; c < ncons; ++c) dst[c] = row_of_cons[c] >= 0 ? hY[(size_t)row_of_cons[c] * R + r] : 0.0;
+            } else {
+                for (int p = 0; p < m; ++p) dst[p] = hY[(size_t)p * R + r];
+            }
+        }
+    }
+    // algorithmic bytes per batch: the blocks X and Y (cleared / written, read), one read of W0 (8 k^2) with its pending terms, the
+    // gathered nucleus parts, one pass over the basis columns of A for the F product (12 bytes per entry + a gather of R doubles);
+    // rows of B^-1: as the ranging block; compact factor: counted as its pending terms per solve, like the ranging
+    const double nz = (double)h_rcol.size();
+    const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
+    if (op == 0)
+        info.bytes = (double)nbat * 16.0 * (double)m * R + (double)solve.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k);
+    else if (fac_on_)
+        info.bytes = (double)nbat * 32.0 * (double)m * R + (double)solve.size() * (24.0 + 16.0 * J) * m;
+    else
+        info.bytes = (double)nbat * (32.0 * (double)m * R + 8.0 * (double)k * k + 16.0 * J * k + 32.0 * (double)k * R
+                                     + (op == 4 ? 16.0 * (double)tab_wt_stripes(k) * k * R : 0.0) + nz * (12.0 + 8.0 * R));
+    info.batches = nbat;
+    info.device_ms = ms_total;
+}
+void Engine::binv_rows(const std::vector<uint64_t>& cols, double* out, TableauInfo& info) {
+    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
+    pull_ctl();
+    std::vector<int> req(cols.size());
+    for (size_t t = 0; t < cols.size(); ++t) {
+        const int loc = h_var_loc[tab_internal_col(cols[t], "binv_rows")];
+        if (loc < 0) throw MlpError(-1, "binv_rows: the column is not basic");
+        req[t] = loc;
+    }
+    info = TableauInfo();
+    info.requests = cols.size();
+    tab_dense(0, req, nullptr, out, info);
+}
+void Engine::binv_cols(const std::vector<uint64_t>& cons, double* out, TableauInfo& info) {
+    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
+    std::vector<int> req(cons.size());
+    for (size_t t = 0; t < cons.size(); ++t) {
+        if (cons[t] >= h_cons_row.size()) throw MlpError(-1, "binv_cols: constraint out of range");
+        if (h_cons_row[cons[t]] < 0) throw MlpError(-1, "binv_cols: the constraint has no terms, hence no row");
+        req[t] = h_cons_row[cons[t]];
+    }
+    info = TableauInfo();
+    info.requests = cons.size();
+    tab_dense(1, req, nullptr, out, info);
+}
+void Engine::tableau_cols(const std::vector<uint64_t>& cols, double* out, TableauInfo& info) {
+    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
+    pull_ctl();
+    std::vector<int> req(cols.size());
+    std::vector<std::pair<size_t, int>> basic;
+    for (size_t t = 0; t < cols.size(); ++t) {
+        const int var = tab_internal_col(cols[t], "tableau_cols");
+        const int loc = h_var_loc[var];
+        req[t] = loc >= 0 ? -1 : var;
+        if (loc >= 0) basic.emplace_back(t, loc);
+    }
+    info = TableauInfo();
+    info.requests = cols.size();
+    tab_dense(2, req, nullptr, out, info);
+    for (const auto& bp : basic) {  // a basic column: the exact unit vector of its position
+        double* dst = out + bp.first * (size_t)m_;
+        std::fill(dst, dst + m_, 0.0);
+        dst[bp.second] = 1.0;
+    }
+}
+void Engine::basis_solve(bool transpose, const double* rhs, size_t n, double* out, TableauInfo& info) {
+    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
+    info = TableauInfo();
+    info.requests = n;
+    if (transpose && m_ == 0) std::fill(out, out + n * h_cons_row.size(), 0.0);
+    tab_dense(transpose ? 4 : 3, std::vector<int>(n, 0), rhs, out, info);
+}
+void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_t>& indptr, std::vector<uint32_t>& indices,
+                          std::vector<double>& values, TableauInfo& info) {
+    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
+    pull_ctl();
+    std::vector<int> pos(cols.size());
+    for (size_t t = 0; t < cols.size(); ++t) {
+        const int loc = h_var_loc[tab_internal_col(cols[t], "tableau_rows")];
+        if (loc < 0) throw MlpError(-1, "tableau_rows: the column is not basic");
+        pos[t] = loc;
+    }
+    info = TableauInfo();
+    info.requests = info.solves = cols.size();
+    indptr.assign(cols.size() + 1, 0);
+    indices.clear();
+    values.clear();
+    if (cols.empty()) return;
+    sync_view();
+    constexpr int R = RG_BATCH;
+    const int m = m_, N = N_;
+    std::vector<uint32_t> col_of_var((size_t)N);  // variable of [A | I] -> user column (monotone: rows are numbered in constraint order)
+    for (int j = 0; j < num_vars; ++j) col_of_var[j] = (uint32_t)j;
+    for (size_t c = 0; c < h_cons_row.size(); ++c)
+        if (h_cons_row[c] >= 0) col_of_var[(size_t)num_vars + h_cons_row[c]] = (uint32_t)(num_vars + c);
+    const RowBatches rb = sparse_row_batches(pos, false, [&](size_t q, const RowBatch& bt) {
+        size_t at = 0;
+        for (int r = 0; r < bt.nreq; ++r) {  // rows are request-major, each sorted by variable
+            for (int e = 0; e < bt.len[r]; ++e) {
+                indices.push_back(col_of_var[bt.col[at + e]]);
+                values.push_back(bt.val[at + e]);
+            }
+            at += (size_t)bt.len[r];
+            indptr[q * R + r + 1] = indices.size();
+        }
+    });
+    const size_t nbat = rb.nbat, ncnt = rb.ncnt;
+    const double ms_total = rb.device_ms;
+    // algorithmic bytes: as the cut generation (the block, one pass over A with a gather of R doubles per entry, the dense block of
+    // alpha written once and read by the count and by the fill, counts and offsets, the emitted rows)
+    const double nz = (double)h_rcol.size();
+    const int J = fac_on_ || hview.lrJ ? h_ctl->nlow : 0;
+    info.batches = nbat;
+    info.nnz = indices.size();
+    info.bytes = (double)nbat * (16.0 * (double)m * R + nz * (12.0 + 8.0 * R) + 24.0 * (double)N * R + 4.0 * N + 12.0 * (double)ncnt)
+                 + (double)cols.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * (double)indices.size();
+    info.device_ms = ms_total;
 }
 }  // namespace mlp

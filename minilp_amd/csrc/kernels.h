@@ -578,6 +578,31 @@ int cut_segments(int N);
 void launch_cut_generate(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* fd, int* cnt,
                          int* off, int* sums, int* len, double* rhs, hipStream_t st);
 void launch_cut_fill(const DevView& dv, const double* fd, int N, const int* off, int* ocol, double* oval, bool gamma, hipStream_t st);
+// reading the tableau of the current basis (tableau.inc): batches of RG_BATCH rows of B^-1 A as sparse rows, and batches of RG_BATCH solves
+// with dense right-hand sides.  X, Y: [m][RG_BATCH], entry i of all right-hand sides in one 128-byte line.  Reads the solver state; writes
+// only these buffers.
+struct TabBufs {
+    double* X;      // right-hand sides: FTRAN by row, BTRAN by position
+    double* Y;      // results: FTRAN by position, BTRAN by row
+    double* XK;     // [k][RG_BATCH]: FTRAN X_K by column slot; BTRAN T_K = X_K - F^T Y_S by row slot
+    double* YK;     // [k][RG_BATCH]: FTRAN W X_K by row slot
+    double* part;   // BTRAN: tab_wt_stripes(k) x k x RG_BATCH partial column sums of W0^T T_K
+    double* lrh;    // LR_MAX x RG_BATCH: V_j . X_K (FTRAN) / U_j . T_K (BTRAN) of the pending terms
+    double* unit;   // m: compact factor: right-hand side of one solve
+    double* tau;    // m: compact factor: private result of the FTRAN
+    double2* rv;    // m: compact factor: private rv of the BTRAN
+    int k, fac;     // nucleus size (explicit inverse), compact factor active
+};
+int tab_wt_stripes(int k);
+// phase 1 of a batch of tableau rows: the block of rows of B^-1 (b as for launch_cut_generate), the dense block ad[N][RG_BATCH] of alpha by
+// variable (basic variables 0, a requested variable itself exactly 1), the scanned offsets and the row lengths (rhs: scratch of the
+// shared head kernel); phase 2 is launch_cut_fill on ad (no edge norms)
+void launch_tab_rows(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* ad, int* cnt, int* off,
+                     int* sums, int* len, double* rhs, hipStream_t st);
+// X of a batch formed on the device (req: RG_BATCH ints on the device, -1 at empty places): mode 1 unit vectors of rows, 2 columns of [A | I]
+void launch_tab_rhs(const DevView& dv, const TabBufs& b, const int* req, int nreq, int mode, hipStream_t st);
+// one batch of solves: Y = B^-1 X, or transposed Y = B^-T X
+void launch_tab_solve(const DevView& dv, const Geom& g, const TabBufs& b, int transpose, int nreq, hipStream_t st);
 // blocked in-place Gauss-Jordan inversion of the nucleus held in dv.W (inverse.inc); *flag = 1: singular
 void launch_blocked_inverse(const DevView& dv, int k, double* rowbuf, int nrowbuf, int* piv, int* src, double* prow, double* ckey,
                             int* cidx, int* flag, hipStream_t st);
