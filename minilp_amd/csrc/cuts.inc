@@ -10,8 +10,8 @@
 //   segment in variable order, so every cut comes out sorted by variable with no atomics, no ballots and no LDS, bit-identically
 //   from run to run and whatever else the batch holds (alpha_j[r] is summed in storage order, then by the xor tree of the lane
 //   group: its value depends on request r alone).  Side-effect free like ranging: only the private buffers are written.
-// Batched row append: one re-layout of the CSC for R new rows (they are the last R rows, so every column gains its new entries at
-//   its end, in row order): per-column counts from the R sorted rows, a scan, one copy kernel.
+// Row append (R = 1 is Solution::add_constraint): one re-layout of the CSC for R new rows (they are the last R rows, so every column
+//   gains its new entries at its end, in row order): per-column counts from the R sorted rows, a scan, one copy kernel.
 
 constexpr int CUT_SEG = 16;  // variables per (segment, request) thread of the count / fill passes
 
@@ -128,7 +128,7 @@ void launch_cut_fill(const DevView& dv, const double* fd, int N, const int* off,
     if (gamma) hipLaunchKernelGGL(k_cut_gamma<R>, dim3(blocks_for(N)), dim3(BLK), 0, st, dv, fd, N);
 }
 
-// ------------------------------------------------------------------- batched row append
+// ------------------------------------------------------------------- row append (R >= 1 rows)
 // The R new rows are the tail of the CSR (rptr[0..R] are the row pointers of the new rows, each row = its sorted terms on old
 // columns followed by its slack).  cnt[j] = number of new rows that hold old column j (binary search per row); cnt[n_old] = 0.
 __device__ __forceinline__ int csc_find(const int* __restrict__ rcol, int b, int e, int j) {  // index of j in the sorted [b, e), or -1

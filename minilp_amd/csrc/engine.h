@@ -156,7 +156,7 @@ public:
     // Solver::try_new (solver.rs:108-369): throws LpFail{1} for min > max / contradictory empty rows
     void try_new(const ProblemData& pd);
     void initial_solve();                                                   // solver.rs:470-485
-    void add_constraint(Constraint c);                                      // solver.rs:549-634 (indices < num_total_vars)
+    void add_constraint(Constraint c);                     // solver.rs:549-634 (indices < num_total_vars): add_constraints of one row
     void fix_var(int var, double val);                                      // solver.rs:378-415
     bool unfix_var(int var);                                                // solver.rs:418-438
     void add_gomory_cut(int var);                                           // solver.rs:440-460
@@ -254,7 +254,7 @@ private:
     std::vector<double> h_rval;
     // Host view of the columns: only what the host logic needs — the length of every column and, for singleton
     // columns, their single entry (classification of the basis in rebuild_inverse).  The CSC itself lives on the
-    // device only (built there from the uploaded CSR-side arrays at try_new, re-laid out there by add_constraint).
+    // device only (built there from the uploaded CSR-side arrays at try_new, re-laid out there by add_constraints).
     std::vector<int> h_cptr, h_crow;       // initial build only (try_new); dropped after the first device-side append
     std::vector<double> h_cval;
     int max_col_nnz_ = 0, max_row_nnz_ = 0;   // longest column / row of A (in-kernel stage heads need them to fit an LDS list)
@@ -517,10 +517,9 @@ private:
     void pull_maps();
     void push_maps();
     int col_nnz(int var) const { return h_colnnz[var]; }
-    DevBuf<int> d_cptr_alt, d_crow_alt, d_row_idx, d_scan_tmp;  // second CSC buffer set of the device-side append, staging
-    DevBuf<double> d_cval_alt, d_row_val;
-    void append_row_on_device(const Constraint& c, int slack, int row);
-    void append_rows_on_device(const std::vector<Constraint>& cs, size_t old_nnz);  // R rows, one CSC re-layout
+    DevBuf<int> d_cptr_alt, d_crow_alt, d_col_cnt, d_scan_tmp;  // second CSC buffer set of the device-side append, its per-column counts
+    DevBuf<double> d_cval_alt;
+    void append_rows_on_device(const std::vector<Constraint>& cs, size_t old_nnz);  // R >= 1 rows, one CSC re-layout
 
     void record_iteration(int phase, bool with_events);  // enqueue the kernel sequence of ONE iteration
     void launch_stage(int phase, int stage, bool with_events);

@@ -2755,158 +2755,21 @@ void Engine::add_gomory_cut(int var) {  // solver.rs:440-460
     add_constraint(std::move(c));
 }
 
-// Device-side row append (solver.rs:597-613 rebuilds both orientations on the host).  The host has
-// already appended the row to its CSR mirror and the variable arrays; here the same row goes to the device copies
-// without a pass over the matrix on the host and without re-uploading it: O(row) host work, one O(nnz) device copy.
-void Engine::append_row_on_device(const Constraint& c, int slack, int row) {
-    const size_t kn = c.idx.size();
-    const size_t old_nnz = h_rcol.size() - kn - 1;  // the host mirror already holds the new row (+ slack)
-    // --- CSR: append in place (capacity-doubling buffers keep their contents)
-    d_rcol.ensure(old_nnz + kn + 1, old_nnz, st);
-    d_rval.ensure(old_nnz + kn + 1, old_nnz, st);
-    d_rptr.ensure((size_t)m_ + 2, (size_t)m_ + 1, st);
-    HIPCHECK(hipMemcpyAsync(d_rcol.p + old_nnz, h_rcol.data() + old_nnz, (kn + 1) * sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_rval.p + old_nnz, h_rval.data() + old_nnz, (kn + 1) * sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_rptr.p + m_ + 1, &h_rptr[m_ + 1], sizeof(int), hipMemcpyHostToDevice, st));
-    // --- per-variable arrays: one new element (the slack)
-    d_lo.ensure((size_t)N_ + 1, (size_t)N_, st); d_hi.ensure((size_t)N_ + 1, (size_t)N_, st); d_obj.ensure((size_t)N_ + 1, (size_t)N_, st);
-    HIPCHECK(hipMemcpyAsync(d_lo.p + N_, &h_lo[N_], sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_hi.p + N_, &h_hi[N_], sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_obj.p + N_, &h_obj[N_], sizeof(double), hipMemcpyHostToDevice, st));
-    // --- CSC: one copy kernel into the second buffer set, then swap
-    d_row_idx.ensure(kn + 1, 0, st); d_row_val.ensure(kn + 1, 0, st);
-    if (kn) {
-        HIPCHECK(hipMemcpyAsync(d_row_idx.p, c.idx.data(), kn * sizeof(int), hipMemcpyHostToDevice, st));
-        HIPCHECK(hipMemcpyAsync(d_row_val.p, c.val.data(), kn * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    d_cptr_alt.ensure((size_t)N_ + 2, 0, st);
-    d_crow_alt.ensure(old_nnz + kn + 1, 0, st);
-    d_cval_alt.ensure(old_nnz + kn + 1, 0, st);
-    launch_csc_append_row(d_cptr.p, d_crow.p, d_cval.p, N_, row, d_row_idx.p, d_row_val.p, (int)kn, d_cptr_alt.p, d_crow_alt.p,
-                          d_cval_alt.p, st);
-    HIPCHECK(hipStreamSynchronize(st));  // c.idx / c.val were staged from pageable memory; the old buffers become the spare set
-    d_cptr.swap(d_cptr_alt); d_crow.swap(d_crow_alt); d_cval.swap(d_cval_alt);
-    // --- host column summaries
-    for (size_t p = 0; p < kn; ++p) {
-        const int var = c.idx[p];
-        h_colnnz[var] += 1;
-        if (h_colnnz[var] == 1) {  // a column that was empty so far (tsp.rs:226-235 has such variables) becomes a singleton
-            h_single_row[var] = row;
-            h_single_val[var] = c.val[p];
-        }
-        max_col_nnz_ = std::max(max_col_nnz_, h_colnnz[var]);
-    }
-    max_row_nnz_ = std::max(max_row_nnz_, (int)kn + 1);
-    for (size_t p = 0; p < kn; ++p) amax_ = std::max(amax_, std::fabs(c.val[p]));
-    amax_ = std::max(amax_, 1.0);  // (the slack entry)
-    h_colnnz.push_back(1);
-    h_single_row.push_back(row);
-    h_single_val.push_back(1.0);
-    if (!h_cptr.empty()) {  // the host CSC of the initial build is stale from here on
-        std::vector<int>().swap(h_cptr); std::vector<int>().swap(h_crow); std::vector<double>().swap(h_cval);
-    }
-    colblk_dirty = true;
-    banded_dirty = true;
-    fpk_valid_ = false;  // (the packed copy of the nucleus columns is a copy of matrix entries)
-    view_dirty = true;
-}
-
-// solver.rs:549-634.  The new slack is a singleton basic column on the new row, so the nucleus
-// inverse is unchanged unless the new row touches a basic singleton column (then: rebuild).
+// solver.rs:549-634.  One row is a round of one: add_constraints below is the only row-append path.  The counters of the round are
+// dropped here (mlp_cut_info reports the batched entry points only).
 void Engine::add_constraint(Constraint c) {
-    cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    double t0 = now_s();
     if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_constraint: model not solved (solver.rs:555-556)");
-    // Round 5: the compact factor SURVIVES a new row.  The new slack is a column singleton on the new row — the first level of the peel,
-    // whatever else the row holds — so the factor of the extended basis is one more refactorisation (a re-peel of the current basis,
-    // ~1 ms: BasisSolver::reset is what the reference does here too, solver.rs:612-613), not a return to the explicit inverse (which
-    // the models this representation exists for cannot even allocate).  The pending rank-1 terms are by position / by row of the OLD
-    // size: the re-peel starts from the current basis and drops them.
-    const bool on_factor = fac_on_;
-    ensure_beta();
-    if (c.idx.empty()) {
-        bool taut = c.op == 0 ? (0.0 == c.rhs) : c.op == 1 ? (0.0 <= c.rhs) : (0.0 >= c.rhs);
-        if (taut) {
-            h_cons_row.push_back(-1);  // (a constraint without terms gets no row; its dual value is 0)
-            return;
-        }
-        throw LpFail{1};
-    }
-    fetch_values();
-    const int slack = N_, row = m_;
-    h_cons_row.push_back(row);
-    double smin = c.op == 1 ? 0.0 : c.op == 2 ? -INF : 0.0;
-    double smax = c.op == 1 ? INF : 0.0;
-    double lhs = 0.0;  // solver.rs:587-595
-    bool touches_basic_singleton = false;
-    for (size_t p = 0; p < c.idx.size(); ++p) {
-        int var = c.idx[p];
-        int loc = h_var_loc[var];
-        lhs += (loc >= 0 ? h_xB[loc] : h_xN[-1 - loc]) * c.val[p];
-        if (loc >= 0 && col_nnz(var) == 1) touches_basic_singleton = true;  // that column stops being a singleton
-    }
-    double xnew = c.rhs - lhs;
-    // matrix: append the CSR row (+ slack), rebuild the CSC (O(nnz), like solver.rs:597-610)
-    for (size_t p = 0; p < c.idx.size(); ++p) {
-        h_rcol.push_back(c.idx[p]);
-        h_rval.push_back(c.val[p]);
-    }
-    h_rcol.push_back(slack);
-    h_rval.push_back(1.0);
-    h_rptr.push_back((int)h_rcol.size());
-    h_rhs.push_back(c.rhs);
-    h_obj.push_back(0.0);
-    h_lo.push_back(smin);
-    h_hi.push_back(smax);
-    HIPCHECK(hipStreamSynchronize(st));
-    alloc_row_buffers(m_ + 1);
-    append_row_on_device(c, slack, row);  // CSR row appended, CSC re-laid out, derived copies marked for a device rebuild
-    m_ += 1;
-    N_ += 1;
-    ensure_red();
-    for (size_t p = 0; p < c.idx.size(); ++p)
-        if (h_var_loc[c.idx[p]] < 0) nnz_nonbasic += 1;
-    // new basic position `row` holding the slack (singleton on the new row)
-    h_basic_vars.push_back(slack);
-    h_var_loc.push_back(row);
-    int neg1 = -1;
-    double one = 1.0, beta0 = 1.0;
-    HIPCHECK(hipMemcpyAsync(d_basic_vars.p + row, &slack, sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_var_loc.p + slack, &row, sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_xB.p + row, &xnew, sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_loB.p + row, &smin, sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_hiB.p + row, &smax, sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_beta.p + row, &beta0, sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_kslot_of_pos.p + row, &neg1, sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_srow_of_pos.p + row, &row, sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_sdiag_of_pos.p + row, &one, sizeof(double), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_kslot_of_row.p + row, &neg1, sizeof(int), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipMemcpyAsync(d_pos_of_srow.p + row, &row, sizeof(int), hipMemcpyHostToDevice, st));
-    const RowInfo ri_new{1.0, row, -1};
-    HIPCHECK(hipMemcpyAsync(d_rowinfo.p + row, &ri_new, sizeof(RowInfo), hipMemcpyHostToDevice, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    values_dirty = true;
-    view_dirty = true;
-    sync_view();
-    launch_init_nb_rng(hview, geom(), st);
-    if (on_factor) {
-        if (!fac_refactor()) fac_leave();  // (the extended basis no longer peels within the bump limit: explicit inverse, as before)
-    } else if (touches_basic_singleton) rebuild_inverse();  // a singleton column just gained an entry
-
-    if (enable_pse || enable_dse) {  // solver.rs:615-630: last tableau row feeds the edge norms
-        calc_row_coeffs(m_ - 1, enable_pse);
-        if (enable_pse) launch_sq_norms_add_row(hview, geom(), st);
-        if (enable_dse) launch_copy_rho_sq_to_beta(hview, row, st);
-    }
-    primal_feasible = false;
-    budget_exhausted = false;
-    restore_feasibility();
-    stats.solve_wall_s += now_s() - t0;
+    std::vector<Constraint> one;
+    one.push_back(std::move(c));
+    CutInfo unused;
+    add_constraints(std::move(one), unused, false);
 }
 
-// ------------------------------------------------------------------ a round of cuts in one call (cuts.inc)
-// R rows on the device at once: the host mirror already holds them (CSR tail, slack bounds); here the CSR tail and the slack
-// entries of the per-variable arrays go up with one copy each, and the CSC is re-laid out ONCE for the whole batch.
+// ------------------------------------------------------------------ appending rows: one row or a round of cuts (cuts.inc)
+// Device-side row append (solver.rs:597-613 rebuilds both orientations on the host).  The host mirror already holds the
+// R new rows (CSR tail, slack bounds); here the CSR tail and the slack entries of the per-variable arrays go up with one copy each,
+// and the CSC is re-laid out ONCE for the whole batch: O(rows) host work, one O(nnz) device copy, no pass over the matrix on the
+// host and no re-upload.
 void Engine::append_rows_on_device(const std::vector<Constraint>& cs, size_t old_nnz) {
     const size_t R = cs.size();
     const size_t add = h_rcol.size() - old_nnz;
@@ -2921,23 +2784,23 @@ void Engine::append_rows_on_device(const std::vector<Constraint>& cs, size_t old
     HIPCHECK(hipMemcpyAsync(d_hi.p + N_, &h_hi[N_], R * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHECK(hipMemcpyAsync(d_obj.p + N_, &h_obj[N_], R * sizeof(double), hipMemcpyHostToDevice, st));
     // --- CSC: per-column counts from the R sorted rows, their scan, one copy kernel into the second buffer set, then swap
-    d_row_idx.ensure((size_t)N_ + 2, 0, st);
+    d_col_cnt.ensure((size_t)N_ + 2, 0, st);
     d_scan_tmp.ensure((size_t)(N_ + 1) / 4096 + 8, 0, st);
     d_cptr_alt.ensure((size_t)N_ + R + 1, 0, st);
     d_crow_alt.ensure(old_nnz + add, 0, st);
     d_cval_alt.ensure(old_nnz + add, 0, st);
-    launch_csc_append_rows(d_cptr.p, d_crow.p, d_cval.p, N_, m_, (int)R, d_rptr.p + m_, d_rcol.p, d_rval.p, d_row_idx.p, d_scan_tmp.p,
+    launch_csc_append_rows(d_cptr.p, d_crow.p, d_cval.p, N_, m_, (int)R, d_rptr.p + m_, d_rcol.p, d_rval.p, d_col_cnt.p, d_scan_tmp.p,
                            d_cptr_alt.p, d_crow_alt.p, d_cval_alt.p, st);
     HIPCHECK(hipStreamSynchronize(st));  // the old buffers become the spare set
     d_cptr.swap(d_cptr_alt); d_crow.swap(d_crow_alt); d_cval.swap(d_cval_alt);
-    // --- host column summaries, row by row as the single form leaves them
+    // --- host column summaries, row by row
     for (size_t i = 0; i < R; ++i) {
         const Constraint& c = cs[i];
         const int row = m_ + (int)i;
         for (size_t p = 0; p < c.idx.size(); ++p) {
             const int var = c.idx[p];
             h_colnnz[var] += 1;
-            if (h_colnnz[var] == 1) {
+            if (h_colnnz[var] == 1) {  // a column that was empty so far (tsp.rs:226-235 has such variables) becomes a singleton
                 h_single_row[var] = row;
                 h_single_val[var] = c.val[p];
             }
@@ -2955,14 +2818,21 @@ void Engine::append_rows_on_device(const std::vector<Constraint>& cs, size_t old
     }
     colblk_dirty = true;
     banded_dirty = true;
-    fpk_valid_ = false;
+    fpk_valid_ = false;  // (the packed copy of the nucleus columns is a copy of matrix entries)
     view_dirty = true;
 }
 
+// The new slacks are singleton basic columns on the new rows, so the nucleus inverse is unchanged unless a new row touches a basic
+// singleton column (then: rebuild).
 void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gomory) {
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
     const double t0 = now_s();
     if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_constraints: model not solved (solver.rs:555-556)");
+    // The compact factor SURVIVES new rows.  A new slack is a column singleton on its new row — the first level of the peel, whatever
+    // else the row holds — so the factor of the extended basis is one more refactorisation (a re-peel of the current basis, ~1 ms:
+    // BasisSolver::reset is what the reference does here too, solver.rs:612-613), not a return to the explicit inverse (which the
+    // models this representation exists for cannot even allocate).  The pending rank-1 terms are by position / by row of the OLD
+    // size: the re-peel starts from the current basis and drops them.
     const bool on_factor = fac_on_;
     ensure_beta();
     // constraints without terms get no row (their dual value is 0); one that is not a tautology makes the model infeasible
@@ -3063,7 +2933,7 @@ void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gom
     }
     // Edge norms.  The tableau row of new row i in the extended basis does not depend on the other new rows
     // (B_ext^-1 = [[B^-1, 0], [-a_B^T B^-1, I]]).  A Gomory cut's row IS its coefficient row (beta = 1, set above; gamma was fed
-    // from the emitted block by launch_cut_fill); a general row takes the path of the single form.
+    // from the emitted block by launch_cut_fill); a general row feeds them from its tableau row (solver.rs:615-630).
     if (!gomory && (enable_pse || enable_dse)) {
         for (int i = 0; i < R; ++i) {
             calc_row_coeffs(row0 + i, enable_pse);
@@ -3673,6 +3543,11 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
     else if (w == "csr_indptr") tmp.assign(h_rptr.begin(), h_rptr.end());    // A with the slack identity, by row (the oracle's names)
     else if (w == "csr_indices") tmp.assign(h_rcol.begin(), h_rcol.end());
     else if (w == "csr_data") tmp = h_rval;
+    else if (w == "dev_csc_indptr") from_dev_i(d_cptr, (size_t)N_ + 1);      // the same matrix as the DEVICE holds it: by column ...
+    else if (w == "dev_csc_indices") from_dev_i(d_crow, h_rcol.size());
+    else if (w == "dev_csc_data") from_dev_d(d_cval.p, h_rcol.size());
+    else if (w == "dev_csr_indptr") from_dev_i(d_rptr, (size_t)m_ + 1);      // ... and by row
+    else if (w == "dev_csr_data") from_dev_d(d_rval.p, h_rcol.size());
     else if (w == "flags") tmp = {(double)primal_feasible, (double)dual_feasible, (double)enable_pse, (double)enable_dse};
     else if (w == "small_basis_launches") {  // iterations that ran BTRAN + pass + v tail + touch as one launch (k_small_basis)
         pull_ctl();

@@ -607,10 +607,8 @@ void launch_tab_solve(const DevView& dv, const Geom& g, const TabBufs& b, int tr
 void launch_blocked_inverse(const DevView& dv, int k, double* rowbuf, int nrowbuf, int* piv, int* src, double* prow, double* ckey,
                             int* cidx, int* flag, hipStream_t st);
 
-// device-side matrix maintenance (add_constraint without a host pass over the non-zeros; also the initial builds)
-void launch_csc_append_row(const int* optr, const int* orow, const double* oval, int n_old, int new_row, const int* ncols,
-                           const double* nvals, int kn, int* nptr, int* nrow, double* nval, hipStream_t st);
-// R rows at once: rptr[0..R] / rcol / rval are the new rows as the CSR holds them (sorted terms on old columns, then the slack);
+// device-side matrix maintenance (appending rows without a host pass over the non-zeros; also the initial builds)
+// R >= 1 rows at once: rptr[0..R] / rcol / rval are the new rows as the CSR holds them (sorted terms on old columns, then the slack);
 // cnt: n_old + 1 ints (per-column counts, then their scan), sums: the scan's scratch
 void launch_csc_append_rows(const int* optr, const int* orow, const double* oval, int n_old, int row0, int R, const int* rptr,
                             const int* rcol, const double* rval, int* cnt, int* sums, int* nptr, int* nrow, double* nval,

@@ -4252,55 +4252,14 @@ void launch_exact_beta(const DevView& dv, hipStream_t st) {
 }
 
 // ------------------------------------------------------------------- device-side matrix maintenance
-// Solution::add_constraint appends ONE row (solver.rs:597-613 rebuilds CSR and CSC on the host, O(nnz)).  Here the
-// matrix stays on the device: the CSR row is appended in place (capacity-doubling buffers), the CSC is re-laid out by
-// one copy kernel (a column's entries move by the number of touched columns before it, found by binary search in the
-// sorted new row; the new row index is the largest, so appending keeps every column's rows ascending), and the
-// derived copies (band-major copy of the banded sweep, row-block offsets of the blocked F push) are rebuilt by the
-// kernels below, which also serve the initial build.  No host pass over the non-zeros, no re-upload.
-template <int G>
-__global__ void __launch_bounds__(BLK) k_csc_append_row(const int* __restrict__ optr, const int* __restrict__ orow,
-                                                        const double* __restrict__ oval, int n_old, int new_row,
-                                                        const int* __restrict__ ncols, const double* __restrict__ nvals, int kn,
-                                                        int* __restrict__ nptr, int* __restrict__ nrow, double* __restrict__ nval) {
-    const int j = (blockIdx.x * BLK + threadIdx.x) / G;  // old column (variable)
-    const int gl = threadIdx.x & (G - 1);
-    if (j > n_old) return;
-    if (j == n_old) {  // the new slack column: one entry (new_row, +1), solver.rs:250
-        if (gl == 0) {
-            const int b = optr[n_old] + kn;
-            nptr[n_old] = b;
-            nptr[n_old + 1] = b + 1;
-            nrow[b] = new_row;
-            nval[b] = 1.0;
-        }
-        return;
-    }
-    int lo = 0, hi = kn;  // shift = number of touched columns < j
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (ncols[mid] < j) lo = mid + 1;
-        else hi = mid;
-    }
-    const int ob = optr[j], oe = optr[j + 1];
-    const int nb = ob + lo;
-    for (int e = ob + gl; e < oe; e += G) {
-        nrow[nb + (e - ob)] = orow[e];
-        nval[nb + (e - ob)] = oval[e];
-    }
-    if (gl == 0) {
-        nptr[j] = nb;
-        if (lo < kn && ncols[lo] == j) {
-            nrow[nb + (oe - ob)] = new_row;
-            nval[nb + (oe - ob)] = nvals[lo];
-        }
-    }
-}
-void launch_csc_append_row(const int* optr, const int* orow, const double* oval, int n_old, int new_row, const int* ncols,
-                           const double* nvals, int kn, int* nptr, int* nrow, double* nval, hipStream_t st) {
-    hipLaunchKernelGGL(k_csc_append_row<16>, dim3(blocks_for((long)(n_old + 1) * 16)), dim3(BLK), 0, st, optr, orow, oval, n_old,
-                       new_row, ncols, nvals, kn, nptr, nrow, nval);
-}
+// Solution::add_constraint(s) appends rows (solver.rs:597-613 rebuilds CSR and CSC on the host, O(nnz)).  Here the
+// matrix stays on the device: the CSR rows are appended in place (capacity-doubling buffers), the CSC is re-laid out by
+// one copy kernel for one row or many (k_csc_append_rows, cuts.inc: a column's entries move by the number of new entries
+// in the columns before it, the exclusive scan below of the per-column counts; the new row indices are the largest, so
+// appending keeps every column's rows ascending), and the derived copies (band-major copy of the banded sweep, row-block
+// offsets of the blocked F push) are rebuilt by the kernels below, which also serve the initial build.  No host pass
+// over the non-zeros, no re-upload.  (A single row had a kernel of its own here that found its shift by binary search
+// in the row: it is the R = 1 case of k_csc_append_rows now.)
 
 // exclusive scan of n ints (in place allowed), three phases: 4096-element block scans, scan of the block sums by
 // one block, add-back.  `sums` holds ceil(n / 4096) + 1 ints.
