@@ -684,6 +684,8 @@ class Solution:
         lib().mlp_solution_stats(self._h, C.byref(s))
         d = {n: getattr(s, n) for n, _ in MlpStats._fields_}
         d["kase"] = list(d["kase"])
+        rl = self.state("ratio_list")  # counters of the control block, not of mlp_stats (whose layout stays as it is)
+        d["ratio_list_decisions"], d["ratio_list_overflows"] = int(rl[1]), int(rl[2])
         return d
 
     def reset_stats(self):

@@ -474,6 +474,8 @@ private:
     DevBuf<double> d_aK, d_rK, d_tK, d_tauK, d_vK, d_klist_a, d_blist_a, d_part_tau, d_part_v;
     DevBuf<int> d_klist_s, d_blist_s;
     DevBuf<double> d_red_key, d_red_key2;
+    DevBuf<int> d_rl_cnt, d_rl_pos;    // list form of the primal Harris test: per ratio block its count and its entries (ensure_red)
+    DevBuf<double> d_rl_ca, d_rl_q;
     DevBuf<int> d_red_idx;
     DevBuf<unsigned> d_ticket;
     DevBuf<Ctl> d_ctl;

@@ -325,6 +325,7 @@ Geom Engine::geom() const {
     // in-kernel wait between the two Harris passes: never while the ranks of a sharded solve share a device (their grids
     // compete for the same CUs), never again after a wait has timed out once
     g.ratio_two = (ratio_two || (shard_world > 1 && ranks_share_device)) ? 1 : 0;
+    g.ratio_list = ratio_spin_limit > 0 ? 1 : 0;  // (a spin limit of 0 is the test hook that makes the in-kernel wait give up: the wait then has to run)
     g.str = (str_now && !stepping && !fac_on_) ? 1 : 0;
     g.sb = (g.str && sb_now) ? 1 : 0;
     g.ph = (g.str && ph_now) ? 1 : 0;
@@ -547,6 +548,7 @@ DevView* Engine::sync_view() {
     v.klist_s = d_klist_s.p; v.klist_a = d_klist_a.p; v.blist_s = d_blist_s.p; v.blist_a = d_blist_a.p;
     v.part_tau = d_part_tau.p; v.part_v = d_part_v.p;
     v.red_key = d_red_key.p; v.red_key2 = d_red_key2.p; v.red_idx = d_red_idx.p; v.ticket = d_ticket.p;
+    v.rl_cnt = d_rl_cnt.p; v.rl_ca = d_rl_ca.p; v.rl_q = d_rl_q.p; v.rl_pos = d_rl_pos.p;
     v.ctl = d_ctl.p;
     v.nb_rng = d_nb_rng.p;
     v.hy_stamp_n = d_hy_stamp.p;
@@ -715,6 +717,12 @@ void Engine::ensure_red() {
     // (k_fpull_p1 reduces over one block per 32 items of m rows + cap slots, cap <= m)
     size_t need = std::max<size_t>(1024, std::max((size_t)(std::max(m_, num_vars) + 255) / 256, ((size_t)m_ * 2 + 2048) / 32) + 8);
     d_red_key.ensure(need, 0, st); d_red_key2.ensure(need, 0, st); d_red_idx.ensure(need, 0, st);
+    if (!d_rl_cnt.p) {  // (fixed size: grid_for never launches more ratio blocks; zeroed once — the final block loads entries beyond a list's count and masks them)
+        d_rl_cnt.ensure(RL_BLOCKS, 0, st); d_rl_pos.ensure((size_t)RL_BLOCKS * RL_CAP, 0, st);
+        d_rl_ca.ensure((size_t)RL_BLOCKS * RL_CAP, 0, st); d_rl_q.ensure((size_t)RL_BLOCKS * RL_CAP, 0, st);
+        HIPCHECK(hipMemsetAsync(d_rl_cnt.p, 0, sizeof(int) * d_rl_cnt.cap, st)); HIPCHECK(hipMemsetAsync(d_rl_pos.p, 0, sizeof(int) * d_rl_pos.cap, st));
+        HIPCHECK(hipMemsetAsync(d_rl_ca.p, 0, sizeof(double) * d_rl_ca.cap, st)); HIPCHECK(hipMemsetAsync(d_rl_q.p, 0, sizeof(double) * d_rl_q.cap, st));
+    }
     view_dirty = true;
 }
 // delayed-update mode: fold the pending rank-1 terms into W0 (host-requested, outside the pivot graph)
@@ -1457,6 +1465,9 @@ void Engine::launch_stage(int phase, int stage, bool with_events) {
     // head inside, the two launches of the pull; t_K rides in the second one, rho_K keeps its BTRAN launch (the v tail waits for the exchange).
     const bool fpl_base = g.fp && phase == 0 && pse && lazy && !stepping && !smallb && !g.head_fused && max_col_nnz_ <= HEAD_LIST_CAP && fpull_supported(dv, g);
     const bool fpl = fpl_base && ((tkr && ftran_head_rides_gather(dv, g)) || (shard_world > 1 && dv.lrJ > 0 && dv.pb_on && !dv.det_pull && dv.rowinfo != nullptr));
+    // medium nucleus (eager update, heads inside their kernels): t_K rides in the ratio launch and its final block forms rho_K — the BTRAN stage
+    // is empty.  MLP_BTRAN_RIDE=0: k_btran.
+    const bool btr = !phead && !smallb && !tkr && !fpl && phase == 0 && pse && lazy && !stepping && shard_world == 1 && !shard_is_live() && btran_rides_ratio(dv, g);
     if (stage == STAGE_BASIS) touch_done = false;
     // The pricing decision (q for primal, r for dual) is already in Ctl: it was taken by the
     // previous iteration's update kernel, or by the standalone pricing kernel at batch start.
@@ -1491,11 +1502,11 @@ void Engine::launch_stage(int phase, int stage, bool with_events) {
             // pull of -F alpha_K (+ y_S) with K5 p1 | K5 p2 (+ K3 head + plan) | t_K; sampled iteration: the FTRAN bracket closes behind the
             // first of the two launches, which completes alpha_q
             launch_fpull_ratio(dv, g, st, with_events ? ev[7] : nullptr);
-        } else if (phase == 0) launch_ratio_primal(dv, g, pse, st, tkr ? 1 : (tkr_s ? 2 : 0));  // K5 p1 (+ ||alpha||^2, y_S), p2 (+ K3 head + plan) [| t_K]
+        } else if (phase == 0) launch_ratio_primal(dv, g, pse, st, tkr ? 1 : ((tkr_s || btr) ? 2 : 0), btr ? 1 : 0);  // K5 p1 (+ ||alpha||^2, y_S), p2 (+ K3 head + plan) [| t_K]
         else launch_ratio_dual(dv, g, st, ar_built_ ? 1 : 0);  // K7 p1, p2 (+ K2 head); over the listed non-zeros of alpha_r when the tableau row listed them
         break;
     case STAGE_BTRAN:
-        if (phead || smallb || rkr) break;
+        if (phead || smallb || rkr || btr) break;
         if (phase == 1 && g.head_fused) {
             launch_btran_fused(dv, g, 0, 1, st);                  // K3 head inside the BTRAN kernel (one launch)
         } else {
@@ -3561,6 +3572,13 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
         tmp = {(double)(hview.fpk_on ? 1 : 0), (double)fpk_builds_, (double)fpk_built_at_, (double)(fpull_supported(hview, geom()) ? 1 : 0)};
     } else if (w == "ratio_primal_form") {  // what launch_ratio_primal runs at this size: 0 one block, 1 the fused grid, 2 two launches with stride loops
         tmp = {(double)ratio_primal_form(hview, geom())};
+    } else if (w == "ratio_list") {  // list form of the grid test (one grid pass): [in effect, decisions it took, decisions whose final block re-scanned]
+        pull_ctl();
+        const Geom g_ = geom();
+        tmp = {(double)((ratio_primal_form(hview, g_) == 1 && ratio_list_cap(hview, g_) >= 0) ? 1 : 0), (double)h_ctl->rl_decisions, (double)h_ctl->rl_overflows};
+    } else if (w == "btran_ride") {  // medium nucleus without a BTRAN launch: [would be in effect at this size, iterations whose rho_K the ratio test's final block formed]
+        pull_ctl();
+        tmp = {(double)(btran_rides_ratio(hview, geom()) ? 1 : 0), (double)h_ctl->rk_rides};
     } else if (w == "golive_checks") {  // fingerprint comparisons passed at the go-live point of the deferred sharding
         tmp = {(double)golive_checks_};
     } else if (w == "shard_live") {

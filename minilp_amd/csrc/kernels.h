@@ -125,6 +125,9 @@ struct Ctl {
     int ar_pauses;  // times the listing was paused since the Solution was created (state("dual_list_tests")[1])
     int ar_keep;  // >= 0: the dual Harris test of this iteration ran over that many listed non-zeros of alpha_r (ar_list still holds them): the
                   // update kernel walks the list instead of all n positions (solver.rs:1073-1080 updates d on the non-zeros of row_coeffs); -1: no list
+    int rk_rides;      // lazy primal iterations whose rho_K was formed by the ratio test's final block: no BTRAN launch (state("btran_ride")[1])
+    int rl_decisions;  // primal Harris tests decided by the list form (one grid pass; state("ratio_list")[1])
+    int rl_overflows;  // ... of which a block's list did not fit and the final block re-scanned every position (state("ratio_list")[2])
 };
 
 // Sharded pricing: one 64-byte mailbox record per (kind, parity, rank) in host
@@ -292,6 +295,9 @@ struct DevView {
     double* part_v;    // [nrowstripes][ld]
     // reductions
     double* red_key; double* red_key2; int* red_idx; unsigned* ticket;
+    // list form of the primal Harris test (k_ratio_primal_fused): per ratio block the number of positions that can still win and up to RL_CAP
+    // of them as (|alpha|, ratio, position) — buffers of their own: the final block reads them while red_key* hold the pass-1 partials
+    int* rl_cnt; double* rl_ca; double* rl_q; int* rl_pos;
     Ctl* ctl;
     // column-block sharding of the pricing path: this rank owns non-basic positions [nb_lo, nb_hi)
     int nb_lo, nb_hi, rank, world;
@@ -393,6 +399,9 @@ struct DevView {
 };
 constexpr int FAC_BMAX = 1024;
 constexpr int AR_CAP = 2048;     // entries of DevView.ar_list the one-block dual Harris test takes (ratio_dual_list); k_sweep stops listing beyond
+constexpr int RK_LDS = 64;       // entries of the BTRAN list the ratio test's final block takes over through LDS when it forms rho_K itself (the rest from memory)
+constexpr int RL_CAP = 8;        // list form of the primal Harris test: entries a ratio block hands to the final block (more: the final block re-scans)
+constexpr int RL_BLOCKS = 512;   // ... and the ratio blocks the list buffers hold (grid_for's largest grid)
 constexpr int TK_ONE = 128;      // a ticket (last_block_arrives) counts up to this many arrivals at one address, more in two steps
 constexpr int TK_GROUPS = 16;    // first-step tickets of the two-step form
 constexpr int TK_STRIDE = 1024;  // words between them: ticket[TK_STRIDE * (1 + x)], x < TK_GROUPS
@@ -422,6 +431,7 @@ struct Geom {
     int fac;            // compact factor of the basis instead of the explicit nucleus inverse (factor.inc)
     int ph;             // small nucleus, lazy primal iteration: FTRAN + Harris test + BTRAN + inverse update + touched columns in ONE workgroup (k_primal_head)
     int ratio_two;      // the two Harris passes as two launches (no in-kernel wait): MLP_RATIO_TWO_KERNELS, ranks sharing a device, after an ITER_STALL
+    int ratio_list;     // the grid form of the primal Harris test may run as ONE grid pass (list form): off when the spin limit of the in-kernel wait is <= 0
     int fp;             // large nucleus, lazy primal iteration: the F product of the FTRAN is PULLED inside the ratio test's launch (fpull.inc)
 };
 
@@ -441,8 +451,10 @@ void launch_fpull_ratio(const DevView& dv, const Geom& g, hipStream_t st, hipEve
 void launch_fpk_build(const DevView& dv, hipStream_t st);   // the packed copy from the CSR of A and the current maps (fpk_in cleared beforehand)
 void launch_btran_fused(const DevView& dv, const Geom& g, int with_rhs, int derive_dual, hipStream_t st);  // BTRAN head + gather (dual iteration)
 constexpr int HEAD_LIST_CAP = 1024;  // entries an in-kernel stage head can hold (longest column / row of A)
-void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride = 0);  // K5 p1 (+alpha_sq, y_S), p2 (+BTRAN head, plan) [| t_K blocks]
+void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride = 0, int rk_inside = 0);  // K5 p1 (+alpha_sq, y_S), p2 (+BTRAN head, plan) [| t_K blocks]
 bool tk_rides_ratio(const DevView& dv, const Geom& g);
+bool btran_rides_ratio(const DevView& dv, const Geom& g);  // medium nucleus: t_K rides in the ratio launch and its final block forms rho_K (no BTRAN launch)
+int ratio_list_cap(const DevView& dv, const Geom& g);   // list form of the grid test: entries per block, -1 when the publish-wait form runs
 int ratio_primal_form(const DevView& dv, const Geom& g);  // 0 one block, 1 fused grid (one launch), 2 two launches with stride loops
 bool tk_rides_ratio_small(const DevView& dv, const Geom& g);  // the same for a small nucleus (k_small_basis), y_S formed on the fly  // large nucleus, lazy primal iteration: t_K is formed by blocks riding behind the ratio blocks
 void launch_post_ftran(const DevView& dv, const Geom& g, int use_pse, hipStream_t st);    // dual path: alpha_sq, y_S, plan

@@ -788,7 +788,10 @@ __device__ void ftran_prep_wave(const DevView& v, Ctl* c, int lane, int derive_p
     if (lane < nlow) c->lr_c[lane] = lr_acc;
 }
 // BTRAN head (one wave): rho = B^-T e_r (solver.rs:680-683) as a short list of rows of W.
-__device__ void btran_prep_wave(const DevView& v, Ctl* c, int lane, int r, int derive_dual, int plan_after, int phase) {
+// l_s / l_a / l_n (LDS, optional): the first RK_LDS entries of the list and its length for a consumer in the same workgroup (rho_K inside the
+// ratio test's final block) — what memory gets is unchanged
+__device__ void btran_prep_wave(const DevView& v, Ctl* c, int lane, int r, int derive_dual, int plan_after, int phase, int* l_s = nullptr,
+                                double* l_a = nullptr, int* l_n = nullptr) {
     IterState* it = &c->it;
     if (derive_dual && !c->forced && lane == 0) {  // solver.rs:892-916 (a host-forced row keeps the host's value)
         double val = v.xB[r], mn = v.loB[r];
@@ -800,6 +803,7 @@ __device__ void btran_prep_wave(const DevView& v, Ctl* c, int lane, int r, int d
     if (v.fac_on) {  // compact factor: rho = B^-T e_r comes from the level-scheduled solve (k_fac_solve), nothing to list
         if (lane == 0) {
             it->blist_n = 0;
+            if (l_n) *l_n = 0;
             if (plan_after) plan_update(v, c, phase);
         }
         return;
@@ -813,6 +817,11 @@ __device__ void btran_prep_wave(const DevView& v, Ctl* c, int lane, int r, int d
             v.blist_s[0] = sr;
             v.blist_a[0] = 1.0;
             it->blist_n = 1;
+            if (l_n) {
+                l_s[0] = sr;
+                l_a[0] = 1.0;
+                *l_n = 1;
+            }
         }
     } else {
         int i_r = v.srow_of_pos[r];
@@ -852,13 +861,20 @@ __device__ void btran_prep_wave(const DevView& v, Ctl* c, int lane, int r, int d
                     int off = cnt + __popcll(mask & ((1ull << lane) - 1ull));
                     v.blist_s[off] = s;
                     v.blist_a[off] = coef;
+                    if (l_n && off < RK_LDS) {
+                        l_s[off] = s;
+                        l_a[off] = coef;
+                    }
                 }
                 cnt += __popcll(mask);
                 // e_j = U[j] . (listed rows): lane j serves pending term j, entries travel by shuffle in list order
                 if (nlow > 0) lr_dot_listed(mask, s, coef, Urow, lane < nlow, lr_acc);
             }
         }
-        if (lane == 0) it->blist_n = cnt;
+        if (lane == 0) {
+            it->blist_n = cnt;
+            if (l_n) *l_n = cnt;
+        }
     }
     if (nlow > 0) {  // delayed-update mode
         if (sr >= 0 && lane < nlow) lr_acc = Urow[sr];
@@ -1446,10 +1462,15 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_p1(DevView v, int use_pse)
 }
 // Finalising block of the primal ratio test: the decision (solver.rs:820-853), in sharded mode the adoption
 // of rank 0's decision, then the BTRAN head and the partition plan.
-__device__ void ratio_primal_finish(const DevView& v, Ctl* c, Cand best) {
+// rk_inside (medium nucleus, lazy primal iteration; launch_ratio_primal): the block goes on with rho_K = sum_j blist_a[j] W[blist_s[j], :],
+// rho by row and ||rho||^2 — the first part of k_btran, whose launch is then not issued (t_K rides in this launch as well).  Per slot the
+// sum runs over j ascending, btran_rk_body's order: rho_K has the same bits.  ||rho||^2 is summed by one block in slot order, so its last
+// bits may differ from the grid fold's; a lazy primal pivot does not read it (the dual edge norms are rebuilt exactly later).
+__device__ __forceinline__ void ratio_primal_finish(const DevView& v, Ctl* c, Cand best, int rk_inside = 0) {
     IterState* it = &c->it;
     const int sign = it->sign;
-    __shared__ int s_r;
+    __shared__ int s_r, s_bn, s_bs[RK_LDS];
+    __shared__ double s_ba[RK_LDS];
     if (threadIdx.x == 0) {
         const int q = it->q;
         const double dq = v.d[q];
@@ -1517,8 +1538,61 @@ __device__ void ratio_primal_finish(const DevView& v, Ctl* c, Cand best) {
     if (s_r >= 0) {
         // the BTRAN head (wave 0) and the partition plan (first lane of wave 1) are independent chains of dependent
         // loads over disjoint outputs: side by side they cost the longer of the two instead of their sum
-        if (threadIdx.x < 64) btran_prep_wave(v, c, threadIdx.x, s_r, 0, 0, 0);
+        if (threadIdx.x < 64) btran_prep_wave(v, c, threadIdx.x, s_r, 0, 0, 0, rk_inside ? s_bs : nullptr, s_ba, rk_inside ? &s_bn : nullptr);
         else if (threadIdx.x == 64) plan_update(v, c, 0);
+    }
+    if (!rk_inside) return;
+    __syncthreads();  // (uniform: the list is in LDS, what did not fit there is visible in memory to this workgroup)
+    if (s_r < 0) return;
+    const int n = s_bn, k = c->k;
+    const size_t ld = (size_t)v.ld;
+    double sq = 0.0;
+    constexpr int RS = 8;  // slots per thread and trip: every load of a trip is issued before its first use
+    for (int s0 = threadIdx.x; s0 < k; s0 += RS * BLK) {
+        double acc[RS];
+        int row[RS];
+#pragma unroll
+        for (int u = 0; u < RS; ++u) {
+            acc[u] = 0.0;
+            row[u] = s0 + u * BLK < k ? v.row_of_kslot[s0 + u * BLK] : 0;
+        }
+        for (int j = 0; j < n; j += 2) {  // two listed rows per trip, added in list order
+            const bool two = j + 1 < n;
+            const double a0 = j < RK_LDS ? s_ba[j] : v.blist_a[j];
+            const int r0 = j < RK_LDS ? s_bs[j] : v.blist_s[j];
+            const double a1 = !two ? 0.0 : (j + 1 < RK_LDS ? s_ba[j + 1] : v.blist_a[j + 1]);
+            const int r1 = !two ? r0 : (j + 1 < RK_LDS ? s_bs[j + 1] : v.blist_s[j + 1]);
+            double w0[RS], w1[RS];
+#pragma unroll
+            for (int u = 0; u < RS; ++u) {
+                const int s = s0 + u * BLK;
+                w0[u] = s < k ? v.W[(size_t)r0 * ld + s] : 0.0;
+                w1[u] = (two && s < k) ? v.W[(size_t)r1 * ld + s] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < RS; ++u) {
+                acc[u] += a0 * w0[u];
+                if (two) acc[u] += a1 * w1[u];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RS; ++u) {
+            const int s = s0 + u * BLK;
+            if (s >= k) continue;
+            v.rK[s] = acc[u];
+            v.rv[row[u]].x = acc[u];
+            sq += acc[u] * acc[u];
+        }
+    }
+    sq = block_sum(sq);
+    if (threadIdx.x == 0) {
+        const int r = s_r;
+        if (v.kslot_of_pos[r] < 0) {
+            const double inv = 1.0 / v.sdiag_of_pos[r];
+            sq += inv * inv;
+        }
+        c->it.rho_sq = sq;
+        atomicAdd(&c->rk_rides, 1);
     }
 }
 
@@ -1659,10 +1733,32 @@ __device__ __forceinline__ void tk_ride_body(const DevView& v, const Ctl* c, int
 // y_S by row (its ys form: the quotient the ratio test would write, use_pse = 2 tells pass 1 not to), so the 2 M-entry pull that
 // made k_btran a 23 us kernel runs in the shadow of the ratio test's two grid-wide hand-offs.  The ratio blocks come first in
 // dispatch order and wait only for each other: the co-residency argument of the in-kernel wait is unchanged.
-__global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_pse, int n_ratio = 0, int tk_lanes = 0, int tk_onfly = 0) {
+__global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_pse, int n_ratio = 0, int tk_lanes = 0, int tk_onfly = 0, int rl_cap = -1, int rk_inside = 0) {
     Ctl* c = v.ctl;
-    if (c->halt || c->it.status != ITER_PIVOT) return;
     const int nrb = n_ratio > 0 ? n_ratio : (int)gridDim.x;
+    // Grid form: the inputs of the thread's PT positions depend on nothing but the block index, so their loads are issued BEFORE the
+    // control block is looked at — the two dependent round trips in front of them (halt / status, then sign and the list length)
+    // no longer stand between kernel entry and pass 1.  (Where supp(alpha_q) is listed the sparse form usually runs: loaded later.)
+    constexpr int PT = 4;               // elements per thread (grid_for's default)
+    double in_co[PT], in_sd[PT], in_xb[PT], in_lo[PT], in_hi[PT];
+    int in_ks[PT], in_sr[PT];
+    const bool loads_first = (int)blockIdx.x < nrb && !aq_listing(v);
+#define RATIO_LOAD_INPUTS()                                                            \
+    _Pragma("unroll") for (int u = 0; u < PT; ++u) {                                   \
+        const int p = (int)blockIdx.x * BLK + threadIdx.x + u * nrb * BLK;             \
+        const bool in = p < v.m;                                                       \
+        in_co[u] = in ? v.alpha_q[p] : 0.0;                                            \
+        in_ks[u] = in ? v.kslot_of_pos[p] : 0;                                         \
+        in_sr[u] = in ? v.srow_of_pos[p] : 0;                                          \
+        in_sd[u] = in ? v.sdiag_of_pos[p] : 1.0;                                       \
+        in_xb[u] = in ? v.xB[p] : 0.0;                                                 \
+        in_lo[u] = in ? v.loB[p] : 0.0;                                                \
+        in_hi[u] = in ? v.hiB[p] : 0.0;                                                \
+    }
+    if (loads_first) {
+        RATIO_LOAD_INPUTS();
+    }
+    if (c->halt || c->it.status != ITER_PIVOT) return;
     if ((int)blockIdx.x >= nrb) {
         const int tb = (int)blockIdx.x - nrb;
         if (tk_onfly) {  // (small nucleus: k_small_basis then carries no t_K blocks and waits for none)
@@ -1678,6 +1774,10 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
     }
     const int sign = c->it.sign;
     KMARK0(c, 1);
+    // (the three forms below leave the winner in `best` and meet at ONE call of ratio_primal_finish: a second call site would make it a real
+    // function, and a DevView passed by reference lives in scratch memory)
+    Cand best = cand_none();
+    do {
     if (aq_listing(v) && c->aq_n <= AQ_CAP) {
         // Sparse form: block 0 alone runs both Harris passes (solver.rs:782-853), ||alpha_q||^2 and the singleton part of v
         // over the listed positions of supp(alpha_q); no grid-wide reduction, no in-kernel wait.  Ties keep the lowest
@@ -1746,7 +1846,6 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
         __syncthreads();
         KMARK(c, 3);
         const double max_step = s_ms;
-        Cand best = cand_none();
 #pragma unroll
         for (int u = 0; u < PL; ++u) {
             if (pos[u] < 0) continue;
@@ -1757,15 +1856,16 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
         }
         best = block_best(best);
         KMARK(c, 4);
-        ratio_primal_finish(v, c, best);
-        KMARK(c, 6);
-        return;
+        break;
     }
     const int epoch0 = c->ratio_epoch;  // written by the previous launch of this kernel: stable here
-    constexpr int PT = 4;               // elements per thread (grid_for's default)
     double ca[PT], stp[PT];
     int pos[PT];
     double mn = INFINITY, sq = 0.0;
+    if (!loads_first) {
+        RATIO_LOAD_INPUTS();
+    }
+#undef RATIO_LOAD_INPUTS
 #pragma unroll
     for (int u = 0; u < PT; ++u) {
         const int p = (int)blockIdx.x * BLK + threadIdx.x + u * nrb * BLK;
@@ -1775,10 +1875,10 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
         if (p >= v.m) continue;
         // every input of the element is loaded up front (independent loads in flight together) instead of behind the
         // branches that use it: one dependent memory round trip less on the critical path of the iteration
-        const double coeff = v.alpha_q[p];
-        const int ks = v.kslot_of_pos[p], sr = v.srow_of_pos[p];
-        const double sd = v.sdiag_of_pos[p];
-        const double xb = v.xB[p], lob = v.loB[p], hib = v.hiB[p];
+        const double coeff = in_co[u];
+        const int ks = in_ks[u], sr = in_sr[u];
+        const double sd = in_sd[u];
+        const double xb = in_xb[u], lob = in_lo[u], hib = in_hi[u];
         if (use_pse) {
             sq += coeff * coeff;
             if (ks < 0 && use_pse != 2) v.rv[sr].y = coeff / sd;
@@ -1792,6 +1892,163 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
         stp[u] = st;
         const double cur = (st + EPS) / a;
         if (cur < mn) mn = cur;
+    }
+    if (rl_cap >= 0) {
+        // List form (one grid pass, no in-kernel wait): pass 2 only looks for the largest |alpha| among the positions whose ratio
+        // q = step / |alpha| is within max_step = min(grid minimum of (step + EPS) / |alpha|, bound), and pass 1 has seen every one of
+        // them with its numbers in registers.  max_step never exceeds lim_b = min(block minimum, bound), so the positions of the block
+        // with q <= lim_b (S_b) contain every position pass 2 could accept.  Exact pruning: top_b = the best of S_b (cand_better); any
+        // other member with q >= q_top can be dropped — whenever it is eligible so is top_b, which beats it.  What is left (top_b and
+        // the members with q < q_top: one or two entries on continuous data, exactly one when every ratio is zero) travels with the
+        // block's pass-1 partials; the last arriver of the ONE ticket folds the partials as grid_min_sum does (the same max_step and
+        // alpha_sq bits), keeps the listed entries with q <= max_step and decides.  The other blocks are done when they have arrived.
+        __shared__ double s_lim, s_tca, s_tq, s_lca[RL_CAP], s_lq[RL_CAP];
+        __shared__ int s_tpos, s_cnt, s_lpos[RL_CAP], s_ovf;
+        const double mb = block_min(mn), sb = block_sum(sq);  // (thread 0)
+        double qv[PT];
+        Cand mine = cand_none();
+        double mine_q = 0.0;
+        if (threadIdx.x == 0) {
+            const double bound = fabs(c->it.entering_other - c->it.entering_cur);
+            s_lim = mb < bound ? mb : bound;
+            s_cnt = 0;
+            s_ovf = 0;
+        }
+        __syncthreads();
+        const double lim = s_lim;
+#pragma unroll
+        for (int u = 0; u < PT; ++u) {  // ascending positions per thread, so ties keep the lowest position
+            qv[u] = 0.0;
+            if (pos[u] < 0) continue;
+            qv[u] = stp[u] / ca[u];  // the very expression pass 2 compares with max_step
+            if (qv[u] <= lim) {
+                Cand t{ca[u], pos[u]};
+                if (cand_better(t, mine)) {
+                    mine = t;
+                    mine_q = qv[u];
+                }
+            } else pos[u] = -1;  // not in S_b
+        }
+        block_best_p(mine, mine_q);  // (thread 0)
+        if (threadIdx.x == 0) {
+            s_tca = mine.key;
+            s_tq = mine_q;
+            s_tpos = mine.idx;
+            if (mine.idx != NONE_IDX) s_cnt = 1;  // entry 0 of the block's list is top_b
+        }
+        __syncthreads();
+        const int tpos = s_tpos;
+        const double tq = s_tq;
+        if (tpos != NONE_IDX) {
+#pragma unroll
+            for (int u = 0; u < PT; ++u) {
+                if (pos[u] < 0 || pos[u] == tpos || !(qv[u] < tq)) continue;
+                const int at = atomicAdd(&s_cnt, 1);  // (the order of the appends does not matter: cand_better is a total order)
+                if (at < rl_cap) {
+                    s_lca[at] = ca[u];
+                    s_lq[at] = qv[u];
+                    s_lpos[at] = pos[u];
+                }
+            }
+        }
+        __syncthreads();
+        const int cnt = s_cnt;  // above rl_cap: stored as it is — the final block then re-scans every position
+        // (the storing lanes are lanes of thread 0's wave: its s_waitcnt in last_block_arrives drains their stores as well)
+        static_assert(RL_CAP <= 64, "the list is stored by lanes of the wave that takes the ticket");
+        if ((int)threadIdx.x < cnt && (int)threadIdx.x < rl_cap) {
+            const size_t at = (size_t)blockIdx.x * RL_CAP + threadIdx.x;
+            st_agent(&v.rl_ca[at], threadIdx.x == 0 ? s_tca : s_lca[threadIdx.x]);
+            st_agent(&v.rl_q[at], threadIdx.x == 0 ? s_tq : s_lq[threadIdx.x]);
+            st_agent(&v.rl_pos[at], threadIdx.x == 0 ? tpos : s_lpos[threadIdx.x]);
+        }
+        if (threadIdx.x == 0) {
+            st_agent(&v.red_key[blockIdx.x], mb);
+            st_agent(&v.red_key2[blockIdx.x], sb);
+            st_agent(&v.rl_cnt[blockIdx.x], cnt);
+        }
+        if (!last_block_arrives(v.ticket, (unsigned)nrb)) return;
+        double y = INFINITY, z = 0.0;
+        for (int i = threadIdx.x; i < nrb; i += blockDim.x) {  // (the fold of grid_min_sum)
+            const double t = ld_agent(&v.red_key[i]);
+            if (t < y) y = t;
+            z += ld_agent(&v.red_key2[i]);
+        }
+        // the lists: entry e belongs to block e / RL_CAP; count and entry are loaded side by side (slots beyond the count hold stale
+        // entries, which the count masks) and before the fold's reductions — no round trip of their own.  RE entries per thread and
+        // trip: one trip covers 128 blocks (524 288 / 4 096 positions: beyond that the loop goes round again)
+        constexpr int RE = 4;
+        static_assert(BLK % RL_CAP == 0, "a thread's entries have one index within their lists");
+        const int n_ent = nrb * RL_CAP;
+        double eca[RE], eq[RE];
+        int epos[RE], ecnt[RE];
+#pragma unroll
+        for (int u = 0; u < RE; ++u) {
+            const int e = threadIdx.x + u * BLK;
+            const bool in = e < n_ent;
+            ecnt[u] = in ? ld_agent(&v.rl_cnt[e / RL_CAP]) : 0;
+            eca[u] = in ? ld_agent(&v.rl_ca[e]) : 0.0;
+            eq[u] = in ? ld_agent(&v.rl_q[e]) : 0.0;
+            epos[u] = in ? ld_agent(&v.rl_pos[e]) : NONE_IDX;
+        }
+        y = block_min(y);
+        z = block_sum(z);
+        if (threadIdx.x == 0) {
+            double max_step = fabs(c->it.entering_other - c->it.entering_cur);
+            if (y < max_step) max_step = y;
+            c->it.max_step = max_step;
+            c->it.alpha_sq = z + 1.0;
+            s_lim = max_step;
+            *v.ticket = 0;
+        }
+        __syncthreads();
+        KMARK(c, 3);
+        const double max_step = s_lim;
+        bool ovf = false;
+        const int j = threadIdx.x % RL_CAP;
+        for (int e0 = 0;;) {
+#pragma unroll
+            for (int u = 0; u < RE; ++u) {
+                if (ecnt[u] > rl_cap) ovf = true;
+                else if (j < ecnt[u] && eq[u] <= max_step) {
+                    Cand t{eca[u], epos[u]};
+                    if (cand_better(t, best)) best = t;
+                }
+            }
+            e0 += RE * BLK;
+            if (e0 >= n_ent) break;
+#pragma unroll
+            for (int u = 0; u < RE; ++u) {
+                const int e = e0 + threadIdx.x + u * BLK;
+                const bool in = e < n_ent;
+                ecnt[u] = in ? ld_agent(&v.rl_cnt[e / RL_CAP]) : 0;
+                eca[u] = in ? ld_agent(&v.rl_ca[e]) : 0.0;
+                eq[u] = in ? ld_agent(&v.rl_q[e]) : 0.0;
+                epos[u] = in ? ld_agent(&v.rl_pos[e]) : NONE_IDX;
+            }
+        }
+        if (ovf) s_ovf = 1;
+        __syncthreads();
+        if (s_ovf) {  // a list did not fit (rare by construction): this block re-runs pass 2 over every position, waiting for nobody
+            best = cand_none();
+            for (int p = threadIdx.x; p < v.m; p += BLK) {
+                const double coeff = v.alpha_q[p];
+                const double a = fabs(coeff);
+                if (a < EPS) continue;
+                bool tm;
+                const double cur = leaving_step(v, p, coeff, sign, tm) / a;
+                if (cur <= max_step) {
+                    Cand t{a, p};
+                    if (cand_better(t, best)) best = t;
+                }
+            }
+        }
+        best = block_best(best);
+        if (threadIdx.x == 0) {
+            atomicAdd(&c->rl_decisions, 1);  // (no value returned: nothing waits for the counters)
+            if (s_ovf) atomicAdd(&c->rl_overflows, 1);
+        }
+        KMARK(c, 4);
+        break;
     }
     __shared__ double s_max_step;
     if (grid_min_sum(mn, sq, v, nrb)) {  // last arriver of pass 1: publish the step bound
@@ -1833,7 +2090,6 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
         return;
     }
     const double max_step = s_max_step;
-    Cand best = cand_none();
 #pragma unroll
     for (int u = 0; u < PT; ++u) {  // ascending positions per thread, so ties keep the lowest position
         if (pos[u] < 0) continue;
@@ -1843,7 +2099,9 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
         }
     }
     if (!grid_best(best, v, nrb)) return;
-    ratio_primal_finish(v, c, best);
+    } while (0);
+    ratio_primal_finish(v, c, best, rk_inside);
+    KMARK(c, 6);
 }
 
 // dual path, after FTRAN: the FTRAN-side pivot, ||alpha_q||^2 and y_S (PSE), then the plan
@@ -4878,12 +5136,29 @@ int ratio_primal_form(const DevView& dv, const Geom& g) {
     const int max_coresident = g.ratio_two ? 0 : coresident_half(reinterpret_cast<const void*>(k_ratio_primal_fused), 0);
     return (nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m) ? 1 : 2;
 }
-void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride) {
+// The list form of the grid test (k_ratio_primal_fused, rl_cap >= 0: one grid pass, no in-kernel wait): entries a block may list, or -1 for
+// the publish-wait form — MLP_RATIO_LIST=0, or a spin limit of 0 or less (Geom.ratio_list = 0: the hook with which a test makes the
+// in-kernel wait give up, so the wait is what has to run).  MLP_RATIO_LIST_CAP (default RL_CAP, 0: every decision re-scans) is for tests.
+int ratio_list_cap(const DevView& dv, const Geom& g) {
+    const char* e = std::getenv("MLP_RATIO_LIST");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
+    if ((e && e[0] == '0') || !g.ratio_list || !dv.rl_cnt || grid_for(g.m) > RL_BLOCKS) return -1;
+    const char* cp = std::getenv("MLP_RATIO_LIST_CAP");
+    return cp ? std::max(0, std::min(RL_CAP, std::atoi(cp))) : RL_CAP;
+}
+// Medium nucleus, lazy primal iteration: no BTRAN launch — t_K rides behind the ratio blocks (y_S on the fly, as for the small nucleus) and
+// the final block of the test forms rho_K (ratio_primal_finish, rk_inside).  Eager update of the inverse only (no pending terms), tiles of the
+// plain fused pass (capacity <= 4 096), heads inside their kernels.  MLP_BTRAN_RIDE=0: k_btran.
+bool btran_rides_ratio(const DevView& dv, const Geom& g) {
+    const char* e = std::getenv("MLP_BTRAN_RIDE");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
+    if (e && e[0] == '0') return false;
+    return g.head_fused && !g.big && !g.fac && !dv.lrJ && g.cap <= 4096 && tk_rides_ratio_small(dv, g);
+}
+void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride, int rk_inside) {
     if (tk_ride) {  // (the caller asked tk_rides_ratio / tk_rides_ratio_small first); 2: small nucleus, y_S on the fly
         const int nb = grid_for(g.m);
         const int lanes = g.lanes <= 4 ? 4 : (g.lanes <= 16 ? 16 : 64);
         hipLaunchKernelGGL(k_ratio_primal_fused, dim3(nb + blocks_for((long)g.cap * lanes)), dim3(BLK), 0, st, dv, tk_ride == 2 ? use_pse : 2, nb, lanes,
-                           tk_ride == 2 ? 1 : 0);
+                           tk_ride == 2 ? 1 : 0, ratio_list_cap(dv, g), rk_inside);
         return;
     }
     const int form = ratio_primal_form(dv, g);
@@ -4893,7 +5168,7 @@ void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStrea
     }
     const int nb = grid_for(g.m);
     if (form == 1) {  // every element fits the fused kernel's registers
-        hipLaunchKernelGGL(k_ratio_primal_fused, dim3(nb), dim3(BLK), 0, st, dv, use_pse, 0, 0, 0);  // both passes + BTRAN head + plan
+        hipLaunchKernelGGL(k_ratio_primal_fused, dim3(nb), dim3(BLK), 0, st, dv, use_pse, 0, 0, 0, ratio_list_cap(dv, g));  // both passes + BTRAN head + plan
         return;
     }
     hipLaunchKernelGGL(k_ratio_primal_p1, dim3(nb), dim3(BLK), 0, st, dv, use_pse);
