@@ -3,11 +3,16 @@
 minimise, print the objective and the non-zero variables.
 
     python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--tableau VAR] [--gomory-rounds K]
+                                 [--gmi-rounds K [--continuous NAME,...]]
 
 --ranging adds a sensitivity table: per variable its value, basis status, reduced cost and cost range; per row its dual value and
 rhs range (rows in file order).  --tableau VAR prints the tableau row of the basic variable VAR (by name): its non-zero coefficients on the
 non-basic variables and on the slacks of the rows, the raw material of a mixed-integer cut.  --gomory-rounds K adds K rounds of Gomory cuts, each over all basic structural variables with a
 fractional value (|x - round x| > 1e-6) in one add_gomory_cuts call, and prints the bound and the call's counters after each round.
+That cut is valid only for a pure integer model with integer slacks whose non-basic columns sit at a zero lower bound.  --gmi-rounds K adds
+K rounds of Gomory mixed-integer cuts instead (one add_gmi_cuts call per round over the basic integer variables with a fractional value):
+every structural variable is integer unless listed in --continuous, the slacks are continuous; it prints the bound, the cuts emitted and
+skipped and the counters after each round.
 
 Runs on the MI355X engine (libminilp_hip.so); there is no CPU back end.  `run(B, ...)` takes the module that
 provides the reference's API so that the tests can drive the same code with their checker."""
@@ -19,7 +24,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None):
+def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=()):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -76,6 +81,29 @@ def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0,
             print("gomory round %d: infeasible" % (k + 1))
             return 1
         print("gomory round %d: %d cuts, bound %.12g, %s" % (k + 1, len(frac), sol.objective(), sol.cut_info()))
+    if gmi_rounds:
+        unknown = [nm for nm in continuous if nm not in f.variables]
+        if unknown:
+            print("gmi: no variable named %s" % ", ".join(unknown))
+            return 1
+        is_int = [True] * len(f.variables)
+        for nm in continuous:
+            is_int[f.variables[nm]] = False
+    for k in range(gmi_rounds):
+        x = sol.values()
+        vs, _ = sol.basis_status()
+        frac = [v for v in range(len(x)) if is_int[v] and vs[v] == 0 and abs(x[v] - round(x[v])) > 1e-6]
+        if not frac:
+            print("gmi round %d: no fractional basic integer variable" % (k + 1))
+            break
+        try:
+            sol, status = sol.add_gmi_cuts(frac, is_int)
+        except B.Infeasible:
+            print("gmi round %d: infeasible" % (k + 1))
+            return 1
+        status = list(status)
+        print("gmi round %d: %d cuts emitted, %d skipped (fraction) + %d skipped (free column), bound %.12g, %s %s" %
+              (k + 1, status.count(0), status.count(1), status.count(2), sol.objective(), sol.gmi_info(), sol.cut_info()))
     return 0
 
 
@@ -88,9 +116,13 @@ def main():
     ap.add_argument("--gomory-rounds", type=int, default=0, metavar="K",
                     help="K rounds of Gomory cuts over the fractional basic variables (one add_gomory_cuts call per round)")
     ap.add_argument("--tableau", metavar="VAR", help="print the tableau row of the basic variable VAR (by name)")
+    ap.add_argument("--gmi-rounds", type=int, default=0, metavar="K",
+                    help="K rounds of Gomory mixed-integer cuts over the fractional basic integer variables (one add_gmi_cuts call per round)")
+    ap.add_argument("--continuous", default="", metavar="NAME,...",
+                    help="with --gmi-rounds: the variables that are NOT integer (all others are; slacks are continuous)")
     a = ap.parse_args()
     import minilp_amd as B
-    return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau)
+    return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau, a.gmi_rounds, [nm for nm in a.continuous.split(",") if nm])
 
 
 if __name__ == "__main__":

@@ -45,6 +45,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
 /* Still version 5: the tableau entry points (mlp_solution_num_rows, mlp_solution_basis_head, mlp_solution_binv_rows / _binv_cols,
  * mlp_solution_tableau_rows / _tableau_cols, mlp_solution_basis_solve, mlp_tableau_info with its own mlp_tableau_info_size()) are
  * additive in the same way. */
+/* Still version 5: the Gomory mixed-integer round (mlp_solution_add_gmi_cuts, mlp_gmi_info with its own mlp_gmi_info_size()) is
+ * additive in the same way; mlp_cut_info keeps its 80 bytes. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -387,6 +389,53 @@ typedef struct mlp_tableau_info {
 } mlp_tableau_info;
 int mlp_solution_tableau_info(const mlp_solution* s, mlp_tableau_info* out);
 uint64_t mlp_tableau_info_size(void);
+
+/* ---- A round of Gomory mixed-integer (GMI) cuts from the tableau, in one call ------------------------------------------------------------
+ * The cut of mlp_solution_add_gomory_cuts is valid only when every non-basic column is an integer variable at a zero lower bound and the
+ * slacks are integer.  The GMI cut handles bounds, columns non-basic at their upper bound, continuous variables and slacks.
+ * Internal form, as for the tableau reads above: A x + s = b.  A request is a BASIC structural variable marked integer, at basis position
+ * p; f0 = xB_p - floor(xB_p).  Every non-basic column j (structural or slack) has a status (the codes of mlp_solution_basis_status), a
+ * value xN_j and a coefficient alpha_j = (e_p^T B^-1) abar_j.  Per column:
+ *   fixed (mlp_solution_fix_var, or lo == hi, which includes the slack of an = row): no term;
+ *   at lower: abar = alpha;   at upper: abar = -alpha;
+ *   free (non-basic at neither bound): |alpha| <= 1e-8 gives no term; otherwise the request has no valid cut and is skipped;
+ *   integer treatment, for a column that is marked integer AND has xN_j == floor(xN_j) exactly (structural columns are marked by
+ *     var_is_int, slacks by con_is_int):  f = abar - floor(abar);  g = f / f0 if f <= f0, else (1 - f) / (1 - f0);
+ *   continuous treatment, for everything else (a marked column whose value is not integral included, which is always valid):
+ *     g = abar / f0 if abar >= 0, else -abar / (1 - f0).
+ * The cut is  sum_j g_j y_j >= 1  with y_j = x_j - xN_j at lower and y_j = xN_j - x_j at upper.  It is stored as
+ * mlp_solution_add_gomory_cut stores its row: operator <=, terms on the non-basic columns (slacks included) in variable order, exact
+ * zeros dropped; stored coefficients c_j = -g_j at lower, +g_j at upper; stored right-hand side rhs = -1 + sum_j c_j xN_j.
+ * The cut is valid for the bounds the call finds: a bound tightened by mlp_solution_fix_var makes it LOCAL to that fixing (it need not
+ * hold once the variable is unfixed).
+ * A request with min(f0, 1 - f0) < away is skipped.  A skipped request appends nothing and takes no constraint number (it is not a
+ * "row without terms").  All cuts of a round come from the basis the call finds, are built on the device (16 per pass over A) and
+ * appended together: one re-layout, at most one re-inversion, feasibility restored once.  A request's row, rhs and status are bit for
+ * bit the same from run to run and whatever else is in the call.
+ * Arguments: vars[n] the requests; var_is_int[num_vars] (num_vars must be mlp_solution_num_vars); con_is_int[num_constraints]
+ *   (num_constraints must be mlp_solution_num_constraints) or NULL with any num_constraints: all slacks continuous; away in (0, 0.5];
+ *   status_out[n] or NULL: 0 emitted, 1 skipped for a fraction within away, 2 skipped for a free non-basic column in the row.
+ * MLP_EINVAL: a variable out of range, non-basic, unmarked or listed twice; a mask length that does not fit; away outside (0, 0.5]; an
+ *   unsolved model; a sharded solution; NULL handles.  MLP_INFEASIBLE => status 1 (a cut whose terms all vanish reads 0 <= -1: the
+ *   marks and the point admit no integer solution).  On every non-zero status the solution is freed and
+ *   *s = NULL, as the other mutators do.  n == 0, or a call in which every request is skipped, leaves the solution untouched.  The
+ *   dual-value / ranging / tableau caches are dropped.
+ * mlp_gmi_info: what the last mlp_solution_add_gmi_cuts call on this solution did (zeros before the first); the call also fills
+ *   mlp_cut_info as mlp_solution_add_gomory_cuts does.  Only grows at its end; mlp_gmi_info_size() is its size as the library was built. */
+int mlp_solution_add_gmi_cuts(mlp_solution** s, const uint32_t* vars, uint64_t n, const uint8_t* var_is_int, uint32_t num_vars,
+                              const uint8_t* con_is_int, uint64_t num_constraints, double away, int32_t* status_out);
+typedef struct mlp_gmi_info {
+    uint64_t requests;          /* variables asked for */
+    uint64_t rows;              /* cuts appended */
+    uint64_t skipped_fraction;  /* requests skipped: fraction within away */
+    uint64_t skipped_free;      /* requests skipped: a free non-basic column in the row */
+    uint64_t nnz;               /* terms of the appended cuts (slack entries of the new rows not counted) */
+    uint64_t batches;           /* batches of 16 requests: one pass over A each */
+    double bytes;               /* algorithmic bytes of the generation */
+    double device_ms;           /* its time on the device (HIP events around the generation launches) */
+} mlp_gmi_info;
+int mlp_solution_gmi_info(const mlp_solution* s, mlp_gmi_info* out);
+uint64_t mlp_gmi_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

@@ -582,6 +582,34 @@ impl Solution {
         self.consume(|s| unsafe { sys::mlp_solution_add_gomory_cuts(s, v.as_ptr(), v.len() as u64) })
     }
 
+    /// Add one round of Gomory mixed-integer cuts, one per listed basic integer variable, all taken from the current
+    /// basis, and return the solution with a status per request: 0 emitted, 1 skipped (fraction within `away`),
+    /// 2 skipped (a free non-basic column in the row).  `integer_vars[j]` marks variable `j` as integer;
+    /// `integer_constraints[c]` marks the slack of constraint `c` (`None`: all slacks continuous).  The cuts are valid
+    /// for the bounds the call finds (extension: no counterpart in the reference; semantics in `minilp_hip.h`).
+    ///
+    /// # Errors
+    ///
+    /// Will return an error if the problem becomes infeasible with the additional constraints.
+    ///
+    /// # Panics
+    ///
+    /// Will panic if a variable is listed twice, is not basic or is not marked integer, if a mask has the wrong
+    /// length, or if `away` is not in (0, 0.5].
+    pub fn add_gmi_cuts(self, vars: &[Variable], integer_vars: &[bool], integer_constraints: Option<&[bool]>, away: f64) -> Result<(Self, Vec<i32>), Error> {
+        let v: Vec<u32> = vars.iter().map(|x| x.0 as u32).collect();
+        assert!(vars.iter().all(|x| x.0 < self.num_vars));
+        let vm: Vec<u8> = integer_vars.iter().map(|&b| b as u8).collect();
+        let cm: Option<Vec<u8>> = integer_constraints.map(|m| m.iter().map(|&b| b as u8).collect());
+        let (cp, cn) = cm.as_ref().map_or((std::ptr::null(), 0u64), |m| (m.as_ptr(), m.len() as u64));
+        let mut status = vec![0i32; v.len()];
+        let sp = status.as_mut_ptr();
+        let out = self.consume(|s| unsafe {
+            sys::mlp_solution_add_gmi_cuts(s, v.as_ptr(), v.len() as u64, vm.as_ptr(), vm.len() as u32, cp, cn, away, sp)
+        })?;
+        Ok((out, status))
+    }
+
     /// The raw handle, for the engine-level stepping API and the diagnostics of `minilp-hip-sys`
     /// (not part of the reference's API).
     pub fn as_raw(&self) -> *mut sys::mlp_solution {

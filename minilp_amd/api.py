@@ -71,6 +71,11 @@ class MlpTableauInfo(C.Structure):  # include/minilp_hip.h: mlp_tableau_info (on
                 ("bytes", C.c_double), ("device_ms", C.c_double)]
 
 
+class MlpGmiInfo(C.Structure):  # include/minilp_hip.h: mlp_gmi_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("rows", C.c_uint64), ("skipped_fraction", C.c_uint64), ("skipped_free", C.c_uint64),
+                ("nnz", C.c_uint64), ("batches", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -200,6 +205,12 @@ def lib():
     sig("mlp_solution_tableau_cols", i32, vp, pu64, u64, pdbl, u64)
     sig("mlp_solution_basis_solve", i32, vp, i32, pdbl, u64, u64, pdbl, u64)
     sig("mlp_solution_tableau_info", i32, vp, C.POINTER(MlpTableauInfo))
+    sig("mlp_gmi_info_size", u64)
+    if L.mlp_gmi_info_size() != C.sizeof(MlpGmiInfo):
+        raise ImportError(f"{_SO}: mlp_gmi_info is {L.mlp_gmi_info_size()} bytes, this binding {C.sizeof(MlpGmiInfo)}: rebuild it")
+    pu8 = C.POINTER(C.c_uint8)
+    sig("mlp_solution_add_gmi_cuts", i32, C.POINTER(vp), pu32, u64, pu8, u32, pu8, u64, dbl, C.POINTER(C.c_int32))
+    sig("mlp_solution_gmi_info", i32, vp, C.POINTER(MlpGmiInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -611,6 +622,43 @@ class Solution:
         h = self._take()
         _raise(lib().mlp_solution_add_gomory_cuts(C.byref(h), _p(v, C.c_uint32), len(v)))
         return Solution(h)
+
+    @staticmethod
+    def _int_mask(marks, n):
+        """uint8 mask from a bool mask (taken as it is, whatever its length: the library checks it) or a list of indices < n."""
+        a = np.asarray(marks)
+        if a.dtype == np.bool_:
+            return np.ascontiguousarray(a, dtype=np.uint8).ravel()
+        idx = a.astype(np.int64).ravel()
+        if len(idx) and (idx.min() < 0 or idx.max() >= n):
+            raise InternalError(-1, "add_gmi_cuts: integer mark out of range")
+        m = np.zeros(n, dtype=np.uint8)
+        m[idx] = 1
+        return m
+
+    def add_gmi_cuts(self, vars, integer_vars, integer_constraints=None, away=0.01):
+        """One round of Gomory mixed-integer cuts (mlp_solution_add_gmi_cuts; semantics in the header), one per listed basic integer
+        variable, all from the current basis; feasibility restored once.  integer_vars / integer_constraints: a bool mask or a list of
+        indices (constraints: the slacks that are integer; None: all slacks continuous).  Returns (Solution, status): status[i] is 0
+        emitted, 1 skipped (fraction within away), 2 skipped (free non-basic column in the row)."""
+        v = np.ascontiguousarray(list(vars), dtype=np.int64)
+        if len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+            raise InternalError(-1, "add_gmi_cuts: variable out of range")
+        v = v.astype(np.uint32)
+        vm = self._int_mask(integer_vars, self.num_vars)
+        cm = None if integer_constraints is None else self._int_mask(integer_constraints, self.num_constraints)
+        status = np.zeros(len(v), dtype=np.int32)
+        h = self._take()
+        _raise(lib().mlp_solution_add_gmi_cuts(C.byref(h), _p(v, C.c_uint32), len(v), _p(vm, C.c_uint8), len(vm),
+                                               None if cm is None else _p(cm, C.c_uint8), 0 if cm is None else len(cm), float(away),
+                                               _p(status, C.c_int32)))
+        return Solution(h), status
+
+    def gmi_info(self):
+        """Counters of the last add_gmi_cuts call (mlp_gmi_info) as a dict."""
+        r = MlpGmiInfo()
+        _raise(lib().mlp_solution_gmi_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpGmiInfo._fields_}
 
     def cut_info(self):
         """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""

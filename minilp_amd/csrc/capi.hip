@@ -22,6 +22,7 @@ struct mlp_solution {
     Engine::RangingInfo ranging;  // of the last mlp_solution_cost_ranging / mlp_solution_rhs_ranging call
     Engine::CutInfo cuts;         // of the last mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts call
     Engine::TableauInfo tableau;  // of the last tableau call
+    Engine::GmiInfo gmi;          // of the last mlp_solution_add_gmi_cuts call
     std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
     std::vector<uint32_t> tab_indices;
     std::vector<double> tab_values;
@@ -575,6 +576,42 @@ int mlp_solution_tableau_info(const mlp_solution* s, mlp_tableau_info* out) {
     });
 }
 uint64_t mlp_tableau_info_size(void) { return (uint64_t)sizeof(mlp_tableau_info); }
+
+// ---- a round of Gomory mixed-integer cuts (gmi.inc)
+int mlp_solution_add_gmi_cuts(mlp_solution** s, const uint32_t* vars, uint64_t n, const uint8_t* var_is_int, uint32_t num_vars,
+                              const uint8_t* con_is_int, uint64_t num_constraints, double away, int32_t* status_out) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        Engine* e = (*s)->eng;
+        if (n && !vars) throw MlpError(MLP_EINVAL, "add_gmi_cuts: NULL variable list");
+        if (num_vars != (uint32_t)e->num_vars || (num_vars && !var_is_int)) throw MlpError(MLP_EINVAL, "add_gmi_cuts: var_is_int must have num_vars entries");
+        if (con_is_int && num_constraints != (uint64_t)e->num_constraints())
+            throw MlpError(MLP_EINVAL, "add_gmi_cuts: con_is_int must have num_constraints entries");
+        if (!(away > 0.0 && away <= 0.5)) throw MlpError(MLP_EINVAL, "add_gmi_cuts: away must be in (0, 0.5]");
+        std::vector<int> v;
+        for (uint64_t i = 0; i < n; ++i) {  // (each index is checked as it is read, nothing is sized by n)
+            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "add_gmi_cuts: variable out of range");
+            v.push_back((int)vars[i]);
+        }
+        (*s)->cuts = Engine::CutInfo();
+        (*s)->gmi = Engine::GmiInfo();
+        if (n == 0) return;
+        e->pivot_budget = -1;
+        stale(*s);
+        e->add_gmi_cuts(v, var_is_int, con_is_int, away, status_out, (*s)->cuts, (*s)->gmi);
+    }));
+}
+int mlp_solution_gmi_info(const mlp_solution* s, mlp_gmi_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / gmi info");
+        std::memset(out, 0, sizeof(*out));
+        const Engine::GmiInfo& g = s->gmi;
+        out->requests = g.requests; out->rows = g.rows; out->skipped_fraction = g.skipped_fraction; out->skipped_free = g.skipped_free;
+        out->nnz = g.nnz; out->batches = g.batches; out->bytes = g.bytes; out->device_ms = g.device_ms;
+    });
+}
+uint64_t mlp_gmi_info_size(void) { return (uint64_t)sizeof(mlp_gmi_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

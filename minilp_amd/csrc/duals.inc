@@ -174,8 +174,8 @@ __global__ void __launch_bounds__(BLK) k_du_reduced(DevView v, DualsBufs b) {
     }
     du_block_write(a, b.bpart + (size_t)blockIdx.x * 8);
 }
-// Row activities over the CSR (structural entries): s0 = b . y, mx0 = max violation of the row against its slack's bounds
-// (slack = rhs - activity must lie in [lo_s, hi_s]).
+// Row activities over the CSR (every entry but the row's own slack: a cut row taken from the tableau has terms on the slacks of other
+// rows): s0 = b . y, mx0 = max violation of the row against its slack's bounds (slack = rhs - activity must lie in [lo_s, hi_s]).
 template <int G>
 __global__ void __launch_bounds__(BLK) k_du_rows(DevView v, DualsBufs b) {
     const int i = (blockIdx.x * BLK + threadIdx.x) / G;
@@ -187,7 +187,7 @@ __global__ void __launch_bounds__(BLK) k_du_rows(DevView v, DualsBufs b) {
         const int end = v.csr_ptr[i + 1];
         for (int e = v.csr_ptr[i] + gl; e < end; e += G) {
             const int col = v.csr_col[e];
-            if (col < b.nv) acc += v.csr_val[e] * du_x(v, col);
+            if (col != b.nv + i) acc += v.csr_val[e] * du_x(v, col);
         }
     }
     acc = group_sum<G>(acc);

@@ -169,6 +169,16 @@ public:
     };
     void add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gomory = false);
     void add_gomory_cuts(const std::vector<int>& vars, CutInfo& info);  // the cut of add_gomory_cut for every listed (basic) variable
+    // A round of Gomory mixed-integer cuts (gmi.inc; include/minilp_hip.h mlp_solution_add_gmi_cuts): one cut per listed
+    // basic integer variable, all from the basis the call finds, appended through add_constraints.  var_is_int: num_vars marks;
+    // con_is_int: num_constraints() marks of the slacks, or nullptr (all slacks continuous); status_out: vars.size() codes (0 emitted,
+    // 1 skipped: fraction within away, 2 skipped: free non-basic column in the row), or nullptr.
+    struct GmiInfo {
+        uint64_t requests = 0, rows = 0, skipped_fraction = 0, skipped_free = 0, nnz = 0, batches = 0;
+        double bytes = 0, device_ms = 0;
+    };
+    void add_gmi_cuts(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, double away, int32_t* status_out,
+                      CutInfo& info, GmiInfo& gmi);
     double get_value(int var);                                              // solver.rs:371-376
     void get_values(double* out, int n);
     double cur_obj_val();                                                   // solver.rs:51
@@ -559,12 +569,15 @@ private:
     // FTRAN / BTRAN of rhs; a request with req < 0 is answered by the caller
     void tab_dense(int op, const std::vector<int>& req, const double* rhs, double* out, TableauInfo& info);
     int tab_internal_col(uint64_t col, const char* what) const;
-    // sparse rows out of dense blocks [N][RG_BATCH] for the basic positions pos, RG_BATCH at a time (gomory: f = floor(alpha) - alpha with
-    // right-hand sides and, if kept, the primal edge norms; else alpha itself); emit gets each batch as the host read it back
+    // sparse rows out of dense blocks [N][RG_BATCH] for the basic positions pos, RG_BATCH at a time; emit gets each batch as the host read
+    // it back.  mode 0: alpha itself (tableau rows); 1: Gomory, f = floor(alpha) - alpha with right-hand sides and, if kept, the primal
+    // edge norms; 2: Gomory mixed-integer, as 1 with the coefficients of gmi.inc and a status per request (gmi_mask: the integrality
+    // marks by variable on the device)
     struct RowBatch {
         int nreq;           // rows of this batch
         const int* len;     // [RG_BATCH] terms of each row
-        const double* rhs;  // [RG_BATCH] right-hand sides (gomory)
+        const double* rhs;  // [RG_BATCH] right-hand sides (modes 1, 2)
+        const int* status;  // [RG_BATCH] mode 2: 0 emitted, 1 / 2 skipped (a skipped row has no terms); else nullptr
         const int* col;     // the rows, request-major, each sorted by variable of [A | I]
         const double* val;
     };
@@ -572,7 +585,8 @@ private:
         size_t nbat = 0, ncnt = 0, nnz = 0;  // batches, counters per batch (RG_BATCH * cut_segments(N)), terms emitted
         double device_ms = 0;                // HIP events around the launches
     };
-    RowBatches sparse_row_batches(const std::vector<int>& pos, bool gomory, const std::function<void(size_t, const RowBatch&)>& emit);
+    RowBatches sparse_row_batches(const std::vector<int>& pos, int mode, const std::function<void(size_t, const RowBatch&)>& emit,
+                                  const uint8_t* gmi_mask = nullptr, double gmi_away = 0.0);
 };
 
 // ---- MPS (mps.rs) on the host side of the product

@@ -2974,12 +2974,13 @@ struct TabEvents {  // (destroyed on every way out, a throwing HIPCHECK included
     }
 };
 }  // namespace
-// Sparse rows out of dense blocks [N][RG_BATCH], batch by batch: the host side that add_gomory_cuts and tableau_rows share.  Per batch of at
-// most RG_BATCH basic positions: phase 1 (gomory: launch_cut_generate, else launch_tab_rows) forms the rows of B^-1, the dense block, the
-// scanned offsets, the row lengths and the right-hand sides; the host reads back the lengths; launch_cut_fill writes the rows
+// Sparse rows out of dense blocks [N][RG_BATCH], batch by batch: the host side that add_gomory_cuts, add_gmi_cuts and tableau_rows share.  Per
+// batch of at most RG_BATCH basic positions: phase 1 (mode 0 launch_tab_rows, 1 launch_cut_generate, 2 launch_gmi_generate) forms the rows
+// of B^-1, the dense block, the scanned offsets, the row lengths and the right-hand sides (mode 2: and the statuses); the host reads back
+// the lengths; launch_cut_fill writes the rows
 // (request-major, each sorted by variable), and the host reads back O(nnz of the rows).  The caller has called pull_ctl() and sync_view().
-Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, bool gomory,
-                                              const std::function<void(size_t, const RowBatch&)>& emit) {
+Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int mode, const std::function<void(size_t, const RowBatch&)>& emit,
+                                              const uint8_t* gmi_mask, double gmi_away) {
     const DevView& dv = hview;
     const Geom g = geom();
     constexpr int R = RG_BATCH;
@@ -3005,6 +3006,14 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, bool 
     RangingBufs b{};
     b.blk = blk.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
     b.N = N; b.nv = num_vars; b.k = fac_on_ ? 0 : k_; b.fac = fac_on_ ? 1 : 0;
+    DevBuf<double> gf0, gpart;
+    DevBuf<int> gflag;  // skip, free flag, status: RG_BATCH each
+    GmiBufs gb{};
+    if (mode == 2) {
+        gf0.ensure(R, 0, st); gpart.ensure(out.ncnt + 8, 0, st); gflag.ensure(3 * R, 0, st);
+        gb.mask = gmi_mask; gb.f0 = gf0.p; gb.skip = gflag.p; gb.freef = gflag.p + R; gb.status = gflag.p + 2 * R; gb.part = gpart.p;
+        gb.away = gmi_away;
+    }
     TabEvents e0, e1;
     std::vector<int> hc;
     std::vector<double> hv;
@@ -3012,11 +3021,14 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, bool 
         const int nreq = (int)std::min<size_t>(R, pos.size() - q * R);
         b.req = req.p + q * R;
         HIPCHECK(hipEventRecord(e0.e[0], st));
-        (gomory ? launch_cut_generate : launch_tab_rows)(dv, g, b, nreq, hreq.data() + q * R, dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
+        if (mode == 2) launch_gmi_generate(dv, g, b, gb, nreq, hreq.data() + q * R, dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
+        else (mode == 1 ? launch_cut_generate : launch_tab_rows)(dv, g, b, nreq, hreq.data() + q * R, dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
         HIPCHECK(hipEventRecord(e0.e[1], st));
         HIPCHECK(hipGetLastError());
         int hlen[R];
         double hrhs[R];
+        int hstatus[R];
+        if (mode == 2) HIPCHECK(hipMemcpyAsync(hstatus, gb.status, sizeof(hstatus), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipMemcpyAsync(hlen, len.p, sizeof(hlen), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipMemcpyAsync(hrhs, rhs.p, sizeof(hrhs), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
@@ -3024,7 +3036,7 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, bool 
         for (int r = 0; r < R; ++r) total += (size_t)hlen[r];
         ocol.ensure(total + 8, 0, st); oval.ensure(total + 8, 0, st);
         HIPCHECK(hipEventRecord(e1.e[0], st));
-        launch_cut_fill(dv, dense.p, N, off.p, ocol.p, oval.p, gomory && enable_pse, st);
+        launch_cut_fill(dv, dense.p, N, off.p, ocol.p, oval.p, mode != 0 && enable_pse, st);
         HIPCHECK(hipEventRecord(e1.e[1], st));
         HIPCHECK(hipGetLastError());
         hc.resize(total);
@@ -3039,7 +3051,7 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, bool 
         HIPCHECK(hipEventElapsedTime(&ms1, e1.e[0], e1.e[1]));
         out.device_ms += (double)ms0 + (double)ms1;
         out.nnz += total;
-        emit(q, RowBatch{nreq, hlen, hrhs, hc.data(), hv.data()});
+        emit(q, RowBatch{nreq, hlen, hrhs, mode == 2 ? hstatus : nullptr, hc.data(), hv.data()});
     }
     return out;
 }
@@ -3067,7 +3079,7 @@ void Engine::add_gomory_cuts(const std::vector<int>& vars, CutInfo& info) {
     constexpr int R = RG_BATCH;
     const int m = m_, N = N_;
     std::vector<Constraint> cuts(vars.size());
-    const RowBatches rb = sparse_row_batches(pos, true, [&](size_t q, const RowBatch& bt) {
+    const RowBatches rb = sparse_row_batches(pos, 1, [&](size_t q, const RowBatch& bt) {
         size_t at = 0;
         for (int r = 0; r < bt.nreq; ++r) {  // rows are request-major, each sorted by variable
             Constraint& c = cuts[q * R + r];
@@ -3090,6 +3102,77 @@ void Engine::add_gomory_cuts(const std::vector<int>& vars, CutInfo& info) {
                  + (double)vars.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * cut_nnz;
     info.device_ms = ms_total;
     info.wall_ms += (now_s() - t0) * 1e3;
+    add_constraints(std::move(cuts), info, true);
+}
+
+// One round of Gomory mixed-integer cuts (gmi.inc; semantics in include/minilp_hip.h), ALL taken from the basis the call finds: the host
+// side of add_gomory_cuts with the integrality marks by variable sent up once, a status per request read back with the row lengths,
+// and the skipped requests left out of the append (they take no constraint number).
+void Engine::add_gmi_cuts(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, double away,
+                          int32_t* status_out, CutInfo& info, GmiInfo& gmi) {
+    const double t0 = now_s();
+    if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_gmi_cuts: model not solved (solver.rs:555-556)");
+    if (!(away > 0.0 && away <= 0.5)) throw MlpError(-1, "add_gmi_cuts: away must be in (0, 0.5]");
+    std::vector<int> pos(vars.size());
+    {
+        std::vector<int> sorted(vars);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "add_gmi_cuts: duplicate variable");
+    }
+    for (size_t t = 0; t < vars.size(); ++t) {
+        if (vars[t] < 0 || vars[t] >= num_vars) throw MlpError(-1, "add_gmi_cuts: variable out of range");
+        if (!var_is_int[vars[t]]) throw MlpError(-1, "add_gmi_cuts: variable is not marked integer");
+        if (h_var_loc[vars[t]] < 0) throw MlpError(-1, "add_gmi_cuts: variable is not basic");
+        pos[t] = h_var_loc[vars[t]];
+    }
+    gmi.requests = vars.size();
+    if (vars.empty()) return;
+    constexpr int R = RG_BATCH;
+    const int m = m_, N = N_;
+    std::vector<uint8_t> mask((size_t)N, 0);  // by variable: the structural variables, then the slack of every row
+    for (int j = 0; j < num_vars; ++j) mask[j] = var_is_int[j] ? 1 : 0;
+    if (con_is_int)
+        for (size_t c = 0; c < h_cons_row.size(); ++c)
+            if (h_cons_row[c] >= 0) mask[(size_t)num_vars + h_cons_row[c]] = con_is_int[c] ? 1 : 0;
+    ensure_beta();  // (before the edge norms are fed)
+    pull_ctl();     // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    DevBuf<uint8_t> dmask;
+    dmask.upload(mask, st);
+    std::vector<Constraint> cuts;
+    const RowBatches rb = sparse_row_batches(pos, 2, [&](size_t q, const RowBatch& bt) {
+        size_t at = 0;
+        for (int r = 0; r < bt.nreq; ++r) {  // rows are request-major, each sorted by variable; a skipped request has no terms
+            const int stt = bt.status[r];
+            if (status_out) status_out[q * R + r] = stt;
+            if (stt == 0) {
+                Constraint c;
+                c.op = 1;
+                c.rhs = bt.rhs[r];
+                c.idx.assign(bt.col + at, bt.col + at + bt.len[r]);
+                c.val.assign(bt.val + at, bt.val + at + bt.len[r]);
+                cuts.push_back(std::move(c));  // (a cut whose terms all vanish reads 0 <= -1: add_constraints reports Infeasible)
+            } else {
+                (stt == 1 ? gmi.skipped_fraction : gmi.skipped_free) += 1;
+            }
+            at += (size_t)bt.len[r];
+        }
+    }, dmask.p, away);
+    // algorithmic bytes: those of the Gomory generation, plus per batch the classification of every column (flags, value, mark: 10
+    // bytes), the clear pass over the block's flags, and the partial right-hand sides (written, then read)
+    const double nz = (double)h_rcol.size();
+    const int J = fac_on_ || hview.lrJ ? h_ctl->nlow : 0;
+    gmi.rows = cuts.size();
+    gmi.nnz = rb.nnz;
+    gmi.batches = rb.nbat;
+    gmi.bytes = (double)rb.nbat * (16.0 * (double)m * R + nz * (12.0 + 8.0 * R) + 24.0 * (double)N * R + 14.0 * N + 28.0 * (double)rb.ncnt)
+                + (double)vars.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * (double)rb.nnz;
+    gmi.device_ms = rb.device_ms;
+    info.batches = rb.nbat;
+    info.bytes = gmi.bytes;
+    info.device_ms = rb.device_ms;
+    info.wall_ms += (now_s() - t0) * 1e3;
+    if (cuts.empty()) return;  // every request skipped: the solution is as the call found it
     add_constraints(std::move(cuts), info, true);
 }
 
@@ -4072,7 +4155,7 @@ void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_
     for (int j = 0; j < num_vars; ++j) col_of_var[j] = (uint32_t)j;
     for (size_t c = 0; c < h_cons_row.size(); ++c)
         if (h_cons_row[c] >= 0) col_of_var[(size_t)num_vars + h_cons_row[c]] = (uint32_t)(num_vars + c);
-    const RowBatches rb = sparse_row_batches(pos, false, [&](size_t q, const RowBatch& bt) {
+    const RowBatches rb = sparse_row_batches(pos, 0, [&](size_t q, const RowBatch& bt) {
         size_t at = 0;
         for (int r = 0; r < bt.nreq; ++r) {  // rows are request-major, each sorted by variable
             for (int e = 0; e < bt.len[r]; ++e) {

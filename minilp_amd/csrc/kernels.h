@@ -590,6 +590,21 @@ int cut_segments(int N);
 void launch_cut_generate(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* fd, int* cnt,
                          int* off, int* sums, int* len, double* rhs, hipStream_t st);
 void launch_cut_fill(const DevView& dv, const double* fd, int N, const int* off, int* ocol, double* oval, bool gamma, hipStream_t st);
+// a round of Gomory mixed-integer cuts (gmi.inc), one batch: launch_gmi_generate is launch_cut_generate with the stored coefficients of
+// the GMI cut in the dense block cd[N][RG_BATCH], rhs = -1 + sum c_j xN_j, and a status per request (0 emitted, 1 skipped: fraction
+// within away, 2 skipped: free non-basic column in the row; a skipped request has length 0 and a zero block column); phase 2 is
+// launch_cut_fill on cd.  Reads the solver state; writes only these buffers.
+struct GmiBufs {
+    const uint8_t* mask;  // N: 1 = integer column (structural variables, then the slacks by row)
+    double* f0;           // RG_BATCH: fraction of xB_p
+    int* skip;            // RG_BATCH: 1 = fraction within away (or an empty place of the batch)
+    int* freef;           // RG_BATCH: 1 = a free non-basic column has |alpha| > EPS
+    double* part;         // RG_BATCH * cut_segments(N): partial right-hand sides per (request, segment)
+    int* status;          // RG_BATCH
+    double away;
+};
+void launch_gmi_generate(const DevView& dv, const Geom& g, const RangingBufs& b, const GmiBufs& gb, int nreq, const int* h_req,
+                         double* cd, int* cnt, int* off, int* sums, int* len, double* rhs, hipStream_t st);
 // reading the tableau of the current basis (tableau.inc): batches of RG_BATCH rows of B^-1 A as sparse rows, and batches of RG_BATCH solves
 // with dense right-hand sides.  X, Y: [m][RG_BATCH], entry i of all right-hand sides in one 128-byte line.  Reads the solver state; writes
 // only these buffers.
