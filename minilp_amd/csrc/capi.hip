@@ -645,7 +645,6 @@ void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     o->factor_switches = t.fac_switches; o->factor_bump = t.fac_bump; o->factor_bump_max = t.fac_bump_max;
 }
 void mlp_solution_reset_stats(mlp_solution* s) {
-    guarded([&] { s->eng->resolve_events(); });
     s->eng->stats = Stats();
     s->eng->restart_sampling();  // profile mode: the next batch is a sampled one, so a short timed region still has samples
 }

@@ -3,13 +3,14 @@
 //
 // Cut generation, RG_BATCH = 16 Gomory cuts per pass over A:
 //   the 16 rows of B^-1 come from launch_ranging_block (ranging.inc: explicit inverse with its pending terms applied, singleton
-//   positions, compact factor) as ONE block rho[m][16]; k_cut_sweep is the pass of k_rg_cost_sweep over A's CSC with
-//   f = floor(alpha) - alpha at its end instead of a ratio test, written as a dense block f[N][16] BY VARIABLE (basic variables: 0);
+//   positions, compact factor) as ONE block rho[m][16]; k_cut_sweep is one pass over A's CSC: alpha = csc_block_dot (ranging.inc, the
+//   accumulator of every batched pass), then f = floor(alpha) - alpha written as a dense block f[N][16] BY VARIABLE (basic variables: 0);
 //   then the non-zero f become sparse rows on the device: a count pass (per segment of CUT_SEG variables and request), an exclusive
 //   scan in request-major order, and an ordered fill.  A thread owns one (segment, request) pair in both passes and walks its
 //   segment in variable order, so every cut comes out sorted by variable with no atomics, no ballots and no LDS, bit-identically
 //   from run to run and whatever else the batch holds (alpha_j[r] is summed in storage order, then by the xor tree of the lane
-//   group: its value depends on request r alone).  Side-effect free like ranging: only the private buffers are written.
+//   group: its value depends on request r alone).  The launches of phase 1 are launch_rows_generate (tableau.inc), shared with the
+//   tableau rows and the GMI round.  Side-effect free like ranging: only the private buffers are written.
 // Row append (R = 1 is Solution::add_constraint): one re-layout of the CSC for R new rows (they are the last R rows, so every column
 //   gains its new entries at its end, in row order): per-column counts from the R sorted rows, a scan, one copy kernel.
 
@@ -17,59 +18,44 @@ constexpr int CUT_SEG = 16;  // variables per (segment, request) thread of the c
 
 template <int R, int G>
 __global__ void __launch_bounds__(BLK) k_cut_sweep(DevView v, RangingBufs b, double* __restrict__ fd) {
-    const int var = (blockIdx.x * BLK + threadIdx.x) / G;
+    const int var = (int)(((long)blockIdx.x * BLK + threadIdx.x) / G);
     const int gl = threadIdx.x & (G - 1);
     double acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0;
     const bool live = var < b.N && v.var_loc[var] < 0;
-    if (live) {
-        const int end = v.csc_ptr[var + 1];
-        for (int e = v.csc_ptr[var] + gl; e < end; e += G) {
-            const double a = v.csc_val[e];
-            const double2* rr = reinterpret_cast<const double2*>(b.blk + (size_t)v.csc_row[e] * R);
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const double2 t = rr[r >> 1];
-                acc[r] += a * t.x;
-                acc[r + 1] += a * t.y;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+    csc_block_dot<R, G>(v, b.blk, live, var, gl, acc);
     if (var < b.N && gl == 0) {
-        double2* out = reinterpret_cast<double2*>(fd + (size_t)var * R);
 #pragma unroll
-        for (int r = 0; r < R; r += 2) {
-            double2 t;
-            t.x = live ? floor(acc[r]) - acc[r] : 0.0;
-            t.y = live ? floor(acc[r + 1]) - acc[r + 1] : 0.0;
-            out[r >> 1] = t;
-        }
+        for (int r = 0; r < R; ++r) acc[r] = live ? floor(acc[r]) - acc[r] : 0.0;
+        store_block_row<R>(fd + (size_t)var * R, acc);
     }
 }
-// count / fill: thread (segment, request); MODE 0 counts the non-zero f of its segment, MODE 1 writes them behind off[r * nseg + seg]
+// count / fill: thread (segment, request); MODE 0 counts the non-zero f of its segment, MODE 1 writes them behind off[r * nseg + seg],
+// MODE 2 (GMI) counts and leaves the segment's share of the right-hand side, sum f_j xN_j in variable order, in part
 template <int R, int MODE>
 __global__ void __launch_bounds__(BLK) k_cut_compact(const double* __restrict__ fd, int N, int nseg, int* __restrict__ cnt,
-                                                     const int* __restrict__ off, int* __restrict__ ocol, double* __restrict__ oval) {
+                                                     const int* __restrict__ off, int* __restrict__ ocol, double* __restrict__ oval,
+                                                     const int* __restrict__ var_loc, const double* __restrict__ xN,
+                                                     double* __restrict__ part) {
     const long gid = (long)blockIdx.x * BLK + threadIdx.x;
     const int r = (int)(gid % R);
     const long seg = gid / R;
     if (seg >= nseg) return;
     const int v0 = (int)seg * CUT_SEG, v1 = min(N, v0 + CUT_SEG);
-    int pos = MODE ? off[(size_t)r * nseg + seg] : 0;
+    int pos = MODE == 1 ? off[(size_t)r * nseg + seg] : 0;
+    double s = 0.0;
     for (int j = v0; j < v1; ++j) {
         const double f = fd[(size_t)j * R + r];
-        if (f != 0.0) {  // exact zeros carry no information
-            if (MODE) {
+        if (f != 0.0) {  // exact zeros carry no information (only a non-basic column holds a non-zero)
+            if (MODE == 1) {
                 ocol[pos] = j;
                 oval[pos] = f;
             }
+            if (MODE == 2) s += f * xN[-1 - var_loc[j]];
             ++pos;
         }
     }
-    if (!MODE) cnt[(size_t)r * nseg + seg] = pos;
+    if (MODE != 1) cnt[(size_t)r * nseg + seg] = pos;
+    if (MODE == 2) part[(size_t)r * nseg + seg] = s;
 }
 // row lengths and right-hand sides of the batch: len[r] from the scanned offsets, rhs[r] = floor(xB_p) - xB_p
 template <int R>
@@ -103,28 +89,13 @@ __global__ void __launch_bounds__(BLK) k_cut_gamma(DevView v, const double* __re
 
 int cut_segments(int N) { return (N + CUT_SEG - 1) / CUT_SEG; }
 
-// phase 1 of a batch: block of rows, sweep, count, scan, heads.  cnt / off: RG_BATCH * cut_segments(N) ints each, sums: the scan's
-// scratch (its last element is the total), len / rhs: RG_BATCH each.
-void launch_cut_generate(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* fd, int* cnt,
-                         int* off, int* sums, int* len, double* rhs, hipStream_t st) {
-    constexpr int R = RG_BATCH;
-    launch_ranging_block(dv, g, b, 0, nreq, h_req, st);
-    const int nb = ranging_blocks(g, 0, b.N);
-    LANES_SWITCH(g.lanes,
-                 hipLaunchKernelGGL((k_cut_sweep<R, 4>), dim3(nb), dim3(BLK), 0, st, dv, b, fd),
-                 hipLaunchKernelGGL((k_cut_sweep<R, 16>), dim3(nb), dim3(BLK), 0, st, dv, b, fd),
-                 hipLaunchKernelGGL((k_cut_sweep<R, 64>), dim3(nb), dim3(BLK), 0, st, dv, b, fd));
-    const int nseg = cut_segments(b.N);
-    const long n = (long)R * nseg;
-    hipLaunchKernelGGL((k_cut_compact<R, 0>), dim3(blocks_for(n)), dim3(BLK), 0, st, fd, b.N, nseg, cnt, nullptr, nullptr, nullptr);
-    launch_exclusive_scan(cnt, off, n, sums, st);
-    hipLaunchKernelGGL(k_cut_heads<R>, dim3(1), dim3(64), 0, st, dv, b.req, off, sums + (n + SCAN_TILE - 1) / SCAN_TILE, nseg, len, rhs);
-}
+// (phase 1 of a batch — block of rows, sweep, count, scan, heads — is launch_rows_generate, tableau.inc)
 // phase 2: the ordered fill (ocol / oval hold the batch's total), and the edge norms when the primal norms are kept
 void launch_cut_fill(const DevView& dv, const double* fd, int N, const int* off, int* ocol, double* oval, bool gamma, hipStream_t st) {
     constexpr int R = RG_BATCH;
     const int nseg = cut_segments(N);
-    hipLaunchKernelGGL((k_cut_compact<R, 1>), dim3(blocks_for((long)R * nseg)), dim3(BLK), 0, st, fd, N, nseg, nullptr, off, ocol, oval);
+    hipLaunchKernelGGL((k_cut_compact<R, 1>), dim3(blocks_for((long)R * nseg)), dim3(BLK), 0, st, fd, N, nseg, nullptr, off, ocol, oval,
+                       nullptr, nullptr, nullptr);
     if (gamma) hipLaunchKernelGGL(k_cut_gamma<R>, dim3(blocks_for(N)), dim3(BLK), 0, st, dv, fd, N);
 }
 

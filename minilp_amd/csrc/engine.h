@@ -236,7 +236,6 @@ public:
     void enable_sharding(int rank, int world, const char* shm_name, const char* transport_name = nullptr, const void* rccl_id = nullptr);
     static void rccl_unique_id(void* out128);
     bool sharded() const { return shard_world > 1; }
-    bool sharding_live() const { return shard_is_live(); }
 
     int num_vars = 0;
     int direction = 0;
@@ -247,7 +246,6 @@ public:
     int sample_every = 0;  // profile mode: 0 = default cadence (every 8th / 4th batch), 1 = every iteration is a sampled eager one
     std::vector<PivotRecord> trace_log;
     Stats stats;
-    void resolve_events() {}
     uint64_t state(const char* what, double* out, uint64_t cap);
     int m() const { return m_; }
     int total_vars() const { return N_; }
@@ -324,7 +322,6 @@ private:
     DevBuf<FacTailRec> d_fac_tprog;  // the tail of the solves as records: FTRAN | BTRAN, FAC_TAIL_CAP each
     DevBuf<int> d_fac_lev3;   // 3 m: level of a position | level of a row's pivot position | reach of a position
     bool fac_skip_ = true;    // every solve walks only the levels its right-hand side can reach
-    bool fac_flow_ = false;   // (unused: the data-flow walk of round 5 was removed)
     DevBuf<double> d_fac_Wb;   // allocated with the first bump
     bool fac_pair_ = true;                   // the two solves of a stage share one walk over the levels
     int fac_bump_ = 0;
@@ -584,7 +581,10 @@ private:
     struct RowBatches {
         size_t nbat = 0, ncnt = 0, nnz = 0;  // batches, counters per batch (RG_BATCH * cut_segments(N)), terms emitted
         double device_ms = 0;                // HIP events around the launches
+        double bytes = 0;                    // algorithmic bytes of the generation
     };
+    struct ReqContext;  // the padded requests and the private compact-factor vectors of one batched read (engine.hip)
+    std::vector<int> cut_round_positions(const std::vector<int>& vars, const std::string& who, const uint8_t* var_is_int, bool refs) const;
     RowBatches sparse_row_batches(const std::vector<int>& pos, int mode, const std::function<void(size_t, const RowBatch&)>& emit,
                                   const uint8_t* gmi_mask = nullptr, double gmi_away = 0.0);
 };

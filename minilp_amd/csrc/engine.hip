@@ -2126,7 +2126,7 @@ void Engine::fac_fill_view(DevView& v) const {
     v.fac_bar = d_fac_bar.p;
     v.fac_lev_of_pos = d_fac_lev3.p; v.fac_lev_of_row = d_fac_lev3.p ? d_fac_lev3.p + (size_t)std::max(m_, 1) : nullptr;
     v.fac_reach_of_pos = d_fac_lev3.p ? d_fac_lev3.p + 2 * (size_t)std::max(m_, 1) : nullptr;
-    v.fac_skip = fac_skip_ ? 1 : 0; v.fac_flow = fac_flow_ ? 1 : 0;
+    v.fac_skip = fac_skip_ ? 1 : 0;
     v.fac_idx_of_pos = d_fac_lev3.p ? d_fac_lev3.p + 3 * (size_t)std::max(m_, 1) : nullptr;
     v.fac_idx_of_row = d_fac_lev3.p ? d_fac_lev3.p + 4 * (size_t)std::max(m_, 1) : nullptr;
     v.fac_tprog_f = d_fac_tprog.p; v.fac_tprog_b = d_fac_tprog.p ? d_fac_tprog.p + (size_t)std::max(m_, 1) : nullptr;
@@ -2963,19 +2963,75 @@ void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gom
 }
 
 namespace {
-struct TabEvents {  // (destroyed on every way out, a throwing HIPCHECK included)
+struct EventPair {  // (destroyed on every way out, a throwing HIPCHECK included)
     hipEvent_t e[2] = {nullptr, nullptr};
-    TabEvents() {
+    EventPair() {
         for (auto& x : e) HIPCHECK(hipEventCreate(&x));
     }
-    ~TabEvents() {
+    ~EventPair() {
         for (auto& x : e)
             if (x) (void)hipEventDestroy(x);
     }
+    double ms() const {  // between the two records, once the stream has been synchronised
+        float t = 0.0f;
+        HIPCHECK(hipEventElapsedTime(&t, e[0], e[1]));
+        return (double)t;
+    }
 };
 }  // namespace
+// What one call of a batched read holds for its batches (sparse_row_batches, ranging, tab_dense): the requests padded to whole batches of
+// RG_BATCH (-1 at the empty places) with their device copy, the representation of B^-1 the kernels will find and the private vectors of
+// the compact factor's one-solve-per-request path.  The caller has called pull_ctl().
+struct Engine::ReqContext {
+    static constexpr int R = RG_BATCH;
+    const size_t n, nbat;
+    std::vector<int> h;
+    DevBuf<int> d;
+    DevBuf<double> unit, tau;
+    DevBuf<double2> rv;
+    SolveBufs sb{};
+    int N, J;            // total variables; pending rank-1 terms
+    size_t rows_binv;    // stored length of a row / column of B^-1: m (compact factor) or the nucleus size
+    ReqContext(Engine& e, const std::vector<int>& ids, bool on_device = true) : n(ids.size()), nbat((n + R - 1) / R), h(nbat * R, -1) {
+        std::copy(ids.begin(), ids.end(), h.begin());
+        if (on_device) d.upload(h, e.st);
+        const size_t m = (size_t)e.m_;
+        sb.k = e.fac_on_ ? 0 : e.k_;
+        sb.fac = e.fac_on_ ? 1 : 0;
+        if (e.fac_on_) {
+            unit.ensure(m + 1, 0, e.st); tau.ensure(m + 1, 0, e.st); rv.ensure(m + 1, 0, e.st);
+            HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * (m + 1), e.st));
+            HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * (m + 1), e.st));
+        }
+        sb.unit = unit.p; sb.tau = tau.p; sb.rv = rv.p;
+        N = e.N_;
+        J = e.fac_on_ || e.hview.lrJ ? e.h_ctl->nlow : 0;
+        rows_binv = e.fac_on_ ? m : (size_t)e.k_;
+    }
+    int count(size_t q) const { return (int)std::min<size_t>(R, n - q * R); }  // requests of batch q
+    const int* host(size_t q) const { return h.data() + q * R; }
+    const int* dev(size_t q) const { return d.p + q * R; }
+    RangingBufs bufs(size_t q, double* blk) const {  // of batch q, around the caller's block
+        RangingBufs b{};
+        static_cast<SolveBufs&>(b) = sb;
+        b.blk = blk;
+        b.req = d.p ? dev(q) : nullptr;
+        b.N = N;
+        return b;
+    }
+    // Algorithmic bytes the batched reads share.  Per batch: a block of `rows` x R (cleared, then written) and one pass over A (12 bytes
+    // per entry) with a gather of R doubles per entry; per request: the stored row / column of B^-1 the block is made of with its
+    // pending terms (the compact factor's solve is counted as its pending terms).
+    double block_bytes(size_t rows) const { return (double)nbat * 16.0 * (double)rows * R + (double)n * (8.0 + 16.0 * J) * (double)rows_binv; }
+    double pass_bytes(double nz) const { return (double)nbat * nz * (12.0 + 8.0 * R); }
+    // ... and of the sparse rows: per batch the dense block [N][R] (written once, read by the count and by the fill) with `per_var` bytes
+    // per variable and `per_cnt` per counter on top; the emitted rows (12 bytes per term)
+    double rows_bytes(size_t m, double nz, double per_var, double per_cnt, size_t ncnt, size_t nnz) const {
+        return block_bytes(m) + pass_bytes(nz) + (double)nbat * (24.0 * (double)N * R + per_var * N + per_cnt * (double)ncnt) + 12.0 * (double)nnz;
+    }
+};
 // Sparse rows out of dense blocks [N][RG_BATCH], batch by batch: the host side that add_gomory_cuts, add_gmi_cuts and tableau_rows share.  Per
-// batch of at most RG_BATCH basic positions: phase 1 (mode 0 launch_tab_rows, 1 launch_cut_generate, 2 launch_gmi_generate) forms the rows
+// batch of at most RG_BATCH basic positions: phase 1 (launch_rows_generate, mode = the RowKind) forms the rows
 // of B^-1, the dense block, the scanned offsets, the row lengths and the right-hand sides (mode 2: and the statuses); the host reads back
 // the lengths; launch_cut_fill writes the rows
 // (request-major, each sorted by variable), and the host reads back O(nnz of the rows).  The caller has called pull_ctl() and sync_view().
@@ -2985,27 +3041,16 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int m
     const Geom g = geom();
     constexpr int R = RG_BATCH;
     const int m = m_, N = N_;
+    ReqContext ctx(*this, pos);
     RowBatches out;
-    out.nbat = (pos.size() + R - 1) / R;
-    std::vector<int> hreq(out.nbat * R, -1);
-    for (size_t t = 0; t < pos.size(); ++t) hreq[t] = pos[t];
+    out.nbat = ctx.nbat;
     const int nseg = cut_segments(N);
     out.ncnt = (size_t)R * nseg;
-    DevBuf<double> blk, dense, rhs, oval, unit, tau;
-    DevBuf<double2> rv;
-    DevBuf<int> req, cnt, off, len, ocol, scan;
+    DevBuf<double> blk, dense, rhs, oval;
+    DevBuf<int> cnt, off, len, ocol, scan;
     blk.ensure((size_t)m * R + R, 0, st); dense.ensure((size_t)N * R + R, 0, st); rhs.ensure(R, 0, st); len.ensure(R, 0, st);
     cnt.ensure(out.ncnt + 8, 0, st); off.ensure(out.ncnt + 8, 0, st);
     scan.ensure(out.ncnt / 4096 + 8, 0, st);  // (private: d_scan_tmp is the appends' scratch)
-    req.upload(hreq, st);
-    if (fac_on_) {
-        unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
-        HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
-        HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
-    }
-    RangingBufs b{};
-    b.blk = blk.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
-    b.N = N; b.nv = num_vars; b.k = fac_on_ ? 0 : k_; b.fac = fac_on_ ? 1 : 0;
     DevBuf<double> gf0, gpart;
     DevBuf<int> gflag;  // skip, free flag, status: RG_BATCH each
     GmiBufs gb{};
@@ -3014,15 +3059,13 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int m
         gb.mask = gmi_mask; gb.f0 = gf0.p; gb.skip = gflag.p; gb.freef = gflag.p + R; gb.status = gflag.p + 2 * R; gb.part = gpart.p;
         gb.away = gmi_away;
     }
-    TabEvents e0, e1;
+    EventPair e0, e1;
     std::vector<int> hc;
     std::vector<double> hv;
     for (size_t q = 0; q < out.nbat; ++q) {
-        const int nreq = (int)std::min<size_t>(R, pos.size() - q * R);
-        b.req = req.p + q * R;
+        const int nreq = ctx.count(q);
         HIPCHECK(hipEventRecord(e0.e[0], st));
-        if (mode == 2) launch_gmi_generate(dv, g, b, gb, nreq, hreq.data() + q * R, dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
-        else (mode == 1 ? launch_cut_generate : launch_tab_rows)(dv, g, b, nreq, hreq.data() + q * R, dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
+        launch_rows_generate(dv, g, ctx.bufs(q, blk.p), (RowKind)mode, &gb, nreq, ctx.host(q), dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
         HIPCHECK(hipEventRecord(e0.e[1], st));
         HIPCHECK(hipGetLastError());
         int hlen[R];
@@ -3046,38 +3089,43 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int m
             HIPCHECK(hipMemcpyAsync(hv.data(), oval.p, total * sizeof(double), hipMemcpyDeviceToHost, st));
         }
         HIPCHECK(hipStreamSynchronize(st));
-        float ms0 = 0.f, ms1 = 0.f;
-        HIPCHECK(hipEventElapsedTime(&ms0, e0.e[0], e0.e[1]));
-        HIPCHECK(hipEventElapsedTime(&ms1, e1.e[0], e1.e[1]));
-        out.device_ms += (double)ms0 + (double)ms1;
+        out.device_ms += e0.ms() + e1.ms();
         out.nnz += total;
         emit(q, RowBatch{nreq, hlen, hrhs, mode == 2 ? hstatus : nullptr, hc.data(), hv.data()});
     }
+    // algorithmic bytes of the generation (ReqContext::rows_bytes); on top of the dense block, per variable: its flags (4 bytes), and for
+    // the GMI round the classification of every column (flags, value, mark: 10 bytes more); per counter: counts and offsets (12 bytes),
+    // and for the GMI round the clear pass over the block's flags and the partial right-hand sides, written, then read (16 more)
+    out.bytes = ctx.rows_bytes((size_t)m, (double)h_rcol.size(), mode == 2 ? 14.0 : 4.0, mode == 2 ? 28.0 : 12.0, out.ncnt, out.nnz);
     return out;
 }
 
 // One round of Gomory cuts (solver.rs:440-460 per cut), ALL taken from the basis the call finds: RG_BATCH rows of B^-1 per block,
 // one pass over A per block, the cuts emitted as sparse rows on the device (cuts.inc).  The host reads back the row lengths and the
 // sparse rows (O(nnz of the cuts)); no dense tableau row crosses.
+// What a round of cuts asks of its variables, Gomory or GMI: no duplicates, in range, (GMI: marked integer,) basic.  Returns their basic
+// positions; refs: the reference's lines as the messages of the Gomory round quote them.
+std::vector<int> Engine::cut_round_positions(const std::vector<int>& vars, const std::string& who, const uint8_t* var_is_int, bool refs) const {
+    std::vector<int> sorted(vars);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, who + ": duplicate variable");
+    std::vector<int> pos(vars.size());
+    for (size_t t = 0; t < vars.size(); ++t) {
+        if (vars[t] < 0 || vars[t] >= num_vars) throw MlpError(-1, who + ": variable out of range" + (refs ? " (lib.rs:420)" : ""));
+        if (var_is_int && !var_is_int[vars[t]]) throw MlpError(-1, who + ": variable is not marked integer");
+        if (h_var_loc[vars[t]] < 0) throw MlpError(-1, who + ": variable is not basic" + (refs ? " (solver.rs:458)" : ""));
+        pos[t] = h_var_loc[vars[t]];
+    }
+    return pos;
+}
 void Engine::add_gomory_cuts(const std::vector<int>& vars, CutInfo& info) {
     const double t0 = now_s();
     if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_gomory_cuts: model not solved (solver.rs:555-556)");
-    std::vector<int> pos(vars.size());
-    {
-        std::vector<int> sorted(vars);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "add_gomory_cuts: duplicate variable");
-    }
-    for (size_t t = 0; t < vars.size(); ++t) {
-        if (vars[t] < 0 || vars[t] >= num_vars) throw MlpError(-1, "add_gomory_cuts: variable out of range (lib.rs:420)");
-        if (h_var_loc[vars[t]] < 0) throw MlpError(-1, "add_gomory_cuts: variable is not basic (solver.rs:458)");
-        pos[t] = h_var_loc[vars[t]];
-    }
+    const std::vector<int> pos = cut_round_positions(vars, "add_gomory_cuts", nullptr, true);
     ensure_beta();  // (before the edge norms are fed)
     pull_ctl();     // (k_ and the count of pending terms as the device holds them)
     sync_view();
     constexpr int R = RG_BATCH;
-    const int m = m_, N = N_;
     std::vector<Constraint> cuts(vars.size());
     const RowBatches rb = sparse_row_batches(pos, 1, [&](size_t q, const RowBatch& bt) {
         size_t at = 0;
@@ -3090,17 +3138,9 @@ void Engine::add_gomory_cuts(const std::vector<int>& vars, CutInfo& info) {
             at += (size_t)bt.len[r];
         }
     });
-    const size_t nbat = rb.nbat, ncnt = rb.ncnt;
-    const double ms_total = rb.device_ms, cut_nnz = (double)rb.nnz;
-    // algorithmic bytes of the generation, per batch: the block (cleared, then written), one pass over A (12 bytes per entry) with
-    // a gather of R doubles per entry, the dense block of f (written once, read by the count and by the fill), the per-variable
-    // flags, the counts and offsets; per request the stored rows the block is made of; and the emitted rows (12 bytes per term)
-    const double nz = (double)h_rcol.size();
-    const int J = fac_on_ || hview.lrJ ? h_ctl->nlow : 0;
-    info.batches = nbat;
-    info.bytes = (double)nbat * (16.0 * (double)m * R + nz * (12.0 + 8.0 * R) + 24.0 * (double)N * R + 4.0 * N + 12.0 * (double)ncnt)
-                 + (double)vars.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * cut_nnz;
-    info.device_ms = ms_total;
+    info.batches = rb.nbat;
+    info.bytes = rb.bytes;
+    info.device_ms = rb.device_ms;
     info.wall_ms += (now_s() - t0) * 1e3;
     add_constraints(std::move(cuts), info, true);
 }
@@ -3113,22 +3153,11 @@ void Engine::add_gmi_cuts(const std::vector<int>& vars, const uint8_t* var_is_in
     const double t0 = now_s();
     if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_gmi_cuts: model not solved (solver.rs:555-556)");
     if (!(away > 0.0 && away <= 0.5)) throw MlpError(-1, "add_gmi_cuts: away must be in (0, 0.5]");
-    std::vector<int> pos(vars.size());
-    {
-        std::vector<int> sorted(vars);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "add_gmi_cuts: duplicate variable");
-    }
-    for (size_t t = 0; t < vars.size(); ++t) {
-        if (vars[t] < 0 || vars[t] >= num_vars) throw MlpError(-1, "add_gmi_cuts: variable out of range");
-        if (!var_is_int[vars[t]]) throw MlpError(-1, "add_gmi_cuts: variable is not marked integer");
-        if (h_var_loc[vars[t]] < 0) throw MlpError(-1, "add_gmi_cuts: variable is not basic");
-        pos[t] = h_var_loc[vars[t]];
-    }
+    const std::vector<int> pos = cut_round_positions(vars, "add_gmi_cuts", var_is_int, false);
     gmi.requests = vars.size();
     if (vars.empty()) return;
     constexpr int R = RG_BATCH;
-    const int m = m_, N = N_;
+    const int N = N_;
     std::vector<uint8_t> mask((size_t)N, 0);  // by variable: the structural variables, then the slack of every row
     for (int j = 0; j < num_vars; ++j) mask[j] = var_is_int[j] ? 1 : 0;
     if (con_is_int)
@@ -3158,15 +3187,10 @@ void Engine::add_gmi_cuts(const std::vector<int>& vars, const uint8_t* var_is_in
             at += (size_t)bt.len[r];
         }
     }, dmask.p, away);
-    // algorithmic bytes: those of the Gomory generation, plus per batch the classification of every column (flags, value, mark: 10
-    // bytes), the clear pass over the block's flags, and the partial right-hand sides (written, then read)
-    const double nz = (double)h_rcol.size();
-    const int J = fac_on_ || hview.lrJ ? h_ctl->nlow : 0;
     gmi.rows = cuts.size();
     gmi.nnz = rb.nnz;
     gmi.batches = rb.nbat;
-    gmi.bytes = (double)rb.nbat * (16.0 * (double)m * R + nz * (12.0 + 8.0 * R) + 24.0 * (double)N * R + 14.0 * N + 28.0 * (double)rb.ncnt)
-                + (double)vars.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * (double)rb.nnz;
+    gmi.bytes = rb.bytes;
     gmi.device_ms = rb.device_ms;
     info.batches = rb.nbat;
     info.bytes = gmi.bytes;
@@ -3582,7 +3606,7 @@ Engine* Engine::clone() {
     HIPCHECK(hipStreamSynchronize(s2));
     std::memcpy(e->h_ctl, h_ctl, sizeof(Ctl));
     e->values_dirty = true;
-    e->fac_mode = fac_mode; e->fac_J_ = fac_J_; e->fac_period_ = fac_period_; e->fac_period_auto_ = fac_period_auto_; e->fac_auto_cap_ = fac_auto_cap_; e->fac_bump_max_ = fac_bump_max_; e->fac_sb_max_ = fac_sb_max_; e->fac_sb_from_ = fac_sb_from_; e->fac_pair_ = fac_pair_; e->fac_skip_ = fac_skip_; e->fac_flow_ = fac_flow_;
+    e->fac_mode = fac_mode; e->fac_J_ = fac_J_; e->fac_period_ = fac_period_; e->fac_period_auto_ = fac_period_auto_; e->fac_auto_cap_ = fac_auto_cap_; e->fac_bump_max_ = fac_bump_max_; e->fac_sb_max_ = fac_sb_max_; e->fac_sb_from_ = fac_sb_from_; e->fac_pair_ = fac_pair_; e->fac_skip_ = fac_skip_;
     e->cold_start_ = false;  // a clone continues a solve (branch-and-bound: clone + fix_var): warm-start policy, no eager capture of the long graph
     if (fac_on_ && !e->fac_enter())  // (a fresh peel of the same basis: the same operator, no pending terms)
         throw MlpError(-3, "clone: the basis of a solution on the compact factor must peel");
@@ -3762,22 +3786,17 @@ void Engine::compute_duals(Duals& out) {
     b.y = y.p; b.cb = cb.p; b.rv = rv.p; b.tK = tK.p; b.part = part.p; b.lrh = lrh.p; b.r = r.p; b.pi = pi.p;
     b.bpart = bpart.p; b.rpart = rpart.p; b.cert = cert.p; b.rhs = rhs.p;
     b.N = N; b.nv = nv; b.k = k; b.fac = fac_on_ ? 1 : 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHECK(hipEventCreate(&e0));
-    HIPCHECK(hipEventCreate(&e1));
-    HIPCHECK(hipEventRecord(e0, st));
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
     launch_duals(dv, g, b, st);
-    HIPCHECK(hipEventRecord(e1, st));
+    HIPCHECK(hipEventRecord(ev.e[1], st));
     HIPCHECK(hipGetLastError());
     std::vector<double> hr((size_t)N), hpi((size_t)m), hc(16);
     if (N) HIPCHECK(hipMemcpyAsync(hr.data(), r.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
     if (m) HIPCHECK(hipMemcpyAsync(hpi.data(), pi.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(hc.data(), cert.p, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    float ms = 0.0f;
-    HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    const double ms = ev.ms();
     // user's objective sense: a Maximize problem is solved as the minimisation of -c (lib.rs:235-238)
     const double sg = direction == 1 ? -1.0 : 1.0;
     out.r.resize((size_t)nv);
@@ -3807,10 +3826,6 @@ void Engine::compute_duals(Duals& out) {
 }
 
 // Basis status of every structural variable and every constraint (= its slack); a constraint without terms has no row: basic.
-static inline int32_t nb_status_of(uint8_t f) {
-    if ((f & NB_FIXED) || ((f & NB_AT_MIN) && (f & NB_AT_MAX))) return 4;
-    return (f & NB_AT_MIN) ? 1 : ((f & NB_AT_MAX) ? 2 : 3);
-}
 void Engine::basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons) {
     if (sharded()) throw MlpError(-1, "the basis status is not available on a sharded solution");
     pull_ctl();
@@ -3898,56 +3913,37 @@ void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du
                 return ksr[a.first] < ksr[b.first];
             });
         }
-        const size_t nbat = (solve.size() + R - 1) / R;
-        std::vector<int> hreq(nbat * R, -1);
-        for (size_t q = 0; q < solve.size(); ++q) hreq[q] = solve[q].first;
+        std::vector<int> ids(solve.size());
+        for (size_t q = 0; q < solve.size(); ++q) ids[q] = solve[q].first;
+        ReqContext ctx(*this, ids);
+        const size_t nbat = ctx.nbat;
         const int nblk = ranging_blocks(g, kind, N);
         const size_t rows = (kind == 0 || fac_on_) ? (size_t)m : (size_t)k;
-        DevBuf<double> blk, r, part, out, unit, tau;
-        DevBuf<double2> rv;
-        DevBuf<int> req;
+        DevBuf<double> blk, r, part, out;
         blk.ensure(rows * R + R, 0, st); part.ensure((size_t)nblk * 2 * R, 0, st); out.ensure(nbat * 2 * R, 0, st);
-        req.upload(hreq, st);
         if (kind == 0) r.upload(du.r_int, st);
-        if (fac_on_) {
-            unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
-            HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
-            HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
-        }
-        RangingBufs b{};
-        b.blk = blk.p; b.r = r.p; b.part = part.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
-        b.N = N; b.nv = num_vars; b.k = k; b.fac = fac_on_ ? 1 : 0;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        HIPCHECK(hipEventCreate(&e0));
-        HIPCHECK(hipEventCreate(&e1));
-        HIPCHECK(hipEventRecord(e0, st));
+        EventPair ev;
+        HIPCHECK(hipEventRecord(ev.e[0], st));
         for (size_t q = 0; q < nbat; ++q) {
-            b.req = req.p + q * R;
-            b.out = out.p + q * 2 * R;
-            launch_ranging_batch(dv, g, b, kind, (int)std::min<size_t>(R, solve.size() - q * R), hreq.data() + q * R, st);
+            RangingBufs b = ctx.bufs(q, blk.p);
+            b.r = r.p; b.part = part.p; b.out = out.p + q * 2 * R;
+            launch_ranging_batch(dv, g, b, kind, ctx.count(q), ctx.host(q), st);
         }
-        HIPCHECK(hipEventRecord(e1, st));
+        HIPCHECK(hipEventRecord(ev.e[1], st));
         HIPCHECK(hipGetLastError());
         std::vector<double> ho(nbat * 2 * R);
         HIPCHECK(hipMemcpyAsync(ho.data(), out.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
-        float ms = 0.0f;
-        HIPCHECK(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         for (size_t q = 0; q < solve.size(); ++q) {
             const size_t t = solve[q].second;
             L[t] = cur[t] + ho[2 * q];
             H[t] = cur[t] + ho[2 * q + 1];
         }
-        // algorithmic bytes per batch: the block (cleared, then written), the stored rows / columns it is made of with the pending
-        // terms, one pass over A (12 bytes per entry) with a gather of R doubles per entry, the per-position vectors of the rhs pull
-        const double nz = (double)h_rcol.size();
-        const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
+        // algorithmic bytes: the block and the pass over A (ReqContext), and per batch the per-variable vectors of the cost sweep / the
+        // per-position vectors of the rhs pull
         info.batches = nbat;
-        info.bytes = (double)nbat * (16.0 * (double)rows * R + nz * (12.0 + 8.0 * R) + (kind == 1 ? 40.0 * m : 13.0 * N))
-                     + (double)solve.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k);
-        info.device_ms = ms;
+        info.bytes = ctx.block_bytes(rows) + ctx.pass_bytes((double)h_rcol.size()) + (double)nbat * (kind == 1 ? 40.0 * m : 13.0 * N);
+        info.device_ms = ev.ms();
     }
     // user's objective sense: a Maximize problem is solved as the minimisation of -c, so its cost range is [-hi, -lo]; rhs ranges keep their sign
     const bool turn = kind == 0 && direction == 1;
@@ -3996,38 +3992,29 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
         if (req[t] >= 0 || op >= 3) solve.push_back(t);
     info.solves = solve.size();
     if (solve.empty() || m == 0) return;
-    const size_t nbat = (solve.size() + R - 1) / R;
-    std::vector<int> hreq(nbat * R, -1);
+    std::vector<int> ids(solve.size(), -1);
     if (op < 3)
-        for (size_t q = 0; q < solve.size(); ++q) hreq[q] = req[solve[q]];
-    DevBuf<double> X, Y, XK, YK, part, lrh, unit, tau;
-    DevBuf<double2> rv;
-    DevBuf<int> dreq;
+        for (size_t q = 0; q < solve.size(); ++q) ids[q] = req[solve[q]];
+    ReqContext ctx(*this, ids, op < 3);
+    const size_t nbat = ctx.nbat;
+    DevBuf<double> X, Y, XK, YK, part, lrh;
     const size_t blk = (size_t)m * R + R;
     Y.ensure(blk, 0, st);
     if (op != 0) X.ensure(blk, 0, st);
-    if (op < 3) dreq.upload(hreq, st);
-    if (fac_on_) {
-        unit.ensure((size_t)m + 1, 0, st); tau.ensure((size_t)m + 1, 0, st); rv.ensure((size_t)m + 1, 0, st);
-        HIPCHECK(hipMemsetAsync(rv.p, 0, sizeof(double2) * ((size_t)m + 1), st));
-        HIPCHECK(hipMemsetAsync(tau.p, 0, sizeof(double) * ((size_t)m + 1), st));
-    } else if (k > 0 && op != 0) {
+    if (!fac_on_ && k > 0 && op != 0) {
         XK.ensure((size_t)k * R + R, 0, st); YK.ensure((size_t)k * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
         if (op == 4) part.ensure((size_t)tab_wt_stripes(k) * k * R + R, 0, st);
     }
     TabBufs b{};
-    b.X = X.p; b.Y = Y.p; b.XK = XK.p; b.YK = YK.p; b.part = part.p; b.lrh = lrh.p; b.unit = unit.p; b.tau = tau.p; b.rv = rv.p;
-    b.k = k; b.fac = fac_on_ ? 1 : 0;
-    RangingBufs rb{};  // op 0: the block of rows IS the result
-    rb.blk = Y.p; rb.unit = unit.p; rb.tau = tau.p; rb.rv = rv.p;
-    rb.N = N_; rb.nv = num_vars; rb.k = k; rb.fac = b.fac;
+    static_cast<SolveBufs&>(b) = ctx.sb;
+    b.X = X.p; b.Y = Y.p; b.XK = XK.p; b.YK = YK.p; b.part = part.p; b.lrh = lrh.p;
     std::vector<int> row_of_cons(h_cons_row);
     std::vector<double> hX, hY(blk);
     if (op >= 3) hX.resize(blk);
-    TabEvents ev;
+    EventPair ev;
     double ms_total = 0.0;
     for (size_t q = 0; q < nbat; ++q) {
-        const int nreq = (int)std::min<size_t>(R, solve.size() - q * R);
+        const int nreq = ctx.count(q);
         if (op >= 3) {  // the right-hand sides of the batch, interleaved
             std::fill(hX.begin(), hX.end(), 0.0);
             for (int r = 0; r < nreq; ++r) {
@@ -4042,20 +4029,17 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
             HIPCHECK(hipMemcpyAsync(X.p, hX.data(), sizeof(double) * (size_t)m * R, hipMemcpyHostToDevice, st));
         }
         HIPCHECK(hipEventRecord(ev.e[0], st));
-        if (op == 0) {
-            rb.req = dreq.p + q * R;
-            launch_ranging_block(dv, g, rb, 0, nreq, hreq.data() + q * R, st);
+        if (op == 0) {  // the block of rows IS the result
+            launch_ranging_block(dv, g, ctx.bufs(q, Y.p), 0, nreq, ctx.host(q), st);
         } else {
-            if (op < 3) launch_tab_rhs(dv, b, dreq.p + q * R, nreq, op, st);
+            if (op < 3) launch_tab_rhs(dv, b, ctx.dev(q), nreq, op, st);
             launch_tab_solve(dv, g, b, op == 4 ? 1 : 0, nreq, st);
         }
         HIPCHECK(hipEventRecord(ev.e[1], st));
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipMemcpyAsync(hY.data(), Y.p, sizeof(double) * (size_t)m * R, hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
-        float ms = 0.0f;
-        HIPCHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-        ms_total += (double)ms;
+        ms_total += ev.ms();
         for (int r = 0; r < nreq; ++r) {
             double* dst = out + solve[q * R + r] * out_stride;
             if (by_cons_out) {
@@ -4068,15 +4052,14 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
     // algorithmic bytes per batch: the blocks X and Y (cleared / written, read), one read of W0 (8 k^2) with its pending terms, the
     // gathered nucleus parts, one pass over the basis columns of A for the F product (12 bytes per entry + a gather of R doubles);
     // rows of B^-1: as the ranging block; compact factor: counted as its pending terms per solve, like the ranging
-    const double nz = (double)h_rcol.size();
-    const int J = fac_on_ || dv.lrJ ? h_ctl->nlow : 0;
+    const int J = ctx.J;
     if (op == 0)
-        info.bytes = (double)nbat * 16.0 * (double)m * R + (double)solve.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k);
+        info.bytes = ctx.block_bytes((size_t)m);
     else if (fac_on_)
         info.bytes = (double)nbat * 32.0 * (double)m * R + (double)solve.size() * (24.0 + 16.0 * J) * m;
     else
         info.bytes = (double)nbat * (32.0 * (double)m * R + 8.0 * (double)k * k + 16.0 * J * k + 32.0 * (double)k * R
-                                     + (op == 4 ? 16.0 * (double)tab_wt_stripes(k) * k * R : 0.0) + nz * (12.0 + 8.0 * R));
+                                     + (op == 4 ? 16.0 * (double)tab_wt_stripes(k) * k * R : 0.0)) + ctx.pass_bytes((double)h_rcol.size());
     info.batches = nbat;
     info.device_ms = ms_total;
 }
@@ -4150,7 +4133,7 @@ void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_
     if (cols.empty()) return;
     sync_view();
     constexpr int R = RG_BATCH;
-    const int m = m_, N = N_;
+    const int N = N_;
     std::vector<uint32_t> col_of_var((size_t)N);  // variable of [A | I] -> user column (monotone: rows are numbered in constraint order)
     for (int j = 0; j < num_vars; ++j) col_of_var[j] = (uint32_t)j;
     for (size_t c = 0; c < h_cons_row.size(); ++c)
@@ -4166,16 +4149,9 @@ void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_
             indptr[q * R + r + 1] = indices.size();
         }
     });
-    const size_t nbat = rb.nbat, ncnt = rb.ncnt;
-    const double ms_total = rb.device_ms;
-    // algorithmic bytes: as the cut generation (the block, one pass over A with a gather of R doubles per entry, the dense block of
-    // alpha written once and read by the count and by the fill, counts and offsets, the emitted rows)
-    const double nz = (double)h_rcol.size();
-    const int J = fac_on_ || hview.lrJ ? h_ctl->nlow : 0;
-    info.batches = nbat;
+    info.batches = rb.nbat;
     info.nnz = indices.size();
-    info.bytes = (double)nbat * (16.0 * (double)m * R + nz * (12.0 + 8.0 * R) + 24.0 * (double)N * R + 4.0 * N + 12.0 * (double)ncnt)
-                 + (double)cols.size() * (8.0 + 16.0 * J) * (fac_on_ ? m : k_) + 12.0 * (double)indices.size();
-    info.device_ms = ms_total;
+    info.bytes = rb.bytes;
+    info.device_ms = rb.device_ms;
 }
 }  // namespace mlp

@@ -141,6 +141,12 @@ struct alignas(64) MailRec {
 
 // Non-basic flags (solver.rs:66-70 NonBasicVarState + nb_var_is_fixed)
 constexpr uint8_t NB_AT_MIN = 1, NB_AT_MAX = 2, NB_FIXED = 4;
+// status of the variable at a non-basic place, from its flags (engine: lo == hi sets both bound flags): 1 at lower, 2 at upper,
+// 3 at neither bound, 4 fixed
+__host__ __device__ inline int nb_status_of(uint8_t f) {
+    if ((f & NB_FIXED) || ((f & NB_AT_MIN) && (f & NB_AT_MAX))) return 4;
+    return (f & NB_AT_MIN) ? 1 : ((f & NB_AT_MAX) ? 2 : 3);
+}
 
 // Everything the kernels need (passed by value); it changes only when a buffer is re-allocated
 // (growth of W, add_constraint), which also invalidates the captured graphs.
@@ -366,7 +372,7 @@ struct DevView {
     int* fac_lev_of_pos;     // m: level of a position (-1: bump)
     int* fac_lev_of_row;     // m: level of the position that pivots on a row (-1: bump row)
     int* fac_reach_of_pos;   // m: highest level any BTRAN dependent of the position reaches
-    int fac_skip, fac_flow;  // fac_skip: walk only the levels a right-hand side can reach (always on); fac_flow: unused (the data-flow walk of round 5 was removed)
+    int fac_skip, pad6;      // fac_skip: walk only the levels a right-hand side can reach (always on)
     // the single-workgroup tail of the solves (factor.inc): place of a position / of a row's pivot position in fac_items (-1: bump),
     // and the tail's items as fixed-size records in walking order (one per direction)
     int* fac_idx_of_pos; int* fac_idx_of_row;
@@ -560,20 +566,25 @@ void launch_duals(const DevView& dv, const Geom& g, const DualsBufs& b, hipStrea
 int duals_var_blocks(const Geom& g, int N);
 int duals_row_blocks(const Geom& g);
 int duals_wt_stripes(int k);
-// cost / rhs ranging of the current basis (ranging.inc): batches of RG_BATCH rows / columns of B^-1 and one ratio-test pass per batch;
-// reads the solver state, writes only these buffers
+// The batched reads of the current basis (ranging.inc, cuts.inc, gmi.inc, tableau.inc) serve their requests RG_BATCH at a time; all of them
+// read the solver state and write only the buffers named here.
 constexpr int RG_BATCH = 16;  // requests per batch (the sweep kernels take it as a template parameter)
-struct RangingBufs {
+// what every one of them needs of the representation of B^-1: the nucleus size and, for the compact factor (one level-scheduled solve
+// per request), the private vectors of that solve
+struct SolveBufs {
+    double* unit;       // m: compact factor: right-hand side of one solve
+    double* tau;        // m: compact factor: private result of the FTRAN
+    double2* rv;        // m: compact factor: private rv of the BTRAN
+    int k, fac;         // nucleus size (explicit inverse), compact factor active
+};
+// cost / rhs ranging (ranging.inc): batches of rows / columns of B^-1 and one ratio-test pass per batch
+struct RangingBufs : SolveBufs {
     double* blk;        // cost: rho[m][RG_BATCH] by row; rhs: H[k][RG_BATCH] by nucleus slot (compact factor: H[m][RG_BATCH] by position)
     const int* req;     // RG_BATCH per batch: cost: basic position of a request; rhs: its row (-1: empty place of the batch)
     const double* r;    // N: reduced costs of the duals read (internal minimisation sense; basic: exactly 0)
     double* part;       // blocks x 2 RG_BATCH: per-block (max of the lower ratios, min of the upper ratios) per request
     double* out;        // 2 RG_BATCH per batch: (delta-, delta+) per request
-    double* unit;       // m: compact factor: right-hand side e_p / e_row of one solve
-    double* tau;        // m: compact factor: private result of the FTRAN
-    double2* rv;        // m: compact factor: private rv of the BTRAN
-    int N, nv;          // total / structural variables
-    int k, fac;         // nucleus size (explicit inverse), compact factor active
+    int N;              // total variables
 };
 // one batch of at most RG_BATCH requests (nreq of them; req / out already point at the batch); kind 0: cost ranging, 1: rhs ranging;
 // h_req: the batch's requests as the host holds them (the compact factor runs one solve per request)
@@ -581,19 +592,18 @@ void launch_ranging_batch(const DevView& dv, const Geom& g, const RangingBufs& b
 int ranging_blocks(const Geom& g, int kind, int N);  // workgroups of the batch's sweep (= rows of RangingBufs.part)
 // the block of one batch alone (rows / nucleus columns of B^-1 of its requests), without the ratio-test pass
 void launch_ranging_block(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st);
-// a round of Gomory cuts (cuts.inc), one batch of at most RG_BATCH basic positions: launch_cut_generate forms the rows of B^-1
-// (b.blk, b.req, compact factor: b.unit / b.tau / b.rv as for ranging), the dense block fd[N][RG_BATCH] of f = floor(alpha) - alpha by
-// variable, the scanned offsets off[RG_BATCH * cut_segments(N)] (cnt: same size, sums: the scan's scratch), the row lengths len and the
-// right-hand sides rhs (RG_BATCH each); launch_cut_fill writes the rows (request-major, sorted by variable) into ocol / oval and, if
-// asked, adds f^2 to the primal edge norms.  Reads the solver state; writes only these buffers (and gamma).
-int cut_segments(int N);
-void launch_cut_generate(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* fd, int* cnt,
-                         int* off, int* sums, int* len, double* rhs, hipStream_t st);
-void launch_cut_fill(const DevView& dv, const double* fd, int N, const int* off, int* ocol, double* oval, bool gamma, hipStream_t st);
-// a round of Gomory mixed-integer cuts (gmi.inc), one batch: launch_gmi_generate is launch_cut_generate with the stored coefficients of
-// the GMI cut in the dense block cd[N][RG_BATCH], rhs = -1 + sum c_j xN_j, and a status per request (0 emitted, 1 skipped: fraction
-// within away, 2 skipped: free non-basic column in the row; a skipped request has length 0 and a zero block column); phase 2 is
-// launch_cut_fill on cd.  Reads the solver state; writes only these buffers.
+// Sparse rows out of a dense block, one batch of at most RG_BATCH basic positions (tableau.inc, cuts.inc, gmi.inc).  Phase 1,
+// launch_rows_generate: the rows of B^-1 (b.blk, b.req, the SolveBufs part as for ranging), one pass over A that leaves the dense block
+// dense[N][RG_BATCH] by variable, the scanned offsets off[RG_BATCH * cut_segments(N)] (cnt: same size, sums: the scan's scratch), the row
+// lengths len and the right-hand sides rhs (RG_BATCH each).  What the block holds is the kind of row:
+//   ROWS_TABLEAU  alpha itself (basic variables 0, a requested variable itself exactly 1); rhs: scratch of the shared head kernel
+//   ROWS_GOMORY   f = floor(alpha) - alpha, rhs = floor(xB_p) - xB_p
+//   ROWS_GMI      the stored coefficients of the Gomory mixed-integer cut, rhs = -1 + sum c_j xN_j, and a status per request (0 emitted,
+//                 1 skipped: fraction within away, 2 skipped: free non-basic column in the row; a skipped request has length 0 and a
+//                 zero block column); needs gb
+// Phase 2, launch_cut_fill: the rows (request-major, sorted by variable) into ocol / oval and, if asked, dense^2 added to the primal edge
+// norms (gamma: the only solver state written).
+enum RowKind : int { ROWS_TABLEAU = 0, ROWS_GOMORY = 1, ROWS_GMI = 2 };
 struct GmiBufs {
     const uint8_t* mask;  // N: 1 = integer column (structural variables, then the slacks by row)
     double* f0;           // RG_BATCH: fraction of xB_p
@@ -603,29 +613,21 @@ struct GmiBufs {
     int* status;          // RG_BATCH
     double away;
 };
-void launch_gmi_generate(const DevView& dv, const Geom& g, const RangingBufs& b, const GmiBufs& gb, int nreq, const int* h_req,
-                         double* cd, int* cnt, int* off, int* sums, int* len, double* rhs, hipStream_t st);
-// reading the tableau of the current basis (tableau.inc): batches of RG_BATCH rows of B^-1 A as sparse rows, and batches of RG_BATCH solves
-// with dense right-hand sides.  X, Y: [m][RG_BATCH], entry i of all right-hand sides in one 128-byte line.  Reads the solver state; writes
-// only these buffers.
-struct TabBufs {
+int cut_segments(int N);
+void launch_rows_generate(const DevView& dv, const Geom& g, const RangingBufs& b, RowKind kind, const GmiBufs* gb, int nreq, const int* h_req,
+                          double* dense, int* cnt, int* off, int* sums, int* len, double* rhs, hipStream_t st);
+void launch_cut_fill(const DevView& dv, const double* fd, int N, const int* off, int* ocol, double* oval, bool gamma, hipStream_t st);
+// batches of RG_BATCH solves with dense right-hand sides (tableau.inc).  X, Y: [m][RG_BATCH], entry i of all right-hand sides in one
+// 128-byte line.
+struct TabBufs : SolveBufs {
     double* X;      // right-hand sides: FTRAN by row, BTRAN by position
     double* Y;      // results: FTRAN by position, BTRAN by row
     double* XK;     // [k][RG_BATCH]: FTRAN X_K by column slot; BTRAN T_K = X_K - F^T Y_S by row slot
     double* YK;     // [k][RG_BATCH]: FTRAN W X_K by row slot
     double* part;   // BTRAN: tab_wt_stripes(k) x k x RG_BATCH partial column sums of W0^T T_K
     double* lrh;    // LR_MAX x RG_BATCH: V_j . X_K (FTRAN) / U_j . T_K (BTRAN) of the pending terms
-    double* unit;   // m: compact factor: right-hand side of one solve
-    double* tau;    // m: compact factor: private result of the FTRAN
-    double2* rv;    // m: compact factor: private rv of the BTRAN
-    int k, fac;     // nucleus size (explicit inverse), compact factor active
 };
 int tab_wt_stripes(int k);
-// phase 1 of a batch of tableau rows: the block of rows of B^-1 (b as for launch_cut_generate), the dense block ad[N][RG_BATCH] of alpha by
-// variable (basic variables 0, a requested variable itself exactly 1), the scanned offsets and the row lengths (rhs: scratch of the
-// shared head kernel); phase 2 is launch_cut_fill on ad (no edge norms)
-void launch_tab_rows(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* ad, int* cnt, int* off,
-                     int* sums, int* len, double* rhs, hipStream_t st);
 // X of a batch formed on the device (req: RG_BATCH ints on the device, -1 at empty places): mode 1 unit vectors of rows, 2 columns of [A | I]
 void launch_tab_rhs(const DevView& dv, const TabBufs& b, const int* req, int nreq, int mode, hipStream_t st);
 // one batch of solves: Y = B^-1 X, or transposed Y = B^-T X

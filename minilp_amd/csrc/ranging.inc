@@ -8,19 +8,79 @@
 //   rhs ranging of R rows whose slack is non-basic:  the R columns of B^-1 restricted to the nucleus as H[k][R], then ONE pass by
 //       position that pulls the singleton part h_p = (e - F h_K)_p / D_p per CSR row and runs the ratio tests on (xB, loB, hiB).
 // Side-effect free in the sense of duals.inc: only the private buffers of RangingBufs are written; the pending rank-1 terms of the
-// delayed-update mode are applied, not folded; the compact factor is not re-peeled (one level-scheduled solve per request on a copy of
-// the view with private result vectors, scattered into the same block); Ctl, d, rv and the work vectors are untouched.  No float
-// atomics; every sum has a fixed order that depends on the request alone (never on what else is in the batch, or where), and the
-// reductions across columns / positions are exact minima and maxima: the two numbers of a request are bit-identical whatever the call.
+// delayed-update mode are applied, not folded; the compact factor is not re-peeled (launch_fac_block: one level-scheduled solve per
+// request on a copy of the view with private result vectors, scattered into the same block); Ctl, d, rv and the work vectors are
+// untouched.  The two accumulators of the sweeps — csc_block_dot over a column of A, csr_nucleus_pull over a singleton row — and
+// launch_fac_block are shared with cuts.inc, gmi.inc and tableau.inc.  No float atomics; every sum has a fixed order that depends on
+// the request alone (never on what else is in the batch, or where), and the reductions across columns / positions are exact minima
+// and maxima: the two numbers of a request are bit-identical whatever the call.
 
 constexpr double RG_INF = __builtin_huge_val();
 
-// status of the variable at a non-basic place, from its flags (engine: lo == hi sets both bound flags)
-__device__ __forceinline__ int rg_nb_status(uint8_t f) {
-    if ((f & NB_FIXED) || ((f & NB_AT_MIN) && (f & NB_AT_MAX))) return 4;
-    if (f & NB_AT_MIN) return 1;
-    if (f & NB_AT_MAX) return 2;
-    return 3;
+// ---- the accumulators every batched pass shares (ranging.inc, cuts.inc, gmi.inc, tableau.inc).  Both leave in acc[r], on every lane of
+// the group, a sum whose order depends on the column / row and on G alone: lane gl takes the entries gl, gl + G, ... in storage order
+// into R accumulators (the [..][R] block is read as double2), then the xor tree of the lane group.  They shuffle: every thread of the
+// workgroup calls them, a thread without work with live = false / sg < 0.  Their callers form the thread's column / position in long
+// (the grid may hold more than 2^31 threads) and narrow the quotient, which never passes N, m or k by more than a workgroup: a 64-bit
+// index kept live through the entry loop costs two VGPRs, and k_gmi_sweep / k_tab_b_rhs sit at the 80-register step of the occupancy.
+// the CSC block dot: acc[r] = sum over the entries e of column var of A of a_e * blk[row_e][r]
+template <int R, int G>
+__device__ __forceinline__ void csc_block_dot(const DevView& v, const double* blk, bool live, int var, int gl, double (&acc)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = 0.0;
+    if (live) {
+        const int end = v.csc_ptr[var + 1];
+        for (int e = v.csc_ptr[var] + gl; e < end; e += G) {
+            const double a = v.csc_val[e];
+            const double2* rr = reinterpret_cast<const double2*>(blk + (size_t)v.csc_row[e] * R);
+#pragma unroll
+            for (int r = 0; r < R; r += 2) {
+                const double2 t = rr[r >> 1];
+                acc[r] += a * t.x;
+                acc[r + 1] += a * t.y;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+}
+// the CSR nucleus pull of singleton row sg: acc[r] = sum over the entries e of CSR row sg whose column is a nucleus basic of
+// a_e * blk[slot_e][r] (blk by nucleus slot)
+template <int R, int G>
+__device__ __forceinline__ void csr_nucleus_pull(const DevView& v, const double* blk, int sg, int gl, double (&acc)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = 0.0;
+    if (sg >= 0) {
+        const int end = v.csr_ptr[sg + 1];
+        for (int e = v.csr_ptr[sg] + gl; e < end; e += G) {
+            const int l2 = v.var_loc[v.csr_col[e]];
+            if (l2 < 0) continue;
+            const int s = v.kslot_of_pos[l2];
+            if (s < 0) continue;
+            const double a = v.csr_val[e];
+            const double2* hh = reinterpret_cast<const double2*>(blk + (size_t)s * R);
+#pragma unroll
+            for (int r = 0; r < R; r += 2) {
+                const double2 t = hh[r >> 1];
+                acc[r] += a * t.x;
+                acc[r + 1] += a * t.y;
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+}
+// R values as one row of a [..][R] block (double2 stores: one 128-byte line at R = 16)
+template <int R>
+__device__ __forceinline__ void store_block_row(double* row, const double (&x)[R]) {
+    double2* out = reinterpret_cast<double2*>(row);
+#pragma unroll
+    for (int r = 0; r < R; r += 2) {
+        double2 t;
+        t.x = x[r];
+        t.y = x[r + 1];
+        out[r >> 1] = t;
+    }
 }
 // entry (s, c) of the nucleus inverse with the pending terms applied (term order)
 __device__ __forceinline__ double rg_w(const DevView& v, int nlow, int s, int c) {
@@ -75,15 +135,21 @@ __global__ void __launch_bounds__(BLK) k_rg_cols(DevView v, RangingBufs b) {
         if (c >= 0) b.blk[(size_t)s * R + r] = rg_w(v, nlow, s, c);
     }
 }
-// compact factor: right-hand side of one solve, and its result into column r of the block
+// compact factor: right-hand side of one solve (the unit vector of idx, or column r of a block X[m][R]), and its result (dir 0: the
+// FTRAN's tau, 1: the BTRAN's v) into column r of the block
 __global__ void __launch_bounds__(BLK) k_rg_unit(double* u, int m, int idx) {
     const int i = blockIdx.x * BLK + threadIdx.x;
     if (i < m) u[i] = i == idx ? 1.0 : 0.0;
 }
 template <int R>
-__global__ void __launch_bounds__(BLK) k_rg_take(RangingBufs b, int m, int r, int kind) {
+__global__ void __launch_bounds__(BLK) k_rg_col(const double* __restrict__ X, double* __restrict__ u, int m, int r) {
+    const long step = (long)gridDim.x * BLK;
+    for (long i = (long)blockIdx.x * BLK + threadIdx.x; i < m; i += step) u[i] = X[(size_t)i * R + r];
+}
+template <int R>
+__global__ void __launch_bounds__(BLK) k_rg_take(SolveBufs s, double* __restrict__ blk, int m, int r, int dir) {
     const int i = blockIdx.x * BLK + threadIdx.x;
-    if (i < m) b.blk[(size_t)i * R + r] = kind == 0 ? b.rv[i].y : b.tau[i];
+    if (i < m) blk[(size_t)i * R + r] = dir ? s.rv[i].y : s.tau[i];
 }
 
 __device__ __forceinline__ double rg_wave_min(double x) {
@@ -118,37 +184,23 @@ __device__ void rg_block_write(const double (&lo)[R], const double (&hi)[R], dou
 }
 
 // Cost ranging: one pass over A's CSC for the whole batch (G lanes per column as k_du_reduced).  Basic columns are skipped; for a
-// non-basic column i, alpha_i[r] = rho_r . a_i (R accumulators per lane, storage order, then the xor tree of the lane group) and
+// non-basic column i, alpha_i[r] = rho_r . a_i (csc_block_dot) and
 //   at lower: alpha > 0 bounds delta+ by r_i / alpha, alpha < 0 bounds delta- ;   at upper: the mirror image;
 //   non-basic at neither bound: alpha != 0 pins both at 0;   fixed: imposes nothing.
 // |alpha| <= EPS counts as zero; a reduced cost of the wrong sign is clamped to 0.
 template <int R, int G>
 __global__ void __launch_bounds__(BLK) k_rg_cost_sweep(DevView v, RangingBufs b) {
-    const int var = (blockIdx.x * BLK + threadIdx.x) / G;
+    const int var = (int)(((long)blockIdx.x * BLK + threadIdx.x) / G);
     const int gl = threadIdx.x & (G - 1);
     double acc[R], lo[R], hi[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) { acc[r] = 0.0; lo[r] = -RG_INF; hi[r] = RG_INF; }
+    for (int r = 0; r < R; ++r) { lo[r] = -RG_INF; hi[r] = RG_INF; }
     int loc = 0;
     if (var < b.N) loc = v.var_loc[var];
     const bool live = var < b.N && loc < 0;
-    if (live) {
-        const int end = v.csc_ptr[var + 1];
-        for (int e = v.csc_ptr[var] + gl; e < end; e += G) {
-            const double a = v.csc_val[e];
-            const double2* rr = reinterpret_cast<const double2*>(b.blk + (size_t)v.csc_row[e] * R);
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const double2 t = rr[r >> 1];
-                acc[r] += a * t.x;
-                acc[r + 1] += a * t.y;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+    csc_block_dot<R, G>(v, b.blk, live, var, gl, acc);
     if (live && gl == 0) {
-        const int stt = rg_nb_status(v.nbflags[-1 - loc]);
+        const int stt = nb_status_of(v.nbflags[-1 - loc]);
         if (stt != 4) {
             const double ri = b.r[var];
             const double num = stt == 1 ? fmax(ri, 0.0) : fmin(ri, 0.0);
@@ -170,40 +222,22 @@ __global__ void __launch_bounds__(BLK) k_rg_cost_sweep(DevView v, RangingBufs b)
     rg_block_write<R>(lo, hi, b.part + (size_t)blockIdx.x * 2 * R);
 }
 // Rhs ranging: one pass by basic position (G lanes per position).  A nucleus position reads h = H[slot]; a singleton position pulls
-// h_p = ((row_r == its row) - sum_e A[sg_p, e] H[slot(e)]) / D_p over the nucleus columns of its CSR row (storage order, xor tree) — a
+// h_p = ((row_r == its row) - sum_e A[sg_p, e] H[slot(e)]) / D_p over the nucleus columns of its CSR row (csr_nucleus_pull) — a
 // pull per row, no push, no atomics.  Then x_B + delta h must stay in [loB, hiB]; |h| <= EPS counts as zero; x_B a hair outside a bound
 // is clamped onto it.
 template <int R, int G>
 __global__ void __launch_bounds__(BLK) k_rg_rhs_pull(DevView v, RangingBufs b) {
-    const int p = (blockIdx.x * BLK + threadIdx.x) / G;
+    const int p = (int)(((long)blockIdx.x * BLK + threadIdx.x) / G);
     const int gl = threadIdx.x & (G - 1);
     double acc[R], lo[R], hi[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) { acc[r] = 0.0; lo[r] = -RG_INF; hi[r] = RG_INF; }
+    for (int r = 0; r < R; ++r) { lo[r] = -RG_INF; hi[r] = RG_INF; }
     int ks = 0, sg = -1;
     if (p < v.m && !b.fac) {
         ks = v.kslot_of_pos[p];
-        if (ks < 0) {
-            sg = v.srow_of_pos[p];
-            const int end = v.csr_ptr[sg + 1];
-            for (int e = v.csr_ptr[sg] + gl; e < end; e += G) {
-                const int l2 = v.var_loc[v.csr_col[e]];
-                if (l2 < 0) continue;
-                const int s = v.kslot_of_pos[l2];
-                if (s < 0) continue;
-                const double a = v.csr_val[e];
-                const double2* hh = reinterpret_cast<const double2*>(b.blk + (size_t)s * R);
-#pragma unroll
-                for (int r = 0; r < R; r += 2) {
-                    const double2 t = hh[r >> 1];
-                    acc[r] += a * t.x;
-                    acc[r + 1] += a * t.y;
-                }
-            }
-        }
+        if (ks < 0) sg = v.srow_of_pos[p];
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+    csr_nucleus_pull<R, G>(v, b.blk, sg, gl, acc);
     if (p < v.m && gl == 0) {
         const double x = v.xB[p];
         const double up = fmax(v.hiB[p] - x, 0.0), dn = fmin(v.loB[p] - x, 0.0);
@@ -246,21 +280,34 @@ __global__ void __launch_bounds__(BLK) k_rg_final(RangingBufs b, int nb) {
 static inline int rg_lanes(const Geom& g) { return g.lanes <= 4 ? 4 : g.lanes <= 16 ? 16 : 64; }
 int ranging_blocks(const Geom& g, int kind, int N) { return blocks_for((long)(kind == 0 ? N : g.m) * rg_lanes(g)); }
 
-// the block of one batch: rows (kind 0) / nucleus columns (kind 1) of B^-1 of its requests (cuts.inc takes its rows here too)
+static inline int tab_grid(long n) { return (int)std::min<long>(blocks_for(n), 8192); }  // (the kernels behind it stride)
+// Compact factor: "solve these requests into the columns of a block".  One level-scheduled solve per request (pending terms included) on a
+// copy of the view with private result vectors; dir 0: blk[:, r] = B^-1 x_r (by position), 1: B^-T x_r (by row); x_r = column r of
+// X[m][R], or, without X, the unit vector of h_req[r].  k_fac_solve with src 2 / dst 1 reads its right-hand side from `unit` alone, walks
+// every level, and its epilogue stores all m entries of tau / rv.y: nothing of one solve is left for the next, so rv and tau need no clear
+// between the solves (rv.x is neither written nor read here).
+static void launch_fac_block(const DevView& dv, const Geom& g, const SolveBufs& s, int dir, int nreq, const int* h_req, const double* X,
+                             double* blk, hipStream_t st) {
+    constexpr int R = RG_BATCH;
+    const int m = g.m;
+    DevView pv = dv;
+    pv.rv = s.rv;
+    pv.tau = s.tau;
+    for (int r = 0; r < nreq; ++r) {
+        if (X) hipLaunchKernelGGL(k_rg_col<R>, dim3(tab_grid(m)), dim3(BLK), 0, st, X, s.unit, m, r);
+        else hipLaunchKernelGGL(k_rg_unit, dim3(blocks_for(m)), dim3(BLK), 0, st, s.unit, m, h_req[r]);
+        launch_fac_solve(pv, g, dir, 2, 1, s.unit, 1, st);
+        hipLaunchKernelGGL(k_rg_take<R>, dim3(blocks_for(m)), dim3(BLK), 0, st, s, blk, m, r, dir);
+    }
+}
+// the block of one batch: rows (kind 0) / nucleus columns (kind 1) of B^-1 of its requests (the sparse rows take their rows here too)
 void launch_ranging_block(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st) {
     constexpr int R = RG_BATCH;
     const int m = g.m;
     const size_t rows = (kind == 0 || b.fac) ? (size_t)m : (size_t)b.k;
     if (rows) (void)hipMemsetAsync(b.blk, 0, sizeof(double) * rows * R, st);
-    if (b.fac) {  // one level-scheduled solve per request (pending terms included), private result vectors
-        DevView pv = dv;
-        pv.rv = b.rv;
-        pv.tau = b.tau;
-        for (int r = 0; r < nreq; ++r) {
-            hipLaunchKernelGGL(k_rg_unit, dim3(blocks_for(m)), dim3(BLK), 0, st, b.unit, m, h_req[r]);
-            launch_fac_solve(pv, g, kind == 0 ? 1 : 0, 2, 1, b.unit, 1, st);
-            hipLaunchKernelGGL(k_rg_take<R>, dim3(blocks_for(m)), dim3(BLK), 0, st, b, m, r, kind);
-        }
+    if (b.fac) {
+        launch_fac_block(dv, g, b, kind == 0 ? 1 : 0, nreq, h_req, nullptr, b.blk, st);
     } else if (kind == 0) {
         hipLaunchKernelGGL(k_rg_rows<R>, dim3(blocks_for(b.k), nreq), dim3(BLK), 0, st, dv, b);
     } else if (b.k > 0) {

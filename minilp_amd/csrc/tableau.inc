@@ -3,16 +3,19 @@
 //
 // Requests are served in batches of R = RG_BATCH that share one pass over the large operand:
 //   rows of B^-1:      the block rho[m][R] of launch_ranging_block (ranging.inc), read back as it is;
-//   tableau rows:      the same block, then k_tab_sweep — the pass of k_cut_sweep over A's CSC that keeps alpha itself in a dense block
-//                      [N][R] by variable (basic variables: 0, the requested variable itself: exactly 1) — and the count / scan / fill of
-//                      cuts.inc, which turn the block into sparse rows sorted by variable;
+//   tableau rows:      the same block, then k_tab_sweep — one pass over A's CSC, alpha = csc_block_dot (ranging.inc) kept as it is in a
+//                      dense block [N][R] by variable (basic variables: 0, the requested variable itself: exactly 1) — and the count /
+//                      scan / fill of cuts.inc, which turn the block into sparse rows sorted by variable (launch_rows_generate, the
+//                      phase 1 that the Gomory and the GMI round share, then launch_cut_fill);
 //   solves with dense right-hand sides X[m][R] (interleaved like the block: entry i of all R right-hand sides is one 128-byte line):
 //       FTRAN  Y_K = W X_K (one wave per row of W, lanes stride its columns, R accumulators per lane, xor tree of the wave), then the pull
 //              Y_S = D^-1 (X_S - F Y_K) per singleton row over its CSR entries;
 //       BTRAN  Y_S = D^-1 X_S, T_K = X_K - F^T Y_S as a pull per nucleus column over its CSC entries, Y_K = W^T T_K (one thread per column
 //              of W, R accumulators, the right-hand sides wave-uniform; partial sums per row stripe, reduced in stripe order);
 //       W = W0 + the pending rank-1 terms of the delayed-update mode, applied in term order, never folded;
-//       compact factor: one level-scheduled solve per right-hand side on a copy of the view with private result vectors.
+//       compact factor: one level-scheduled solve per right-hand side on a copy of the view with private result vectors
+//              (launch_fac_block, ranging.inc);
+//       the two pulls are the accumulators of ranging.inc: csr_nucleus_pull (k_tab_f_pull), csc_block_dot (k_tab_b_rhs).
 // Side-effect free in the sense of duals.inc: only the private buffers of TabBufs / RangingBufs are written.  No float atomics; every sum
 // has a fixed order that depends on its own right-hand side alone (never on what else is in the batch, or in which place), so the numbers
 // of a request are bit-identical whatever the call.  Every kernel walks its index space with a stride loop or a grid computed to cover
@@ -22,38 +25,19 @@ constexpr int TB_STRIPES = 16;  // the transposed pass splits the rows of W0 int
 
 template <int R, int G>
 __global__ void __launch_bounds__(BLK) k_tab_sweep(DevView v, RangingBufs b, double* __restrict__ ad) {
-    const long var = ((long)blockIdx.x * BLK + threadIdx.x) / G;
+    const int var = (int)(((long)blockIdx.x * BLK + threadIdx.x) / G);
     const int gl = threadIdx.x & (G - 1);
     double acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0;
     int loc = 0;
     if (var < b.N) loc = v.var_loc[var];
     const bool live = var < b.N && loc < 0;
-    if (live) {
-        const int end = v.csc_ptr[var + 1];
-        for (int e = v.csc_ptr[var] + gl; e < end; e += G) {
-            const double a = v.csc_val[e];
-            const double2* rr = reinterpret_cast<const double2*>(b.blk + (size_t)v.csc_row[e] * R);
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const double2 t = rr[r >> 1];
-                acc[r] += a * t.x;
-                acc[r + 1] += a * t.y;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+    csc_block_dot<R, G>(v, b.blk, live, var, gl, acc);
     if (var < b.N && gl == 0) {  // a basic variable: 0, and exactly 1 in the rows that were asked for it (req: -1 at an empty place)
-        double2* out = reinterpret_cast<double2*>(ad + (size_t)var * R);
+        if (!live) {
 #pragma unroll
-        for (int r = 0; r < R; r += 2) {
-            double2 t;
-            t.x = live ? acc[r] : (b.req[r] == loc ? 1.0 : 0.0);
-            t.y = live ? acc[r + 1] : (b.req[r + 1] == loc ? 1.0 : 0.0);
-            out[r >> 1] = t;
+            for (int r = 0; r < R; ++r) acc[r] = b.req[r] == loc ? 1.0 : 0.0;
         }
+        store_block_row<R>(ad + (size_t)var * R, acc);
     }
 }
 
@@ -143,38 +127,18 @@ __global__ void __launch_bounds__(BLK) k_tab_wx(DevView v, TabBufs b) {
 // order, xor tree of the lane group) — a pull per row, no push, no atomics
 template <int R, int G>
 __global__ void __launch_bounds__(BLK) k_tab_f_pull(DevView v, TabBufs b) {
-    const long p = ((long)blockIdx.x * BLK + threadIdx.x) / G;
+    const int p = (int)(((long)blockIdx.x * BLK + threadIdx.x) / G);
     const int gl = threadIdx.x & (G - 1);
     double acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0;
     int sg = -1;
-    if (p < v.m && v.kslot_of_pos[p] < 0) {
-        sg = v.srow_of_pos[p];
-        const int end = v.csr_ptr[sg + 1];
-        for (int e = v.csr_ptr[sg] + gl; e < end; e += G) {
-            const int l2 = v.var_loc[v.csr_col[e]];
-            if (l2 < 0) continue;
-            const int s = v.kslot_of_pos[l2];
-            if (s < 0) continue;
-            const double a = v.csr_val[e];
-            const double2* hh = reinterpret_cast<const double2*>(b.YK + (size_t)s * R);
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const double2 t = hh[r >> 1];
-                acc[r] += a * t.x;
-                acc[r + 1] += a * t.y;
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+    if (p < v.m && v.kslot_of_pos[p] < 0) sg = v.srow_of_pos[p];
+    csr_nucleus_pull<R, G>(v, b.YK, sg, gl, acc);
     if (sg >= 0 && gl == 0) {
         const double d = v.sdiag_of_pos[p];
         const double2* xx = reinterpret_cast<const double2*>(b.X + (size_t)sg * R);
         double2* out = reinterpret_cast<double2*>(b.Y + (size_t)p * R);
 #pragma unroll
-        for (int r = 0; r < R; r += 2) {
+        for (int r = 0; r < R; r += 2) {  // (pair by pair: load, finish, store)
             const double2 x = xx[r >> 1];
             double2 t;
             t.x = (x.x - acc[r]) / d;
@@ -197,34 +161,20 @@ __global__ void __launch_bounds__(BLK) k_tab_b_gather(DevView v, TabBufs b) {
 // T_K = X_K - F^T Y_S by row slot: a pull over the CSC entries of the nucleus column (G lanes; its nucleus rows read exact zeros)
 template <int R, int G>
 __global__ void __launch_bounds__(BLK) k_tab_b_rhs(DevView v, TabBufs b) {
-    const long slot = ((long)blockIdx.x * BLK + threadIdx.x) / G;
+    const int slot = (int)(((long)blockIdx.x * BLK + threadIdx.x) / G);
     const int gl = threadIdx.x & (G - 1);
     double acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.0;
-    int p = -1;
+    int p = -1, var = 0;
     if (slot < b.k) {
         p = v.pos_of_kslot[slot];
-        const int var = v.basic_vars[p];
-        const int end = v.csc_ptr[var + 1];
-        for (int e = v.csc_ptr[var] + gl; e < end; e += G) {
-            const double a = v.csc_val[e];
-            const double2* yy = reinterpret_cast<const double2*>(b.Y + (size_t)v.csc_row[e] * R);
-#pragma unroll
-            for (int r = 0; r < R; r += 2) {
-                const double2 t = yy[r >> 1];
-                acc[r] += a * t.x;
-                acc[r + 1] += a * t.y;
-            }
-        }
+        var = v.basic_vars[p];
     }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = group_sum<G>(acc[r]);
+    csc_block_dot<R, G>(v, b.Y, p >= 0, var, gl, acc);
     if (p >= 0 && gl == 0) {
         const double2* xx = reinterpret_cast<const double2*>(b.X + (size_t)p * R);
         double2* out = reinterpret_cast<double2*>(b.XK + (size_t)slot * R);
 #pragma unroll
-        for (int r = 0; r < R; r += 2) {
+        for (int r = 0; r < R; r += 2) {  // (pair by pair: load, subtract, store)
             const double2 x = xx[r >> 1];
             double2 t;
             t.x = x.x - acc[r];
@@ -253,14 +203,7 @@ __global__ void __launch_bounds__(BLK) k_tab_wt(DevView v, TabBufs b, int rows) 
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[r] += a * t[r];
     }
-    double2* out = reinterpret_cast<double2*>(b.part + ((size_t)blockIdx.y * k + c) * R);
-#pragma unroll
-    for (int r = 0; r < R; r += 2) {
-        double2 t;
-        t.x = acc[r];
-        t.y = acc[r + 1];
-        out[r >> 1] = t;
-    }
+    store_block_row<R>(b.part + ((size_t)blockIdx.y * k + c) * R, acc);
 }
 // Y_K = the partials in stripe order + sum_j V_j (U_j . T_K) in term order, scattered to the nucleus rows
 template <int R>
@@ -280,33 +223,39 @@ __global__ void __launch_bounds__(BLK) k_tab_wt_reduce(DevView v, TabBufs b, int
         b.Y[(size_t)v.row_of_kslot[c] * R + r] = s;
     }
 }
-// compact factor: right-hand side r of the block as the vector of one solve (its result goes back through k_rg_take)
-template <int R>
-__global__ void __launch_bounds__(BLK) k_tab_col(const double* __restrict__ X, double* __restrict__ u, int m, int r) {
-    const long step = (long)gridDim.x * BLK;
-    for (long i = (long)blockIdx.x * BLK + threadIdx.x; i < m; i += step) u[i] = X[(size_t)i * R + r];
-}
-
-static inline int tab_grid(long n) { return (int)std::min<long>(blocks_for(n), 8192); }  // (the kernels behind it stride)
 int tab_wt_stripes(int k) { return std::max(1, std::min(TB_STRIPES, (k + DU_WT_ROWS - 1) / DU_WT_ROWS)); }
 static inline int tab_wt_rows(int k) { const int ns = tab_wt_stripes(k); return (k + ns - 1) / ns; }
 
-// phase 1 of a batch of tableau rows: block of rows, sweep, count, scan, heads (the buffers of launch_cut_generate; ad: [N][RG_BATCH]);
-// phase 2 is launch_cut_fill on ad
-void launch_tab_rows(const DevView& dv, const Geom& g, const RangingBufs& b, int nreq, const int* h_req, double* ad, int* cnt, int* off,
-                     int* sums, int* len, double* rhs, hipStream_t st) {
+// Phase 1 of a batch of sparse rows, whatever their kind (kernels.h: RowKind): the block of rows of B^-1, the kind's sweep over A into the
+// dense block, (GMI: the clear of the requests that met a free column,) count, scan, heads.  Phase 2 is launch_cut_fill on the block.
+void launch_rows_generate(const DevView& dv, const Geom& g, const RangingBufs& b, RowKind kind, const GmiBufs* gb, int nreq, const int* h_req,
+                          double* dense, int* cnt, int* off, int* sums, int* len, double* rhs, hipStream_t st) {
     constexpr int R = RG_BATCH;
     launch_ranging_block(dv, g, b, 0, nreq, h_req, st);
+    if (kind == ROWS_GMI) hipLaunchKernelGGL(k_gmi_head<R>, dim3(1), dim3(64), 0, st, dv, b.req, *gb);
     const int nb = ranging_blocks(g, 0, b.N);
-    LANES_SWITCH(g.lanes,
-                 hipLaunchKernelGGL((k_tab_sweep<R, 4>), dim3(nb), dim3(BLK), 0, st, dv, b, ad),
-                 hipLaunchKernelGGL((k_tab_sweep<R, 16>), dim3(nb), dim3(BLK), 0, st, dv, b, ad),
-                 hipLaunchKernelGGL((k_tab_sweep<R, 64>), dim3(nb), dim3(BLK), 0, st, dv, b, ad));
+#define ROW_SWEEP(G)                                                                                                              \
+    do {                                                                                                                          \
+        if (kind == ROWS_TABLEAU) hipLaunchKernelGGL((k_tab_sweep<R, G>), dim3(nb), dim3(BLK), 0, st, dv, b, dense);              \
+        else if (kind == ROWS_GOMORY) hipLaunchKernelGGL((k_cut_sweep<R, G>), dim3(nb), dim3(BLK), 0, st, dv, b, dense);          \
+        else hipLaunchKernelGGL((k_gmi_sweep<R, G>), dim3(nb), dim3(BLK), 0, st, dv, b, *gb, dense);                              \
+    } while (0)
+    LANES_SWITCH(g.lanes, ROW_SWEEP(4), ROW_SWEEP(16), ROW_SWEEP(64));
+#undef ROW_SWEEP
     const int nseg = cut_segments(b.N);
     const long n = (long)R * nseg;
-    hipLaunchKernelGGL((k_cut_compact<R, 0>), dim3(blocks_for(n)), dim3(BLK), 0, st, ad, b.N, nseg, cnt, nullptr, nullptr, nullptr);
+    const int* total = sums + (n + SCAN_TILE - 1) / SCAN_TILE;
+    if (kind == ROWS_GMI) {
+        hipLaunchKernelGGL(k_gmi_clear<R>, dim3(blocks_for((long)b.N * R)), dim3(BLK), 0, st, *gb, b.N, dense);
+        hipLaunchKernelGGL((k_cut_compact<R, 2>), dim3(blocks_for(n)), dim3(BLK), 0, st, dense, b.N, nseg, cnt, nullptr, nullptr, nullptr,
+                           dv.var_loc, dv.xN, gb->part);
+    } else {
+        hipLaunchKernelGGL((k_cut_compact<R, 0>), dim3(blocks_for(n)), dim3(BLK), 0, st, dense, b.N, nseg, cnt, nullptr, nullptr, nullptr,
+                           nullptr, nullptr, nullptr);
+    }
     launch_exclusive_scan(cnt, off, n, sums, st);
-    hipLaunchKernelGGL(k_cut_heads<R>, dim3(1), dim3(64), 0, st, dv, b.req, off, sums + (n + SCAN_TILE - 1) / SCAN_TILE, nseg, len, rhs);
+    if (kind == ROWS_GMI) hipLaunchKernelGGL(k_gmi_heads<R>, dim3(R), dim3(BLK), 0, st, *gb, off, total, nseg, len, rhs);
+    else hipLaunchKernelGGL(k_cut_heads<R>, dim3(1), dim3(64), 0, st, dv, b.req, off, total, nseg, len, rhs);
 }
 // right-hand sides of a batch formed on the device: mode 1 unit vectors of the rows req[], mode 2 the columns req[] of [A | I]
 void launch_tab_rhs(const DevView& dv, const TabBufs& b, const int* req, int nreq, int mode, hipStream_t st) {
@@ -320,19 +269,8 @@ void launch_tab_solve(const DevView& dv, const Geom& g, const TabBufs& b, int tr
     const int m = g.m, k = b.k;
     if (m <= 0) return;
     (void)hipMemsetAsync(b.Y, 0, sizeof(double) * (size_t)m * R, st);
-    if (b.fac) {  // one level-scheduled solve per right-hand side (pending terms included), private result vectors
-        DevView pv = dv;
-        pv.rv = b.rv;
-        pv.tau = b.tau;
-        RangingBufs rb{};
-        rb.blk = b.Y; rb.rv = b.rv; rb.tau = b.tau;
-        for (int r = 0; r < nreq; ++r) {
-            (void)hipMemsetAsync(b.rv, 0, sizeof(double2) * (size_t)m, st);
-            (void)hipMemsetAsync(b.tau, 0, sizeof(double) * (size_t)m, st);
-            hipLaunchKernelGGL(k_tab_col<R>, dim3(tab_grid(m)), dim3(BLK), 0, st, b.X, b.unit, m, r);
-            launch_fac_solve(pv, g, transpose ? 1 : 0, 2, 1, b.unit, 1, st);
-            hipLaunchKernelGGL(k_rg_take<R>, dim3(blocks_for(m)), dim3(BLK), 0, st, rb, m, r, transpose ? 0 : 1);
-        }
+    if (b.fac) {
+        launch_fac_block(dv, g, b, transpose ? 1 : 0, nreq, nullptr, b.X, b.Y, st);
         return;
     }
     const int G = rg_lanes(g);

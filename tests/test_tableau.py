@@ -479,6 +479,70 @@ def test_batch_edges_and_independence(monkeypatch, rep):
         assert _pending(s) == before > 0
 
 
+def _gomory_round_from_tableau_rows(s, on_self, before_call=None):
+    """17 basic variables (two batches): what add_gomory_cuts stores for each must be, bit for bit, floor(a) - a of the row tableau_rows
+    returns for it, exact zeros dropped, and its right-hand side floor(x) - x of the variable's value.  Returns the rows compared."""
+    from tests.test_cut_rounds import _stored_rows
+    n = s.num_vars
+    assert s.num_rows == s.num_constraints                          # every constraint has a row: slack columns number alike in both
+    vs, _ = s.basis_status()
+    x = s.values()
+    basic = [j for j in range(n) if vs[j] == M.MLP_BASIC]
+    frac = [j for j in basic if abs(x[j] - round(x[j])) > 1e-6]
+    req = (frac + [j for j in basic if j not in set(frac)])[:17]
+    assert len(req) == 17 and len(frac) >= 10, (len(req), len(frac))
+    ip, ix, dv = s.tableau_rows(req)
+    assert s.tableau_info()["batches"] == 2
+    m0 = len(s.state("csr_indptr")) - 1
+    t = s if on_self else s.clone()
+    if before_call:
+        before_call(t)
+    t = t.add_gomory_cuts(req)
+    info = t.cut_info()
+    assert info["batches"] == 2, info
+    stored = iter(_stored_rows(t, m0))
+    compared = terms = 0
+    for q, j in enumerate(req):
+        a = dv[ip[q]:ip[q + 1]]
+        f = np.floor(a) - a
+        keep = f != 0.0
+        if not keep.any():
+            continue                                                # (a row without terms is not stored: counted below)
+        cols, vals, rhs = next(stored)
+        assert cols.tobytes() == ix[ip[q]:ip[q + 1]][keep].astype(np.int64).tobytes(), (q, j)
+        assert vals.tobytes() == f[keep].tobytes(), (q, j)
+        assert np.float64(rhs).tobytes() == np.float64(math.floor(x[j]) - x[j]).tobytes(), (q, j, rhs, x[j])
+        compared += 1
+        terms += int(keep.sum())
+    assert next(stored, None) is None
+    assert compared + info["rows_without_terms"] == len(req) and compared >= 10, (compared, info)
+    print("gomory round against tableau rows: %d rows, %d terms, bit-identical" % (compared, terms))
+    return compared
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rep", ["explicit", "pending", "factor", (40, 30, 6, 9), (200, 150, 8, 3), (600, 500, 10, 5)], ids=str)
+def test_a_gomory_round_is_the_tableau_rows_bit_for_bit(monkeypatch, rep):
+    """The Gomory round and the tableau rows form alpha = rho . a_j with ONE accumulator (csc_block_dot) over the same block of rows of
+    B^-1: on the three representations of test_batch_edges_and_independence and on the instances of test_cut_rounds'
+    test_gomory_rows_against_a_host_reference.  With pending terms the round is added to the solution itself: a clone folds them."""
+    check = None
+    if rep == "pending":
+        _big(monkeypatch)
+        s, _ = _with_pending_terms(lpgen.gen_sparse_lp(400, 300, 12, 7))
+
+        def check(t):
+            assert _pending(t) > 0
+    elif rep == "factor":
+        monkeypatch.setenv("MLP_FACTOR", "1")
+        s = lpgen.build_problem(M.Problem, lpgen.gen_transport_lp(600, 700, 4, 5, tight=0.45)).solve()
+        assert s.stats()["factor_active"] == 1
+    else:
+        s = lpgen.build_problem(M.Problem, lpgen.gen_sparse_lp(*((400, 300, 12, 7) if rep == "explicit" else rep))).solve()
+        assert s.stats()["factor_active"] == 0
+    _gomory_round_from_tableau_rows(s, on_self=rep == "pending", before_call=check)
+
+
 @pytest.fixture(scope="module")
 def mixed():
     lp = lpgen.gen_mixed_lp(300, 400, 6, 3)
