@@ -3,7 +3,7 @@
 minimise, print the objective and the non-zero variables.
 
     python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--tableau VAR] [--gomory-rounds K]
-                                 [--gmi-rounds K [--continuous NAME,...]]
+                                 [--gmi-rounds K [--continuous NAME,...]] [--branch-penalties [--continuous NAME,...]]
 
 --ranging adds a sensitivity table: per variable its value, basis status, reduced cost and cost range; per row its dual value and
 rhs range (rows in file order).  --tableau VAR prints the tableau row of the basic variable VAR (by name): its non-zero coefficients on the
@@ -12,7 +12,9 @@ fractional value (|x - round x| > 1e-6) in one add_gomory_cuts call, and prints 
 That cut is valid only for a pure integer model with integer slacks whose non-basic columns sit at a zero lower bound.  --gmi-rounds K adds
 K rounds of Gomory mixed-integer cuts instead (one add_gmi_cuts call per round over the basic integer variables with a fractional value):
 every structural variable is integer unless listed in --continuous, the slacks are continuous; it prints the bound, the cuts emitted and
-skipped and the counters after each round.
+skipped and the counters after each round.  --branch-penalties prints, for every basic structural variable with a fractional value at the
+LP optimum, the one-pivot bounds of its down and up branch (plain, and with Tomlin's strengthening: every structural variable is integer
+unless listed in --continuous, the slacks are continuous), the child bounds they give and the columns that would enter.
 
 Runs on the MI355X engine (libminilp_hip.so); there is no CPU back end.  `run(B, ...)` takes the module that
 provides the reference's API so that the tests can drive the same code with their checker."""
@@ -24,7 +26,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=()):
+def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -68,6 +70,27 @@ def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0,
         print("tableau row of %s (= %.12g):" % (tableau, x[var]))
         for col, a in zip(ix, dv):
             print("  %-12s %.12g" % (names[col] if col < len(x) else "slack(row %d)" % (col - len(x)), a))
+    if branch_penalties:
+        unknown = [nm for nm in continuous if nm not in f.variables]
+        if unknown:
+            print("branch penalties: no variable named %s" % ", ".join(unknown))
+            return 1
+        marks = [True] * len(f.variables)
+        for nm in continuous:
+            marks[f.variables[nm]] = False
+        names = {v: n for n, v in f.variables.items()}
+        col = lambda c: "-" if c < 0 else (names[c] if c < len(x) else "slack(row %d)" % (c - len(x)))
+        plain, strong = sol.branch_penalties(range(len(x))), sol.branch_penalties(range(len(x)), marks)
+        sg = -1.0 if maximize else 1.0
+        obj = sol.objective()
+        rows = [v for v in range(len(x)) if plain["status"][v] == 0]
+        print("branch penalties of %d fractional basic variables (objective %.12g), %s" % (len(rows), obj, sol.branch_info()))
+        print("%-12s %12s %14s %14s %14s %14s %14s %14s   %s" % ("variable", "fraction", "down", "up", "down (int)", "up (int)",
+                                                                  "bound down", "bound up", "entering (down, up)"))
+        for v in rows:
+            print("%-12s %12.8g %14.8g %14.8g %14.8g %14.8g %14.8g %14.8g   %s, %s" %
+                  (names[v], plain["frac"][v], plain["down"][v], plain["up"][v], strong["down"][v], strong["up"][v],
+                   obj + sg * plain["down"][v], obj + sg * plain["up"][v], col(plain["down_col"][v]), col(plain["up_col"][v])))
     for k in range(gomory_rounds):
         x = sol.values()
         vs, _ = sol.basis_status()
@@ -119,10 +142,13 @@ def main():
     ap.add_argument("--gmi-rounds", type=int, default=0, metavar="K",
                     help="K rounds of Gomory mixed-integer cuts over the fractional basic integer variables (one add_gmi_cuts call per round)")
     ap.add_argument("--continuous", default="", metavar="NAME,...",
-                    help="with --gmi-rounds: the variables that are NOT integer (all others are; slacks are continuous)")
+                    help="with --gmi-rounds / --branch-penalties: the variables that are NOT integer (all others are; slacks are continuous)")
+    ap.add_argument("--branch-penalties", action="store_true",
+                    help="print the one-pivot branching bounds of the fractional basic variables (Solution.branch_penalties)")
     a = ap.parse_args()
     import minilp_amd as B
-    return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau, a.gmi_rounds, [nm for nm in a.continuous.split(",") if nm])
+    return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau, a.gmi_rounds, [nm for nm in a.continuous.split(",") if nm],
+               a.branch_penalties)
 
 
 if __name__ == "__main__":

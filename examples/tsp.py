@@ -7,7 +7,11 @@ rows = 2, Stoer–Wagner min cut to find violated subtour rows (cut weight < 2 -
 branching with `fix_var` on cloned solutions.  Written against the Problem/Solution API only, so it
 runs on any backend module that mirrors it (`minilp_amd` on the GPU, or the CPU oracle in tests).
 
-usage: python examples/tsp.py tests/golden/bn130.tsp [--nodes N] [--max-bb-nodes K]
+usage: python examples/tsp.py tests/golden/bn130.tsp [--nodes N] [--max-bb-nodes K] [--branching fractional|penalties]
+
+--branching penalties picks the branching variable by the one-pivot bounds of `Solution.branch_penalties` (the product rule on the down
+and up penalty) instead of the most fractional one, and skips a side whose penalty already proves it infeasible or no better than the
+best tour, without cloning the solution.
 """
 import argparse
 import math
@@ -80,8 +84,10 @@ def stoer_wagner_py(w):
 
 
 class TspSolver:
-    def __init__(self, backend, pts, log=None, batch_cuts=False):
+    def __init__(self, backend, pts, log=None, batch_cuts=False, branching="fractional"):
         self.B = backend
+        assert branching in ("fractional", "penalties")
+        self.branching = branching  # "penalties": Solution.branch_penalties chooses the variable and prunes sides (needs a back end that has it)
         self.batch_cuts = batch_cuts  # separate ALL violated subtour constraints of an LP solution and add them with one call
         self.pts = pts
         self.n = len(pts)
@@ -89,6 +95,8 @@ class TspSolver:
         d = pts[:, None, :] - pts[None, :, :]
         self.dist = np.sqrt((d ** 2).sum(axis=2))  # un-rounded Euclidean distance (tsp.rs:19-25)
         self.stats = dict(lp_solves=1, cuts=0, fix_calls=0, clones=0, bb_nodes=0)
+        if branching == "penalties":
+            self.stats.update(penalty_calls=0, skipped_sides=0)
         n = self.n
         self.edge_var = -np.ones((n, n), dtype=np.int64)
         p = backend.Problem(backend.MINIMIZE)
@@ -166,14 +174,32 @@ class TspSolver:
         v = int(np.argmax(div))
         return v if div[v] > 1e-5 else None
 
+    def choose_branch(self, sol):
+        """(variable, penalties) of the next branching, or None at an integral point; penalties = (down, up) bounds on the rise of the
+        objective with the variable at 0 / at 1, or None for most-fractional branching."""
+        if self.branching == "fractional":
+            var = self.choose_branch_var(sol)
+            return None if var is None else (var, None)
+        nv = self.n * (self.n - 1) // 2
+        # every edge variable is integer: Tomlin's strengthening applies (the bounds are used against tours, never against a child LP)
+        bp = sol.branch_penalties(range(nv), integer_vars=np.ones(nv, dtype=bool))
+        self.stats["penalty_calls"] += 1
+        cand = np.flatnonzero((bp["frac"] > 1e-5) & (bp["frac"] < 1.0 - 1e-5))
+        if len(cand) == 0:
+            return None
+        dn, up = bp["down"][cand], bp["up"][cand]
+        score = np.maximum(np.minimum(dn, up), 1e-6) * np.maximum(np.maximum(dn, up), 1e-6)
+        t = int(np.argmax(score))
+        return int(cand[t]), (float(dn[t]), float(up[t]))
+
     def solve(self, max_nodes=None):  # tsp.rs:211-392
         sol = self.relaxation()
         self.log("relaxation bound %.6f after %d cuts" % (sol.objective(), self.stats["cuts"]))
-        var = self.choose_branch_var(sol)
-        if var is None:
+        pick = self.choose_branch(sol)
+        if pick is None:
             return sol.objective(), self.tour(sol)
         best_cost, best_tour = math.inf, None
-        stack = [dict(start=sol, var=var, start_val=0 if sol[var] < 0.5 else 1, cur=None)]
+        stack = [dict(start=sol, var=pick[0], pen=pick[1], start_val=0 if sol[pick[0]] < 0.5 else 1, cur=None)]
         while stack:
             step = stack[-1]
             if step["cur"] is None:
@@ -183,6 +209,11 @@ class TspSolver:
             else:
                 stack.pop()
                 continue
+            if step["pen"] is not None:  # the side's one-pivot bound: infeasible, or no better than the best tour => no clone, no LP
+                pen = step["pen"][step["cur"]]
+                if pen == math.inf or step["start"].objective() + pen > best_cost:
+                    self.stats["skipped_sides"] += 1
+                    continue
             self.stats["bb_nodes"] += 1
             if max_nodes and self.stats["bb_nodes"] > max_nodes:
                 break
@@ -201,9 +232,9 @@ class TspSolver:
             obj = cur.objective()
             if obj > best_cost:
                 continue
-            var = self.choose_branch_var(cur)
-            if var is not None:
-                stack.append(dict(start=cur, var=var, start_val=0 if cur[var] < 0.5 else 1, cur=None))
+            pick = self.choose_branch(cur)
+            if pick is not None:
+                stack.append(dict(start=cur, var=pick[0], pen=pick[1], start_val=0 if cur[pick[0]] < 0.5 else 1, cur=None))
             elif obj < best_cost:
                 best_cost, best_tour = obj, self.tour(cur)
                 self.log("node %d depth %d: new best tour %.6f" % (self.stats["bb_nodes"], len(stack), obj))
@@ -271,13 +302,15 @@ def main():
     ap.add_argument("--svg", default=None, help="write the tour as an SVG drawing (tsp.rs:169-208)")
     ap.add_argument("--batch-cuts", action="store_true",
                     help="separate all violated subtour constraints of an LP solution and add them with one add_constraints call")
+    ap.add_argument("--branching", choices=["fractional", "penalties"], default="fractional",
+                    help="penalties: choose the branching variable by Solution.branch_penalties and skip sides its bounds rule out")
     a = ap.parse_args()
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import minilp_amd as backend  # the MI355X engine; there is no CPU back end (tests pass their checker to TspSolver)
     name, pts = read_tsplib(a.file, a.nodes)
     t0 = time.time()
-    s = TspSolver(backend, pts, log=lambda m: print("[%.1fs] %s" % (time.time() - t0, m), flush=True), batch_cuts=a.batch_cuts)
+    s = TspSolver(backend, pts, log=lambda m: print("[%.1fs] %s" % (time.time() - t0, m), flush=True), batch_cuts=a.batch_cuts, branching=a.branching)
     cost, tour = s.solve(a.max_bb_nodes)
     print("problem %s (%d cities): tour cost %.10f, %s, %.1fs" % (name, len(pts), cost, s.stats, time.time() - t0))
     print("tour:", " ".join(str(int(t) + 1) for t in tour))  # Tour::to_string (tsp.rs:161-167): 1-based city numbers

@@ -47,6 +47,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * additive in the same way. */
 /* Still version 5: the Gomory mixed-integer round (mlp_solution_add_gmi_cuts, mlp_gmi_info with its own mlp_gmi_info_size()) is
  * additive in the same way; mlp_cut_info keeps its 80 bytes. */
+/* Still version 5: the branching penalties (mlp_solution_branch_penalties, mlp_branch_info with its own mlp_branch_info_size()) are
+ * additive in the same way. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -436,6 +438,54 @@ typedef struct mlp_gmi_info {
 } mlp_gmi_info;
 int mlp_solution_gmi_info(const mlp_solution* s, mlp_gmi_info* out);
 uint64_t mlp_gmi_info_size(void);
+
+/* ---- Branching penalties: one-pivot bounds for both branches of a variable (Driebeek-Tomlin) -----------------------------------------------
+ * What does it cost to branch on x_j?  The penalty of a branch is the objective change of the FIRST dual-simplex pivot after the bound
+ * x_j <= floor(x_j) (down) or x_j >= ceil(x_j) (up) is imposed: a lower bound on the degradation of that child, read from the tableau row
+ * of x_j without a re-solve.  The call also names the column that would enter, and it proves a branch infeasible when no column can.
+ * Internal form, as for the ranging and the tableau reads above: min c^.x, A x + s = b, with c^ = -c for a Maximize problem.  Columns:
+ * j < num_vars is structural variable j, num_vars + c the slack of constraint c.  d are the internal reduced costs of the dual-value read.
+ * A request is a structural variable j.
+ *   non-basic j: frac = xN_j - floor(xN_j), down = up = 0, both columns -1, status 1.  This is no error: drivers pass whole lists.
+ *   basic j at position p: x = xB_p, f_dn = x - floor(x), f_up = ceil(x) - x, frac = f_dn.  If f_dn == 0 exactly: answered as a non-basic
+ *     request.  Otherwise status 0, and over every non-basic column i with alpha_i = (e_p^T B^-1) abar_i (|alpha_i| <= 1e-8 counts as
+ *     zero) and the numerator |d_i| (a reduced cost of the wrong sign clamped to 0, exactly as the cost ranging does it):
+ *       eligible in the down branch (x_j must fall by f_dn): i at lower with alpha_i > 0, or at upper with alpha_i < 0;
+ *       eligible in the up branch: the mirror image;
+ *       MLP_NB_FREE with alpha_i != 0: eligible both ways with ratio 0;   MLP_NB_FIXED: never eligible;
+ *       rho_i = |d_i| / |alpha_i|.
+ *     down = f_dn * min rho_i over the down set, up = f_up * min rho_i over the up set; an empty set gives +inf: that branch is infeasible
+ *     for the bounds the call finds (a bound tightened by mlp_solution_fix_var counts).  down_col / up_col are the minimising columns;
+ *     among exactly equal candidates the lowest column number wins; -1 for an empty set.
+ * Tomlin's strengthening (optional): a column that is marked integer (structural columns by var_is_int, slacks by con_is_int, as for
+ *   mlp_solution_add_gmi_cuts), whose status is at lower or at upper and whose xN_i == floor(xN_i) exactly must itself move by at least 1
+ *   in an integer solution, so it takes the candidate T_i = max(f * rho_i, |d_i|) instead of f * rho_i; the result is min T_i with the same
+ *   tie rule.  The strengthened numbers bound the integer-feasible descendants of the branch, NOT the child LP.  var_is_int == NULL:
+ *   nothing is strengthened (num_vars is then ignored, and con_is_int must be NULL too).
+ * User's sense: both numbers are non-negative DEGRADATIONS and no sign is turned: the child's bound is objective() + down for a Minimize
+ *   problem and objective() - down for a Maximize problem.
+ * The numbers are those of the CURRENT basis, whatever it is; they are bounds at a dual-feasible basis (an optimum, or the basis a
+ *   mutator's re-solve ends in) and the same formulas, never an error, on a budget-limited solve — like the ranging.
+ * The six outputs of a request are bit for bit the same alone, anywhere in any call and from run to run (16 requests share one pass over
+ *   A; the minimum over the columns is exact).  Duplicates are allowed; n == 0 is a successful no-op.  The call is a read, side-effect
+ *   free like the ranging: no solution is freed and no cache is dropped.
+ * MLP_EINVAL: a variable out of range, a mask length that does not fit (num_vars != mlp_solution_num_vars with var_is_int given,
+ *   num_constraints != mlp_solution_num_constraints with con_is_int given, con_is_int without var_is_int), a sharded solution, NULL
+ *   handles or outputs.
+ * mlp_branch_info: counters of the last mlp_solution_branch_penalties call on this solution (zeros before the first).  Only grows at its
+ *   end; mlp_branch_info_size() is its size as the library was built. */
+int mlp_solution_branch_penalties(const mlp_solution* s, const uint32_t* vars, uint64_t n, const uint8_t* var_is_int, uint32_t num_vars,
+                                  const uint8_t* con_is_int, uint64_t num_constraints, double* down, double* up, int64_t* down_col,
+                                  int64_t* up_col, double* frac, int32_t* status);
+typedef struct mlp_branch_info {
+    uint64_t requests;   /* variables asked for */
+    uint64_t solves;     /* of them: basic fractional requests, which reached the device */
+    uint64_t batches;    /* batches of 16 of them: one pass over A each */
+    double bytes;        /* algorithmic bytes of the batches */
+    double device_ms;    /* their time on the device (HIP events around the launches) */
+} mlp_branch_info;
+int mlp_solution_branch_info(const mlp_solution* s, mlp_branch_info* out);
+uint64_t mlp_branch_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

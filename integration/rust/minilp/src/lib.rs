@@ -388,6 +388,35 @@ impl Solution {
         (lo, hi)
     }
 
+    /// Branching penalties of the listed variables at the current basis: per variable `(down, up, down_col, up_col, frac)`, the
+    /// one-pivot (Driebeek-Tomlin) lower bounds on the objective degradation of the branches `x <= floor(x)` and `x >= ceil(x)`
+    /// (`f64::INFINITY`: the branch is infeasible), the columns that would enter (`None`: no column; `num_vars + c` is the slack
+    /// of constraint `c`) and the fraction of the variable.  A non-basic or integral variable returns zeros and no columns.
+    /// `integer_vars` / `integer_constraints` switch Tomlin's strengthening on: the numbers then bound the integer descendants of
+    /// the branch, not the child LP (extension: no counterpart in the reference; semantics in `minilp_hip.h`).
+    ///
+    /// # Panics
+    ///
+    /// Will panic if a mask has the wrong length or `integer_constraints` is given without `integer_vars`.
+    pub fn branch_penalties(&self, vars: &[Variable], integer_vars: Option<&[bool]>, integer_constraints: Option<&[bool]>) -> Vec<(f64, f64, Option<usize>, Option<usize>, f64)> {
+        assert!(vars.iter().all(|x| x.0 < self.num_vars));
+        let v: Vec<u32> = vars.iter().map(|x| x.0 as u32).collect();
+        let vm: Option<Vec<u8>> = integer_vars.map(|m| m.iter().map(|&b| b as u8).collect());
+        let cm: Option<Vec<u8>> = integer_constraints.map(|m| m.iter().map(|&b| b as u8).collect());
+        let (vp, vn) = vm.as_ref().map_or((std::ptr::null(), 0u32), |m| (m.as_ptr(), m.len() as u32));
+        let (cp, cn) = cm.as_ref().map_or((std::ptr::null(), 0u64), |m| (m.as_ptr(), m.len() as u64));
+        let n = v.len();
+        let (mut down, mut up, mut frac) = (vec![0.0f64; n], vec![0.0f64; n], vec![0.0f64; n]);
+        let (mut dcol, mut ucol, mut status) = (vec![0i64; n], vec![0i64; n], vec![0i32; n]);
+        let st = unsafe {
+            sys::mlp_solution_branch_penalties(self.raw, v.as_ptr(), n as u64, vp, vn, cp, cn, down.as_mut_ptr(), up.as_mut_ptr(),
+                                               dcol.as_mut_ptr(), ucol.as_mut_ptr(), frac.as_mut_ptr(), status.as_mut_ptr())
+        };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        let col = |c: i64| if c < 0 { None } else { Some(c as usize) };
+        (0..n).map(|t| (down[t], up[t], col(dcol[t]), col(ucol[t]), frac[t])).collect()
+    }
+
     /// Range `(lo, hi)` of the right-hand side of a constraint (by index, in the order the constraints were added) over which the
     /// current basis stays feasible; within it the objective moves by `dual_value * delta` (extension).
     pub fn rhs_range(&self, constraint: usize) -> (f64, f64) {

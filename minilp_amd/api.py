@@ -76,6 +76,10 @@ class MlpGmiInfo(C.Structure):  # include/minilp_hip.h: mlp_gmi_info (only grows
                 ("nnz", C.c_uint64), ("batches", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
 
 
+class MlpBranchInfo(C.Structure):  # include/minilp_hip.h: mlp_branch_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("solves", C.c_uint64), ("batches", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -211,6 +215,12 @@ def lib():
     pu8 = C.POINTER(C.c_uint8)
     sig("mlp_solution_add_gmi_cuts", i32, C.POINTER(vp), pu32, u64, pu8, u32, pu8, u64, dbl, C.POINTER(C.c_int32))
     sig("mlp_solution_gmi_info", i32, vp, C.POINTER(MlpGmiInfo))
+    sig("mlp_branch_info_size", u64)
+    if L.mlp_branch_info_size() != C.sizeof(MlpBranchInfo):
+        raise ImportError(f"{_SO}: mlp_branch_info is {L.mlp_branch_info_size()} bytes, this binding {C.sizeof(MlpBranchInfo)}: rebuild it")
+    sig("mlp_solution_branch_penalties", i32, vp, pu32, u64, pu8, u32, pu8, u64, pdbl, pdbl, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+        pdbl, C.POINTER(C.c_int32))
+    sig("mlp_solution_branch_info", i32, vp, C.POINTER(MlpBranchInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -659,6 +669,37 @@ class Solution:
         r = MlpGmiInfo()
         _raise(lib().mlp_solution_gmi_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in MlpGmiInfo._fields_}
+
+    # ---- branching penalties (include/minilp_hip.h: mlp_solution_branch_penalties; definitions there)
+    def branch_penalties(self, vars, integer_vars=None, integer_constraints=None):
+        """One-pivot (Driebeek-Tomlin) bounds on the objective degradation of the down and the up branch of every listed structural
+        variable, from the current basis.  Returns a dict of arrays: down, up (non-negative, inf: the branch is infeasible), down_col,
+        up_col (the column that would enter; -1: none), frac, status (0 basic and fractional, 1 non-basic or integral: zeros).
+        integer_vars / integer_constraints: a bool mask or a list of indices, as for add_gmi_cuts; they switch Tomlin's strengthening on
+        (the numbers then bound the integer descendants of the branch, not the child LP).  A read: the solution is left as it is."""
+        v = np.ascontiguousarray(list(vars), dtype=np.int64).reshape(-1)
+        if len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+            raise InternalError(-1, "branch_penalties: variable out of range")
+        v = v.astype(np.uint32)
+        if integer_vars is None and integer_constraints is not None:
+            raise InternalError(-1, "branch_penalties: integer_constraints needs integer_vars")
+        vm = None if integer_vars is None else self._int_mask(integer_vars, self.num_vars)
+        cm = None if integer_constraints is None else self._int_mask(integer_constraints, self.num_constraints)
+        n = len(v)
+        out = dict(down=np.zeros(n), up=np.zeros(n), down_col=np.zeros(n, dtype=np.int64), up_col=np.zeros(n, dtype=np.int64),
+                   frac=np.zeros(n), status=np.zeros(n, dtype=np.int32))
+        _raise(lib().mlp_solution_branch_penalties(self._h, _p(v, C.c_uint32), n, None if vm is None else _p(vm, C.c_uint8),
+                                                   0 if vm is None else len(vm), None if cm is None else _p(cm, C.c_uint8),
+                                                   0 if cm is None else len(cm), _p(out["down"], C.c_double), _p(out["up"], C.c_double),
+                                                   _p(out["down_col"], C.c_int64), _p(out["up_col"], C.c_int64),
+                                                   _p(out["frac"], C.c_double), _p(out["status"], C.c_int32)))
+        return out
+
+    def branch_info(self):
+        """Counters of the last branch_penalties call (mlp_branch_info) as a dict."""
+        r = MlpBranchInfo()
+        _raise(lib().mlp_solution_branch_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpBranchInfo._fields_}
 
     def cut_info(self):
         """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""

@@ -23,6 +23,7 @@ struct mlp_solution {
     Engine::CutInfo cuts;         // of the last mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts call
     Engine::TableauInfo tableau;  // of the last tableau call
     Engine::GmiInfo gmi;          // of the last mlp_solution_add_gmi_cuts call
+    Engine::BranchInfo branch;    // of the last mlp_solution_branch_penalties call
     std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
     std::vector<uint32_t> tab_indices;
     std::vector<double> tab_values;
@@ -612,6 +613,38 @@ int mlp_solution_gmi_info(const mlp_solution* s, mlp_gmi_info* out) {
     });
 }
 uint64_t mlp_gmi_info_size(void) { return (uint64_t)sizeof(mlp_gmi_info); }
+
+// ---- branching penalties (branch.inc)
+int mlp_solution_branch_penalties(const mlp_solution* cs, const uint32_t* vars, uint64_t n, const uint8_t* var_is_int, uint32_t num_vars,
+                                  const uint8_t* con_is_int, uint64_t num_constraints, double* down, double* up, int64_t* down_col,
+                                  int64_t* up_col, double* frac, int32_t* status) {
+    return guarded([&] {
+        mlp_solution* s = const_cast<mlp_solution*>(cs);
+        const Engine::Duals& d = duals_of(s);  // (refuses a NULL handle and a sharded solution; the reduced costs come from the cached read)
+        Engine* e = s->eng;
+        if (n && !vars) throw MlpError(MLP_EINVAL, "branch_penalties: NULL variable list");
+        if (n && (!down || !up || !down_col || !up_col || !frac || !status)) throw MlpError(MLP_EINVAL, "branch_penalties: NULL output");
+        if (var_is_int ? num_vars != (uint32_t)e->num_vars : con_is_int != nullptr)
+            throw MlpError(MLP_EINVAL, "branch_penalties: var_is_int must have num_vars entries (and con_is_int needs it)");
+        if (con_is_int && num_constraints != e->num_constraints())
+            throw MlpError(MLP_EINVAL, "branch_penalties: con_is_int must have num_constraints entries");
+        std::vector<int> v((size_t)n);
+        for (uint64_t i = 0; i < n; ++i) {
+            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "branch_penalties: variable out of range");
+            v[i] = (int)vars[i];
+        }
+        e->branch_penalties(v, var_is_int, con_is_int, d, down, up, down_col, up_col, frac, status, s->branch);
+    });
+}
+int mlp_solution_branch_info(const mlp_solution* s, mlp_branch_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / branch info");
+        std::memset(out, 0, sizeof(*out));
+        out->requests = s->branch.requests; out->solves = s->branch.solves; out->batches = s->branch.batches;
+        out->bytes = s->branch.bytes; out->device_ms = s->branch.device_ms;
+    });
+}
+uint64_t mlp_branch_info_size(void) { return (uint64_t)sizeof(mlp_branch_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

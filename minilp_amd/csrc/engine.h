@@ -206,6 +206,16 @@ public:
     };
     void basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons);
     void ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du, double* lo, double* hi, RangingInfo& info);
+    // Branching penalties of the current basis (branch.inc; include/minilp_hip.h mlp_solution_branch_penalties): for every
+    // listed structural variable the Driebeek–Tomlin bounds of its down and up branch, the columns that would enter (numbering of the
+    // tableau reads, -1: none) and its fraction; status 0 = basic and fractional (served on the device, RG_BATCH per pass over A),
+    // 1 = non-basic or integral (zeros).  var_is_int == nullptr: plain penalties.  Reads the state only, like ranging.
+    struct BranchInfo {
+        uint64_t requests = 0, solves = 0, batches = 0;
+        double bytes = 0, device_ms = 0;
+    };
+    void branch_penalties(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, const Duals& du, double* down,
+                          double* up, int64_t* down_col, int64_t* up_col, double* frac, int32_t* status, BranchInfo& info);
     // Reading the tableau of the current basis (tableau.inc; include/minilp_hip.h mlp_solution_binv_rows ...).  Columns:
     // j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by CONSTRAINT (0 / ignored for one
     // without a row), vectors by position have length num_rows().  Internal form A x + s = b: no sign turn for Maximize.  Requests are

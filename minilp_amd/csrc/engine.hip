@@ -3954,6 +3954,100 @@ void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du
     }
 }
 
+// Branching penalties (branch.inc).  The basic fractional requests are served in batches of RG_BATCH; the others
+// (non-basic variables, basic variables at an integral value) are answered here.  Nothing is written but private buffers and the host's
+// cached copy of the point (fetch_values, as get_values).
+void Engine::branch_penalties(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, const Duals& du,
+                              double* down, double* up, int64_t* down_col, int64_t* up_col, double* frac, int32_t* status, BranchInfo& info) {
+    if (sharded()) throw MlpError(-1, "branch_penalties is not available on a sharded solution");
+    const size_t nreq = vars.size();
+    for (int j : vars)
+        if (j < 0 || j >= num_vars) throw MlpError(-1, "branch_penalties: variable out of range");
+    if ((int)du.r_int.size() != N_) throw MlpError(-1, "branch_penalties: the duals belong to another state");
+    info = BranchInfo();
+    info.requests = nreq;
+    if (!nreq) return;
+    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    fetch_values();
+    const DevView& dv = hview;
+    const Geom g = geom();
+    const int m = m_, N = N_;
+    std::vector<std::pair<int, size_t>> solve;  // (basic position, request)
+    for (size_t t = 0; t < nreq; ++t) {
+        const int loc = h_var_loc[vars[t]];
+        const double x = loc >= 0 ? h_xB[loc] : h_xN[-1 - loc];
+        frac[t] = x - std::floor(x);
+        down[t] = up[t] = 0.0;
+        down_col[t] = up_col[t] = -1;
+        status[t] = 1;
+        if (loc >= 0 && frac[t] != 0.0) {
+            status[t] = 0;
+            solve.emplace_back(loc, t);
+        }
+    }
+    info.solves = solve.size();
+    if (solve.empty()) return;
+    constexpr int R = RG_BATCH;
+    std::vector<int> ids(solve.size());
+    for (size_t q = 0; q < solve.size(); ++q) ids[q] = solve[q].first;
+    ReqContext ctx(*this, ids);
+    const size_t nbat = ctx.nbat;
+    const int nblk = ranging_blocks(g, 0, N);
+    DevBuf<double> blk, r, f, pval, oval;
+    DevBuf<int> pcol, ocol;
+    DevBuf<uint8_t> dmask;
+    blk.ensure((size_t)m * R + R, 0, st); f.ensure(nbat * 2 * R, 0, st);
+    pval.ensure((size_t)nblk * 2 * R, 0, st); pcol.ensure((size_t)nblk * 2 * R, 0, st);
+    oval.ensure(nbat * 2 * R, 0, st); ocol.ensure(nbat * 2 * R, 0, st);
+    r.upload(du.r_int, st);
+    if (var_is_int) {  // by variable: the structural variables, then the slack of every row (as add_gmi_cuts)
+        std::vector<uint8_t> mask((size_t)N, 0);
+        for (int j = 0; j < num_vars; ++j) mask[j] = var_is_int[j] ? 1 : 0;
+        if (con_is_int)
+            for (size_t c = 0; c < h_cons_row.size(); ++c)
+                if (h_cons_row[c] >= 0) mask[(size_t)num_vars + h_cons_row[c]] = con_is_int[c] ? 1 : 0;
+        dmask.upload(mask, st);
+    }
+    BranchBufs bb{};
+    bb.mask = var_is_int ? dmask.p : nullptr;
+    bb.pval = pval.p; bb.pcol = pcol.p;
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
+    launch_branch_heads(dv, ctx.dev(0), f.p, (int)nbat, st);
+    for (size_t q = 0; q < nbat; ++q) {
+        RangingBufs b = ctx.bufs(q, blk.p);
+        b.r = r.p;
+        bb.f = f.p + q * 2 * R;
+        bb.oval = oval.p + q * 2 * R; bb.ocol = ocol.p + q * 2 * R;
+        launch_branch_batch(dv, g, b, bb, ctx.count(q), ctx.host(q), st);
+    }
+    HIPCHECK(hipEventRecord(ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    std::vector<double> hv(nbat * 2 * R);
+    std::vector<int> hc(nbat * 2 * R);
+    HIPCHECK(hipMemcpyAsync(hv.data(), oval.p, sizeof(double) * hv.size(), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(hc.data(), ocol.p, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    std::vector<int64_t> cons_of_row((size_t)m, -1);
+    for (size_t c = 0; c < h_cons_row.size(); ++c)
+        if (h_cons_row[c] >= 0) cons_of_row[h_cons_row[c]] = (int64_t)c;
+    auto column = [&](int v) -> int64_t { return v < 0 ? -1 : (v < num_vars ? (int64_t)v : (int64_t)num_vars + cons_of_row[v - num_vars]); };
+    for (size_t q = 0; q < solve.size(); ++q) {
+        const size_t t = solve[q].second;
+        down[t] = hv[2 * q];
+        up[t] = hv[2 * q + 1];
+        down_col[t] = column(hc[2 * q]);
+        up_col[t] = column(hc[2 * q + 1]);
+    }
+    // algorithmic bytes: the block and the pass over A (ReqContext); per batch and variable its location, flags, reduced cost, value and
+    // mark (22 bytes), and the partials written, then read (12 bytes per slot, twice)
+    info.batches = nbat;
+    info.bytes = ctx.block_bytes((size_t)m) + ctx.pass_bytes((double)h_rcol.size()) +
+                 (double)nbat * (22.0 * N + 24.0 * 2 * R * (double)nblk);
+    info.device_ms = ev.ms();
+}
+
 // ------------------------------------------------------------------ reading the tableau (tableau.inc)
 // Nothing here writes solver state: the kernels write private buffers, the pending rank-1 terms are applied, not folded, the compact
 // factor is not re-peeled; Ctl, d, rv and the work vectors are untouched.

@@ -592,6 +592,21 @@ void launch_ranging_batch(const DevView& dv, const Geom& g, const RangingBufs& b
 int ranging_blocks(const Geom& g, int kind, int N);  // workgroups of the batch's sweep (= rows of RangingBufs.part)
 // the block of one batch alone (rows / nucleus columns of B^-1 of its requests), without the ratio-test pass
 void launch_ranging_block(const DevView& dv, const Geom& g, const RangingBufs& b, int kind, int nreq, const int* h_req, hipStream_t st);
+// branching penalties (branch.inc): the block of launch_ranging_block (kind 0), then one dual ratio test per batch with the entering columns
+struct BranchBufs {
+    const uint8_t* mask;  // N: 1 = integer column (structural variables, then the slacks by row); nullptr: nothing is strengthened
+    const double* f;      // 2 RG_BATCH per batch: (f_dn, f_up) per request (launch_branch_heads)
+    double* pval;         // blocks x 2 RG_BATCH: per-block minimum candidate (down, up) per request
+    int* pcol;            // blocks x 2 RG_BATCH: its column
+    double* oval;         // 2 RG_BATCH per batch: (down, up) per request
+    int* ocol;            // 2 RG_BATCH per batch: the minimising columns (-1: empty set)
+};
+// the fractions of all nbat batches of a call in one launch (req: RG_BATCH per batch, f: 2 RG_BATCH per batch)
+void launch_branch_heads(const DevView& dv, const int* req, double* f, int nbat, hipStream_t st);
+// one batch of at most RG_BATCH basic requests (b.req, b.r and the SolveBufs part as for cost ranging; b.part / b.out unused);
+// ranging_blocks(g, 0, N) workgroups = rows of pval / pcol
+void launch_branch_batch(const DevView& dv, const Geom& g, const RangingBufs& b, const BranchBufs& bb, int nreq, const int* h_req,
+                         hipStream_t st);
 // Sparse rows out of a dense block, one batch of at most RG_BATCH basic positions (tableau.inc, cuts.inc, gmi.inc).  Phase 1,
 // launch_rows_generate: the rows of B^-1 (b.blk, b.req, the SolveBufs part as for ranging), one pass over A that leaves the dense block
 // dense[N][RG_BATCH] by variable, the scanned offsets off[RG_BATCH * cut_segments(N)] (cnt: same size, sums: the scan's scratch), the row

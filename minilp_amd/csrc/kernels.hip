@@ -5623,6 +5623,7 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
 }
 #include "duals.inc"  // dual values, reduced costs and the KKT certificate (side-effect free reads of the solver state)
 #include "ranging.inc"  // cost / rhs ranging: batched rows / columns of B^-1 and one ratio-test pass per batch (side-effect free)
+#include "branch.inc"  // branching penalties: the ranging block, then one dual ratio test per batch with the entering columns (side-effect free)
 #include "cuts.inc"  // a round of cuts: 16 Gomory rows per pass over A as sparse rows, and the CSC re-layout for R appended rows
 #include "gmi.inc"  // a round of Gomory mixed-integer cuts: the pass of the Gomory round with the per-column classification at its end (side-effect free)
 #include "tableau.inc" // reading the tableau: 16 rows of B^-1 A as sparse rows, 16 solves with dense right-hand sides per pass over W0 (side-effect free)
