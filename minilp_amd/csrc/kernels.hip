@@ -995,17 +995,22 @@ __global__ void __launch_bounds__(64) k_ftran_prep(DevView v, int derive_primal)
     ftran_prep_wave(v, c, threadIdx.x, derive_primal);
 }
 // push of -x * (column of the basic variable at `p`) into the singleton positions
+// (the lane's entries e, e + G, ... < end of a column)
 template <int G>
-__device__ __forceinline__ void push_F(const DevView& v, int p, double x, double* out_pos, int gl, Ctl* list_ctl = nullptr) {
-    int var = v.basic_vars[p];
-    int end = v.csc_ptr[var + 1];
-    for (int e = v.csc_ptr[var] + gl; e < end; e += G) {
+__device__ __forceinline__ void push_F_entries(const DevView& v, int e, int end, double x, double* out_pos, Ctl* list_ctl) {
+    for (; e < end; e += G) {
         const RowInfo ri = v.rowinfo[v.csc_row[e]];
         if (ri.kslot < 0) {
             unsafeAtomicAdd(&out_pos[ri.pos], -v.csc_val[e] * x / ri.diag);
             if (list_ctl) aq_list_add(v, list_ctl, ri.pos);
         }
     }
+}
+template <int G>
+__device__ __forceinline__ void push_F(const DevView& v, int p, double x, double* out_pos, int gl, Ctl* list_ctl = nullptr) {
+    int var = v.basic_vars[p];
+    int end = v.csc_ptr[var + 1];
+    push_F_entries<G>(v, v.csc_ptr[var] + gl, end, x, out_pos, list_ctl);
 }
 // Deterministic FTRAN of a large model with a small nucleus (sharded solves of config 4: DESIGN.md §6): the pull per singleton
 // row walks every entry of the row, 10^7 entries per pivot whatever the nucleus size.  The gather MARKS the singleton positions
@@ -2239,10 +2244,10 @@ __global__ void __launch_bounds__(BLK) k_btran(DevView v, int n_gather, int afte
 // effects (pivot scalars, entries on singleton rows, the list for the records).  Used while the delayed-update mode is
 // off and every column / row fits the LDS list (Geom.head_fused).
 constexpr int HEAD_CAP = 1024;
-__device__ void ftran_head_lds(const DevView& v, Ctl* c, int lane, int derive_primal, bool primary, int* ls, double* la, int* ln) {
+// (q, var = nb_vars[q] and the column's range [base, end) come from the caller, which loads them beside its own chain)
+__device__ void ftran_head_lds(const DevView& v, Ctl* c, int lane, int derive_primal, bool primary, int q, int var, int base, int end, int* ls,
+                               double* la, int* ln) {
     IterState* it = &c->it;
-    const int q = it->q;
-    const int var = v.nb_vars[q];
     if (primary && lane == 0) {
         it->entering_var = var;
         if (derive_primal) {  // solver.rs:741-748
@@ -2257,7 +2262,6 @@ __device__ void ftran_head_lds(const DevView& v, Ctl* c, int lane, int derive_pr
     // other blocks of this launch push -F alpha_K into the singleton positions with atomics while block 0 lands the
     // column's own singleton-row entries: both must then be atomic adds onto the zeroed vector
     const bool atomic_land = !v.pb_on && !v.det_pull;
-    const int base = v.csc_ptr[var], end = v.csc_ptr[var + 1];
     int cnt = 0;
     for (int e0 = base; e0 < end; e0 += 64) {
         const int e = e0 + lane;
@@ -2432,30 +2436,73 @@ __global__ void __launch_bounds__(BLK) k_ftran_gather_lrh(DevView v, int fpk) {
 }
 template <int G>
 __global__ void __launch_bounds__(BLK) k_ftran_fused(DevView v, int derive_primal) {
+    // Everything but the multiplier alpha_K[slot] of the F push is independent of the entering column: every wave reads the control
+    // block in one clause and then walks its slot's chain (position -> basic variable -> column range -> the lane's first FP_E
+    // entries -> their row maps) BESIDE the head instead of behind it; the head wave gets q's variable and column range from the same
+    // clauses.  Behind the barrier only the W gather and the atomics are left.  Nothing is read through a map entry of a slot >= k
+    // (stale).  The marks of the deterministic pull (mark_F) keep their loop; the blocked push has no push here.
+    constexpr int FP_E = 2;  // prefetched entries per lane (G = 64: columns of up to 128 entries); the rest go through the loop
     Ctl* c = v.ctl;
-    if (c->halt || c->it.status != ITER_PIVOT) return;
+    const int halt = c->halt, status = c->it.status, k = c->k, q = c->it.q;
+    if (halt || status != ITER_PIVOT) return;
     KMARK0(c, 0);
     __shared__ int s_ls[HEAD_CAP];
     __shared__ double s_la[HEAD_CAP];
     __shared__ int s_n;
-    if (threadIdx.x < 64) ftran_head_lds(v, c, threadIdx.x, derive_primal, blockIdx.x == 0, s_ls, s_la, &s_n);
-    __syncthreads();
     const int slot = (blockIdx.x * BLK + threadIdx.x) / G;
     const int gl = threadIdx.x & (G - 1);
-    if (slot >= c->k) return;
+    const bool head = threadIdx.x < 64, live = slot < k;
+    const bool push = live && !v.pb_on && !v.det_pull;
+    const int p = live ? v.pos_of_kslot[slot] : 0;
+    const int qvar = head ? v.nb_vars[q] : 0;
+    const int fvar = push ? v.basic_vars[p] : 0;
+    int qbase = 0, qend = 0, e0 = 0, fend = 0;
+    if (head) {
+        qbase = v.csc_ptr[qvar];
+        qend = v.csc_ptr[qvar + 1];
+    }
+    if (push) {
+        e0 = v.csc_ptr[fvar] + gl;
+        fend = v.csc_ptr[fvar + 1];
+    }
+    int frow[FP_E];
+    double fval[FP_E];
+    RowInfo fri[FP_E];
+#pragma unroll
+    for (int u = 0; u < FP_E; ++u) {
+        const bool in = e0 + u * G < fend;  // (never without `push`)
+        frow[u] = in ? v.csc_row[e0 + u * G] : -1;
+        fval[u] = in ? v.csc_val[e0 + u * G] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < FP_E; ++u) {
+        fri[u] = RowInfo{0.0, -1, 0};
+        if (frow[u] >= 0) fri[u] = v.rowinfo[frow[u]];
+    }
+    if (head) ftran_head_lds(v, c, threadIdx.x, derive_primal, blockIdx.x == 0, q, qvar, qbase, qend, s_ls, s_la, &s_n);
+    __syncthreads();
+    if (!live) return;
     const int n = s_n;
     double acc = 0.0;
     const double* wrow = v.W + (size_t)slot * v.ld;
     for (int j = gl; j < n; j += G) acc += s_la[j] * wrow[s_ls[j]];
     acc = group_sum<G>(acc);
-    const int p = v.pos_of_kslot[slot];
     if (gl == 0) {
         v.aK[slot] = acc;
         v.alpha_q[p] = acc;
         if (acc != 0.0 && aq_listing(v)) aq_list_add(v, c, p);
     }
-    if (acc != 0.0 && !v.pb_on && !v.det_pull) push_F<G>(v, p, acc, v.alpha_q, gl, aq_listing(v) ? c : nullptr);
-    else if (acc != 0.0 && v.det_pull && v.fmark) mark_F<G>(v, p, gl);
+    if (acc != 0.0 && push) {
+        Ctl* list_ctl = aq_listing(v) ? c : nullptr;
+#pragma unroll
+        for (int u = 0; u < FP_E; ++u) {  // (push_F_entries on the entries held in registers)
+            if (frow[u] >= 0 && fri[u].kslot < 0) {
+                unsafeAtomicAdd(&v.alpha_q[fri[u].pos], -fval[u] * acc / fri[u].diag);
+                if (list_ctl) aq_list_add(v, list_ctl, fri[u].pos);
+            }
+        }
+        push_F_entries<G>(v, e0 + FP_E * G, fend, acc, v.alpha_q, list_ctl);
+    } else if (acc != 0.0 && v.det_pull && v.fmark) mark_F<G>(v, p, gl);
 }
 __device__ void btran_head_lds(const DevView& v, Ctl* c, int lane, int derive_dual, bool primary, int* ls, double* la, int* ln) {
     IterState* it = &c->it;
@@ -3364,41 +3411,79 @@ __global__ void __launch_bounds__(BLK) k_fused_w(DevView v) {
 #pragma unroll 1
     for (int sub = 0; sub < RL; ++sub) {
         double tacc[TR];
+        if constexpr (DO_UPDATE) {
+            // Eager update: the loads of eight rows (W words, tK, aK) go out in one group, unconditionally — a row or a column past k
+            // reads a clamped address and is masked — then the arithmetic and the stores.  Row by row the loads of row a + 1 could not
+            // pass the stores of row a (tK / aK may alias W for all the compiler knows), and a wait for a load also waits for the store
+            // acknowledgements in front of it: eight dependent round trips per tile.  A thread only touches its own elements, so
+            // loading all rows before storing any is safe; per element and per accumulator the operations and their order (rows
+            // ascending) are the ones of the row-by-row form.  (ld is even and the pad past an odd k is allocated.)
+            constexpr int GR = 8;
+            const int c0 = one0 ? cidx[0] : col0, c2 = one1 ? cidx[2] : col0;
 #pragma unroll
-        for (int a = 0; a < TR; ++a) {
-            int row = row0 + sub * TR + a;
-            tacc[a] = 0.0;
-            if (row >= k) continue;
-            double* wp = v.W + (size_t)row * ld;
-            double w[4] = {0.0, 0.0, 0.0, 0.0};
-            if (pair0) {
-                double2 t = fw_load2<NT>(wp + cidx[0]);
-                w[0] = t.x;
-                w[1] = t.y;
-            } else if (one0) {
-                w[0] = wp[cidx[0]];
-            }
-            if (pair1) {
-                double2 t = fw_load2<NT>(wp + cidx[2]);
-                w[2] = t.x;
-                w[3] = t.y;
-            } else if (one1) {
-                w[2] = wp[cidx[2]];
-            }
-            if (WITH_TAU) tacc[a] = w[0] * rk[0] + w[1] * rk[1] + w[2] * rk[2] + w[3] * rk[3];
-            if (WITH_V) {
-                double t = v.tK[row];
+            for (int g0 = 0; g0 < TR; g0 += GR) {
+                double2 wa[GR], wb[GR];
+                double tk[GR], ak[GR];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) vacc[j] += w[j] * t;
-            }
-            if (DO_UPDATE) {
-                double u = (v.aK[row] - (row == rslot ? 1.0 : 0.0)) * inv_alpha;
+                for (int a = 0; a < GR; ++a) {
+                    const int row = row0 + sub * TR + g0 + a;
+                    const int rc = row < k ? row : k - 1;
+                    const double* wp = v.W + (size_t)rc * ld;
+                    wa[a] = fw_load2<NT>(wp + c0);
+                    wb[a] = fw_load2<NT>(wp + c2);
+                    tk[a] = WITH_V ? v.tK[rc] : 0.0;
+                    ak[a] = v.aK[rc];
+                }
 #pragma unroll
-                for (int j = 0; j < 4; ++j) w[j] -= u * rk[j];
-                if (pair0) fw_store2<NT>(wp + cidx[0], w[0], w[1]);
-                else if (one0) wp[cidx[0]] = w[0];
-                if (pair1) fw_store2<NT>(wp + cidx[2], w[2], w[3]);
-                else if (one1) wp[cidx[2]] = w[2];
+                for (int a = 0; a < GR; ++a) {
+                    const int row = row0 + sub * TR + g0 + a;
+                    tacc[g0 + a] = 0.0;
+                    if (row >= k) continue;
+                    double* wp = v.W + (size_t)row * ld;
+                    double w[4] = {one0 ? wa[a].x : 0.0, pair0 ? wa[a].y : 0.0, one1 ? wb[a].x : 0.0, pair1 ? wb[a].y : 0.0};
+                    if (WITH_TAU) tacc[g0 + a] = w[0] * rk[0] + w[1] * rk[1] + w[2] * rk[2] + w[3] * rk[3];
+                    if (WITH_V) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) vacc[j] += w[j] * tk[a];
+                    }
+                    double u = (ak[a] - (row == rslot ? 1.0 : 0.0)) * inv_alpha;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) w[j] -= u * rk[j];
+                    if (pair0) fw_store2<NT>(wp + cidx[0], w[0], w[1]);
+                    else if (one0) wp[cidx[0]] = w[0];
+                    if (pair1) fw_store2<NT>(wp + cidx[2], w[2], w[3]);
+                    else if (one1) wp[cidx[2]] = w[2];
+                }
+            }
+        } else {
+            // (read-only passes: row by row)
+#pragma unroll
+            for (int a = 0; a < TR; ++a) {
+                int row = row0 + sub * TR + a;
+                tacc[a] = 0.0;
+                if (row >= k) continue;
+                double* wp = v.W + (size_t)row * ld;
+                double w[4] = {0.0, 0.0, 0.0, 0.0};
+                if (pair0) {
+                    double2 t = fw_load2<NT>(wp + cidx[0]);
+                    w[0] = t.x;
+                    w[1] = t.y;
+                } else if (one0) {
+                    w[0] = wp[cidx[0]];
+                }
+                if (pair1) {
+                    double2 t = fw_load2<NT>(wp + cidx[2]);
+                    w[2] = t.x;
+                    w[3] = t.y;
+                } else if (one1) {
+                    w[2] = wp[cidx[2]];
+                }
+                if (WITH_TAU) tacc[a] = w[0] * rk[0] + w[1] * rk[1] + w[2] * rk[2] + w[3] * rk[3];
+                if (WITH_V) {
+                    double t = v.tK[row];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) vacc[j] += w[j] * t;
+                }
             }
         }
         if (WITH_TAU) {
