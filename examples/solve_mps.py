@@ -4,6 +4,7 @@ minimise, print the objective and the non-zero variables.
 
     python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--tableau VAR] [--gomory-rounds K]
                                  [--gmi-rounds K [--continuous NAME,...]] [--branch-penalties [--continuous NAME,...]]
+                                 [--cutoff VALUE [--continuous NAME,...]]
 
 --ranging adds a sensitivity table: per variable its value, basis status, reduced cost and cost range; per row its dual value and
 rhs range (rows in file order).  --tableau VAR prints the tableau row of the basic variable VAR (by name): its non-zero coefficients on the
@@ -14,7 +15,9 @@ K rounds of Gomory mixed-integer cuts instead (one add_gmi_cuts call per round o
 every structural variable is integer unless listed in --continuous, the slacks are continuous; it prints the bound, the cuts emitted and
 skipped and the counters after each round.  --branch-penalties prints, for every basic structural variable with a fractional value at the
 LP optimum, the one-pivot bounds of its down and up branch (plain, and with Tomlin's strengthening: every structural variable is integer
-unless listed in --continuous, the slacks are continuous), the child bounds they give and the columns that would enter.
+unless listed in --continuous, the slacks are continuous), the child bounds they give and the columns that would enter.  --cutoff VALUE
+prints the bounds that the reduced costs imply once an incumbent of objective VALUE is known (Solution.cutoff_bounds; every structural
+variable is integer unless listed in --continuous): per tightened variable its bounds and whether it can be fixed.
 
 Runs on the MI355X engine (libminilp_hip.so); there is no CPU back end.  `run(B, ...)` takes the module that
 provides the reference's API so that the tests can drive the same code with their checker."""
@@ -26,7 +29,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False):
+def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False, cutoff=None):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -91,6 +94,23 @@ def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0,
             print("%-12s %12.8g %14.8g %14.8g %14.8g %14.8g %14.8g %14.8g   %s, %s" %
                   (names[v], plain["frac"][v], plain["down"][v], plain["up"][v], strong["down"][v], strong["up"][v],
                    obj + sg * plain["down"][v], obj + sg * plain["up"][v], col(plain["down_col"][v]), col(plain["up_col"][v])))
+    if cutoff is not None:
+        unknown = [nm for nm in continuous if nm not in f.variables]
+        if unknown:
+            print("cutoff: no variable named %s" % ", ".join(unknown))
+            return 1
+        marks = [True] * len(f.variables)
+        for nm in continuous:
+            marks[f.variables[nm]] = False
+        names = {v: n for n, v in f.variables.items()}
+        cv, clo, chi, pruned = sol.cutoff_bounds(cutoff, marks)
+        if pruned:
+            print("cutoff %.12g: the LP bound %.12g is already worse, nothing to tighten" % (cutoff, sol.objective()))
+        else:
+            print("cutoff %.12g: %d variables tightened, %d of them fixed, %s" % (cutoff, len(cv), int((clo == chi).sum()), sol.fix_info()))
+            print("%-12s %14s %14s   %s" % ("variable", "lower", "upper", ""))
+            for v, a, b in zip(cv, clo, chi):
+                print("%-12s %14.8g %14.8g   %s" % (names[int(v)], a, b, "fixed" if a == b else ""))
     for k in range(gomory_rounds):
         x = sol.values()
         vs, _ = sol.basis_status()
@@ -142,13 +162,15 @@ def main():
     ap.add_argument("--gmi-rounds", type=int, default=0, metavar="K",
                     help="K rounds of Gomory mixed-integer cuts over the fractional basic integer variables (one add_gmi_cuts call per round)")
     ap.add_argument("--continuous", default="", metavar="NAME,...",
-                    help="with --gmi-rounds / --branch-penalties: the variables that are NOT integer (all others are; slacks are continuous)")
+                    help="with --gmi-rounds / --branch-penalties / --cutoff: the variables that are NOT integer (all others are; slacks are continuous)")
     ap.add_argument("--branch-penalties", action="store_true",
                     help="print the one-pivot branching bounds of the fractional basic variables (Solution.branch_penalties)")
+    ap.add_argument("--cutoff", type=float, default=None, metavar="VALUE",
+                    help="print the bounds the reduced costs imply for an incumbent of objective VALUE (Solution.cutoff_bounds)")
     a = ap.parse_args()
     import minilp_amd as B
     return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau, a.gmi_rounds, [nm for nm in a.continuous.split(",") if nm],
-               a.branch_penalties)
+               a.branch_penalties, a.cutoff)
 
 
 if __name__ == "__main__":

@@ -7,11 +7,15 @@ rows = 2, Stoer–Wagner min cut to find violated subtour rows (cut weight < 2 -
 branching with `fix_var` on cloned solutions.  Written against the Problem/Solution API only, so it
 runs on any backend module that mirrors it (`minilp_amd` on the GPU, or the CPU oracle in tests).
 
-usage: python examples/tsp.py tests/golden/bn130.tsp [--nodes N] [--max-bb-nodes K] [--branching fractional|penalties]
+usage: python examples/tsp.py tests/golden/bn130.tsp [--nodes N] [--max-bb-nodes K] [--branching fractional|penalties] [--rc-fixing]
 
 --branching penalties picks the branching variable by the one-pivot bounds of `Solution.branch_penalties` (the product rule on the down
 and up penalty) instead of the most fractional one, and skips a side whose penalty already proves it infeasible or no better than the
 best tour, without cloning the solution.
+
+--rc-fixing fixes edge variables by their reduced costs (`Solution.fix_by_reduced_cost`) after every node LP once a tour is known: an
+edge whose reduced cost exceeds the gap to the best tour cannot leave its bound in a better tour.  The fixings are local to the node;
+its children inherit them through `clone`.
 """
 import argparse
 import math
@@ -84,7 +88,7 @@ def stoer_wagner_py(w):
 
 
 class TspSolver:
-    def __init__(self, backend, pts, log=None, batch_cuts=False, branching="fractional"):
+    def __init__(self, backend, pts, log=None, batch_cuts=False, branching="fractional", rc_fixing=False):
         self.B = backend
         assert branching in ("fractional", "penalties")
         self.branching = branching  # "penalties": Solution.branch_penalties chooses the variable and prunes sides (needs a back end that has it)
@@ -97,6 +101,9 @@ class TspSolver:
         self.stats = dict(lp_solves=1, cuts=0, fix_calls=0, clones=0, bb_nodes=0)
         if branching == "penalties":
             self.stats.update(penalty_calls=0, skipped_sides=0)
+        self.rc_fixing = rc_fixing  # reduced-cost fixing at every node once a tour is known (needs a back end that has it)
+        if rc_fixing:
+            self.stats.update(rc_calls=0, rc_fixed=0)
         n = self.n
         self.edge_var = -np.ones((n, n), dtype=np.int64)
         p = backend.Problem(backend.MINIMIZE)
@@ -232,6 +239,10 @@ class TspSolver:
             obj = cur.objective()
             if obj > best_cost:
                 continue
+            if self.rc_fixing and best_cost < math.inf:  # every edge variable is integer; the fixed edges already sit at their value
+                cur, fixed = cur.fix_by_reduced_cost(best_cost, integer_vars=np.ones(self.n * (self.n - 1) // 2, dtype=bool))
+                self.stats["rc_calls"] += 1
+                self.stats["rc_fixed"] += len(fixed)
             pick = self.choose_branch(cur)
             if pick is not None:
                 stack.append(dict(start=cur, var=pick[0], pen=pick[1], start_val=0 if cur[pick[0]] < 0.5 else 1, cur=None))
@@ -304,13 +315,16 @@ def main():
                     help="separate all violated subtour constraints of an LP solution and add them with one add_constraints call")
     ap.add_argument("--branching", choices=["fractional", "penalties"], default="fractional",
                     help="penalties: choose the branching variable by Solution.branch_penalties and skip sides its bounds rule out")
+    ap.add_argument("--rc-fixing", action="store_true",
+                    help="fix edge variables by their reduced costs (Solution.fix_by_reduced_cost) after every node LP once a tour is known")
     a = ap.parse_args()
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import minilp_amd as backend  # the MI355X engine; there is no CPU back end (tests pass their checker to TspSolver)
     name, pts = read_tsplib(a.file, a.nodes)
     t0 = time.time()
-    s = TspSolver(backend, pts, log=lambda m: print("[%.1fs] %s" % (time.time() - t0, m), flush=True), batch_cuts=a.batch_cuts, branching=a.branching)
+    s = TspSolver(backend, pts, log=lambda m: print("[%.1fs] %s" % (time.time() - t0, m), flush=True), batch_cuts=a.batch_cuts, branching=a.branching,
+                  rc_fixing=a.rc_fixing)
     cost, tour = s.solve(a.max_bb_nodes)
     print("problem %s (%d cities): tour cost %.10f, %s, %.1fs" % (name, len(pts), cost, s.stats, time.time() - t0))
     print("tour:", " ".join(str(int(t) + 1) for t in tour))  # Tour::to_string (tsp.rs:161-167): 1-based city numbers

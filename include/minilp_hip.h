@@ -49,6 +49,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * additive in the same way; mlp_cut_info keeps its 80 bytes. */
 /* Still version 5: the branching penalties (mlp_solution_branch_penalties, mlp_branch_info with its own mlp_branch_info_size()) are
  * additive in the same way. */
+/* Still version 5: the reduced-cost bounds and the batched fixing (mlp_solution_cutoff_bounds, mlp_solution_fix_vars,
+ * mlp_solution_unfix_vars, mlp_fix_info with its own mlp_fix_info_size()) are additive in the same way. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -486,6 +488,69 @@ typedef struct mlp_branch_info {
 } mlp_branch_info;
 int mlp_solution_branch_info(const mlp_solution* s, mlp_branch_info* out);
 uint64_t mlp_branch_info_size(void);
+
+/* ---- Reduced-cost bounds from a cutoff, and fixing many variables in one call ------------------------------------------------------------
+ * Once an incumbent exists, the reduced cost of a non-basic column bounds how far the column can move before the objective of this LP
+ * passes the incumbent (weak duality).  mlp_solution_cutoff_bounds lists every structural variable whose bound tightens that way;
+ * mlp_solution_fix_vars applies such a list — or a dive, or a multi-variable branch — in one call; mlp_solution_unfix_vars releases one.
+ *
+ * mlp_solution_cutoff_bounds (a read).  Internal form as above: min c^.x with c^ = -c for a Maximize problem.  The gap is
+ *   g = cutoff - mlp_solution_objective() for a Minimize problem and mlp_solution_objective() - cutoff for a Maximize problem, formed
+ *   exactly, without a tolerance.  g < 0: the node is worse than the cutoff, *pruned = 1, *count = 0, status 0.  g = +inf lists nothing.
+ *   d_j is the internal reduced cost of column j as the engine's pricing holds it on the device; it agrees with
+ *   mlp_solution_reduced_costs (turned to the internal sense) to rounding.  Structural variables only: a slack has no bound to apply.
+ *     basic, MLP_NB_FREE and MLP_NB_FIXED columns impose nothing;
+ *     at lower with d_j > 0:  t = g / d_j,   new_hi = lo_j + t;     at upper with d_j < 0:  t = g / |d_j|,   new_lo = hi_j - t;
+ *     a reduced cost of the wrong sign (-1e-13 at a lower bound) counts as 0, as in the cost ranging, and gives no entry;
+ *     var_is_int[j] != 0 and xN_j == floor(xN_j) exactly (the test of Tomlin's strengthening above): t is replaced by floor(t + 1e-9)
+ *       — the 1e-9 can only loosen the bound.  var_is_int == NULL: no variable is integer (num_vars is still checked).
+ *   A variable is listed only if the bound strictly tightens (new_hi < hi_j, or new_lo > lo_j).  An entry carries BOTH bounds,
+ *   (lo_j, new_hi) or (new_lo, hi_j); a tightened bound that reaches the other bound is clamped to it, so such an entry has
+ *   new_lo == new_hi == xN_j: the variable can be fixed.  Bounds are in the user's terms, no sign is turned for Maximize.
+ *   Entries come in ascending variable number; *count is always set; cap < *count is MLP_EINVAL with nothing written (cap = num_vars
+ *   always suffices).  The list is bit-identical from run to run (one classifying pass, compaction by ballots and prefix counts, no
+ *   atomics).  The call is a read, side-effect free like the ranging: the host reads back the count and O(count) entries.
+ *   MLP_EINVAL: a solution that is not solved (budget-limited or paused: the bound is false at a dual-infeasible basis), a NaN cutoff,
+ *   num_vars != mlp_solution_num_vars, a sharded solution, NULL handle / count / pruned.
+ *
+ * mlp_solution_fix_vars leaves the model that mlp_solution_fix_var(vars[i], vals[i]) for i = 0, 1, ... would leave; only the pivot path
+ *   differs, so the optimum value is the same.  Checked before anything changes: a variable out of range or listed twice is MLP_EINVAL;
+ *   a value outside [lo, hi] is status 1 (Infeasible), as for the single form.  Then
+ *     1. all requests NON-BASIC at the basis the call finds are served together: r = sum_j (val_j - xN_j) a_j is formed on the device in
+ *        an order that does not depend on the order of the list, ONE FTRAN follows, x_B -= B^-1 r, the objective moves by
+ *        sum_j (val_j - xN_j) d_j (ascending variable number), xN_j = val_j and the columns become MLP_NB_FIXED.  When every variable
+ *        already sits at its value — reduced-cost fixing — there is no solve: only the flags are written, and values and objective keep
+ *        their bits;
+ *     2. each BASIC request, in list order, leaves the basis by the forced dual pivot of the single form (an Infeasible verdict of that
+ *        pivot is status 1); the columns fixed in step 1 cannot enter;
+ *     3. feasibility is restored ONCE (status 1 if the fixings are infeasible together).
+ * mlp_solution_unfix_vars applies the rule of mlp_solution_unfix_var to every request — a basic or not-fixed variable is skipped (this
+ *   includes a second mention), the status of a released one is rebuilt from its value against its bounds — and runs ONE primal re-solve
+ *   if any was released; *unfixed (may be NULL) = the released count.  If none was, the solution is left exactly as it is.
+ * Both: n == 0 is a successful no-op; any non-zero status frees the solution and sets *s = NULL; a sharded solution is MLP_EINVAL; a
+ *   pivot budget is lifted; cached duals and ranges are dropped.
+ * mlp_fix_info: what the last of these three calls on this solution did (zeros before the first).  Only grows at its end;
+ *   mlp_fix_info_size() is its size as the library was built. */
+int mlp_solution_cutoff_bounds(const mlp_solution* s, double cutoff, const uint8_t* var_is_int, uint32_t num_vars, uint32_t* vars,
+                               double* new_lo, double* new_hi, uint64_t cap, uint64_t* count, int* pruned);
+int mlp_solution_fix_vars(mlp_solution** s, const uint32_t* vars, const double* vals, uint64_t n);
+int mlp_solution_unfix_vars(mlp_solution** s, const uint32_t* vars, uint64_t n, uint64_t* unfixed);
+typedef struct mlp_fix_info {
+    uint64_t requests;       /* fix_vars / unfix_vars: variables listed */
+    uint64_t nonbasic;       /* fix_vars: of them non-basic at the basis the call found (served together) */
+    uint64_t shifted;        /* ... of them with val != xN */
+    uint64_t forced_pivots;  /* fix_vars: basic requests, one forced dual pivot each */
+    uint64_t solves;         /* fix_vars: FTRANs of the non-basic requests, 0 or 1 */
+    uint64_t unfixed;        /* unfix_vars: variables released */
+    uint64_t listed;         /* cutoff_bounds: entries */
+    uint64_t listed_fixed;   /* ... of them with new_lo == new_hi */
+    uint64_t pivots;         /* iterations of the call: the forced pivots and the re-solve */
+    double bytes;            /* algorithmic bytes of the batched device work (without the re-solve) */
+    double device_ms;        /* its time on the device (HIP events around the launches) */
+    double wall_ms;          /* the whole mutator call on the host, re-solve included (0 for the read) */
+} mlp_fix_info;
+int mlp_solution_fix_info(const mlp_solution* s, mlp_fix_info* out);
+uint64_t mlp_fix_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

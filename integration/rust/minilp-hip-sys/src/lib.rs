@@ -117,6 +117,11 @@ extern "C" {
     pub fn mlp_solution_branch_penalties(s: *const mlp_solution, vars: *const u32, n: u64, var_is_int: *const u8, num_vars: u32, con_is_int: *const u8, num_constraints: u64, down: *mut f64, up: *mut f64, down_col: *mut i64, up_col: *mut i64, frac: *mut f64, status: *mut i32) -> c_int;
     pub fn mlp_solution_branch_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
     pub fn mlp_branch_info_size() -> u64;
+    pub fn mlp_solution_cutoff_bounds(s: *const mlp_solution, cutoff: c_double, var_is_int: *const u8, num_vars: u32, vars: *mut u32, new_lo: *mut f64, new_hi: *mut f64, cap: u64, count: *mut u64, pruned: *mut c_int) -> c_int;
+    pub fn mlp_solution_fix_vars(s: *mut *mut mlp_solution, vars: *const u32, vals: *const f64, n: u64) -> c_int;
+    pub fn mlp_solution_unfix_vars(s: *mut *mut mlp_solution, vars: *const u32, n: u64, unfixed: *mut u64) -> c_int;
+    pub fn mlp_solution_fix_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
+    pub fn mlp_fix_info_size() -> u64;
     // reading the tableau: rows / columns of B^-1 A and of B^-1, solves with the basis (additive: the ABI version stays 5)
     pub fn mlp_solution_num_rows(s: *const mlp_solution) -> u64;
     pub fn mlp_solution_basis_head(s: *const mlp_solution, head: *mut u64, num_rows: u64) -> c_int;

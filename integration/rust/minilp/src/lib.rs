@@ -417,6 +417,31 @@ impl Solution {
         (0..n).map(|t| (down[t], up[t], col(dcol[t]), col(ucol[t]), frac[t])).collect()
     }
 
+    /// Bounds that the reduced costs imply once an incumbent of objective value `cutoff` is known: `None` if this LP is already
+    /// worse than the cutoff (prune the node), else every variable whose bound tightens as `(variable, lo, hi)` in ascending order;
+    /// `lo == hi` means the variable can be fixed ([`fix_vars`](Self::fix_vars)).  `integer_vars` rounds the bound of a marked
+    /// variable to whole steps (extension: no counterpart in the reference; semantics in `minilp_hip.h`).
+    ///
+    /// # Panics
+    ///
+    /// Will panic if the mask has the wrong length, the cutoff is NaN or the solution is not solved.
+    pub fn cutoff_bounds(&self, cutoff: f64, integer_vars: Option<&[bool]>) -> Option<Vec<(Variable, f64, f64)>> {
+        let vm: Option<Vec<u8>> = integer_vars.map(|m| m.iter().map(|&b| b as u8).collect());
+        let (vp, vn) = vm.as_ref().map_or((std::ptr::null(), self.num_vars as u32), |m| (m.as_ptr(), m.len() as u32));
+        let n = self.num_vars;
+        let (mut v, mut lo, mut hi) = (vec![0u32; n], vec![0.0f64; n], vec![0.0f64; n]);
+        let (mut count, mut pruned): (u64, std::os::raw::c_int) = (0, 0);
+        let st = unsafe {
+            sys::mlp_solution_cutoff_bounds(self.raw, cutoff, vp, vn, v.as_mut_ptr(), lo.as_mut_ptr(), hi.as_mut_ptr(), n as u64, &mut count,
+                                            &mut pruned)
+        };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        if pruned != 0 {
+            return None;
+        }
+        Some((0..count as usize).map(|t| (Variable(v[t] as usize), lo[t], hi[t])).collect())
+    }
+
     /// Range `(lo, hi)` of the right-hand side of a constraint (by index, in the order the constraints were added) over which the
     /// current basis stays feasible; within it the objective moves by `dual_value * delta` (extension).
     pub fn rhs_range(&self, constraint: usize) -> (f64, f64) {
@@ -553,6 +578,40 @@ impl Solution {
             .consume(|s| unsafe { sys::mlp_solution_unfix_var(s, var.0 as u32, &mut was) })
             .expect("unfix_var cannot make the problem infeasible or unbounded (lib.rs:433 unwrap)");
         (sol, was != 0)
+    }
+
+    /// [`fix_var`](Self::fix_var) for every `(variable, value)` pair in one call: the variables that are non-basic share one
+    /// FTRAN (none at all when each already sits at its value), the basic ones take one forced pivot each, and feasibility is
+    /// restored once.  The model left behind is that of the single form called pair by pair (extension: no counterpart in the
+    /// reference).
+    ///
+    /// # Errors
+    ///
+    /// Will return an error if a value lies outside the bounds of its variable or the problem becomes infeasible.
+    ///
+    /// # Panics
+    ///
+    /// Will panic if a variable is listed twice.
+    pub fn fix_vars(self, fixings: &[(Variable, f64)]) -> Result<Self, Error> {
+        assert!(fixings.iter().all(|x| x.0 .0 < self.num_vars));
+        let mut seen: Vec<usize> = fixings.iter().map(|x| x.0 .0).collect();
+        seen.sort_unstable();
+        assert!(seen.windows(2).all(|w| w[0] != w[1]), "fix_vars: a variable is listed twice");
+        let vars: Vec<u32> = fixings.iter().map(|x| x.0 .0 as u32).collect();
+        let vals: Vec<f64> = fixings.iter().map(|x| x.1).collect();
+        self.consume(|s| unsafe { sys::mlp_solution_fix_vars(s, vars.as_ptr(), vals.as_ptr(), vars.len() as u64) })
+    }
+
+    /// [`unfix_var`](Self::unfix_var) for every listed variable with one re-solve; returns the solution and how many of the
+    /// variables were really fixed (extension).
+    pub fn unfix_vars(self, vars: &[Variable]) -> (Self, usize) {
+        assert!(vars.iter().all(|x| x.0 < self.num_vars));
+        let v: Vec<u32> = vars.iter().map(|x| x.0 as u32).collect();
+        let mut released: u64 = 0;
+        let sol = self
+            .consume(|s| unsafe { sys::mlp_solution_unfix_vars(s, v.as_ptr(), v.len() as u64, &mut released) })
+            .expect("unfix_vars cannot make the problem infeasible or unbounded (lib.rs:433 unwrap)");
+        (sol, released as usize)
     }
 
     /// Add a Gomory cut constraint to the problem and return the solution.  (`lib.rs:419-423`)

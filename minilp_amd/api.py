@@ -80,6 +80,12 @@ class MlpBranchInfo(C.Structure):  # include/minilp_hip.h: mlp_branch_info (only
     _fields_ = [("requests", C.c_uint64), ("solves", C.c_uint64), ("batches", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
 
 
+class MlpFixInfo(C.Structure):  # include/minilp_hip.h: mlp_fix_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("nonbasic", C.c_uint64), ("shifted", C.c_uint64), ("forced_pivots", C.c_uint64),
+                ("solves", C.c_uint64), ("unfixed", C.c_uint64), ("listed", C.c_uint64), ("listed_fixed", C.c_uint64),
+                ("pivots", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -221,6 +227,13 @@ def lib():
     sig("mlp_solution_branch_penalties", i32, vp, pu32, u64, pu8, u32, pu8, u64, pdbl, pdbl, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
         pdbl, C.POINTER(C.c_int32))
     sig("mlp_solution_branch_info", i32, vp, C.POINTER(MlpBranchInfo))
+    sig("mlp_fix_info_size", u64)
+    if L.mlp_fix_info_size() != C.sizeof(MlpFixInfo):
+        raise ImportError(f"{_SO}: mlp_fix_info is {L.mlp_fix_info_size()} bytes, this binding {C.sizeof(MlpFixInfo)}: rebuild it")
+    sig("mlp_solution_cutoff_bounds", i32, vp, dbl, pu8, u32, pu32, pdbl, pdbl, u64, pu64, C.POINTER(i32))
+    sig("mlp_solution_fix_vars", i32, C.POINTER(vp), pu32, pdbl, u64)
+    sig("mlp_solution_unfix_vars", i32, C.POINTER(vp), pu32, u64, pu64)
+    sig("mlp_solution_fix_info", i32, vp, C.POINTER(MlpFixInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -700,6 +713,60 @@ class Solution:
         r = MlpBranchInfo()
         _raise(lib().mlp_solution_branch_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in MlpBranchInfo._fields_}
+
+    # ---- reduced-cost bounds from a cutoff, batched fixing (include/minilp_hip.h: mlp_solution_cutoff_bounds ...; semantics there)
+    def cutoff_bounds(self, cutoff, integer_vars=None):
+        """Bounds that the reduced costs and the objective value `cutoff` of an incumbent imply.  Returns (vars, lo, hi, pruned): the
+        structural variables whose bound tightens, ascending, each with both of its bounds; lo == hi: the variable can be fixed.
+        pruned: this LP is already worse than the cutoff (the arrays are empty).  integer_vars: a bool mask or a list of indices; the
+        bound of a marked variable is rounded to whole steps.  A read on a solved model: the solution is left as it is."""
+        n = self.num_vars
+        vm = None if integer_vars is None else self._int_mask(integer_vars, n)
+        v, lo, hi = np.zeros(n, dtype=np.uint32), np.zeros(n), np.zeros(n)
+        count, pruned = C.c_uint64(), C.c_int()
+        _raise(lib().mlp_solution_cutoff_bounds(self._h, float(cutoff), None if vm is None else _p(vm, C.c_uint8),
+                                                n if vm is None else len(vm), _p(v, C.c_uint32), _p(lo, C.c_double), _p(hi, C.c_double), n,
+                                                C.byref(count), C.byref(pruned)))
+        k = int(count.value)
+        return v[:k].copy(), lo[:k].copy(), hi[:k].copy(), bool(pruned.value)
+
+    @staticmethod
+    def _var_list(vars, who):
+        v = np.ascontiguousarray(list(vars), dtype=np.int64).reshape(-1)
+        if len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+            raise InternalError(-1, who + ": variable out of range")
+        return v.astype(np.uint32)
+
+    def fix_vars(self, vars, vals):
+        """fix_var(vars[i], vals[i]) for every i in one call: the non-basic requests share one FTRAN (none when every variable already
+        sits at its value), the basic ones take one forced pivot each, feasibility is restored once."""
+        v = self._var_list(vars, "fix_vars")
+        x = np.ascontiguousarray(list(vals), dtype=np.float64).reshape(-1)
+        if len(x) != len(v):
+            raise InternalError(-1, "fix_vars: vars and vals differ in length")
+        h = self._take()
+        _raise(lib().mlp_solution_fix_vars(C.byref(h), _p(v, C.c_uint32), _p(x, C.c_double), len(v)))
+        return Solution(h)
+
+    def unfix_vars(self, vars):
+        """unfix_var for every listed variable with one re-solve.  Returns (Solution, released count)."""
+        v = self._var_list(vars, "unfix_vars")
+        h = self._take()
+        k = C.c_uint64()
+        _raise(lib().mlp_solution_unfix_vars(C.byref(h), _p(v, C.c_uint32), len(v), C.byref(k)))
+        return Solution(h), int(k.value)
+
+    def fix_by_reduced_cost(self, cutoff, integer_vars=None):
+        """cutoff_bounds, then fix_vars on the entries with lo == hi.  Returns (Solution, fixed variables); a pruned LP fixes nothing."""
+        v, lo, hi, _ = self.cutoff_bounds(cutoff, integer_vars)
+        sel = lo == hi
+        return self.fix_vars(v[sel], lo[sel]), v[sel]
+
+    def fix_info(self):
+        """Counters of the last cutoff_bounds / fix_vars / unfix_vars call (mlp_fix_info) as a dict."""
+        r = MlpFixInfo()
+        _raise(lib().mlp_solution_fix_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpFixInfo._fields_}
 
     def cut_info(self):
         """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""

@@ -24,6 +24,7 @@ struct mlp_solution {
     Engine::TableauInfo tableau;  // of the last tableau call
     Engine::GmiInfo gmi;          // of the last mlp_solution_add_gmi_cuts call
     Engine::BranchInfo branch;    // of the last mlp_solution_branch_penalties call
+    Engine::FixInfo fix;          // of the last mlp_solution_cutoff_bounds / mlp_solution_fix_vars / mlp_solution_unfix_vars call
     std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
     std::vector<uint32_t> tab_indices;
     std::vector<double> tab_values;
@@ -645,6 +646,96 @@ int mlp_solution_branch_info(const mlp_solution* s, mlp_branch_info* out) {
     });
 }
 uint64_t mlp_branch_info_size(void) { return (uint64_t)sizeof(mlp_branch_info); }
+
+// ---- reduced-cost bounds from a cutoff, batched fixing (fixing.inc)
+int mlp_solution_cutoff_bounds(const mlp_solution* cs, double cutoff, const uint8_t* var_is_int, uint32_t num_vars, uint32_t* vars,
+                               double* new_lo, double* new_hi, uint64_t cap, uint64_t* count, int* pruned) {
+    return guarded([&] {
+        mlp_solution* s = const_cast<mlp_solution*>(cs);
+        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+        if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "cutoff_bounds is not available on a sharded solution");
+        Engine* e = s->eng;
+        if (!count || !pruned) throw MlpError(MLP_EINVAL, "cutoff_bounds: NULL count / pruned");
+        *count = 0;
+        *pruned = 0;
+        if (std::isnan(cutoff)) throw MlpError(MLP_EINVAL, "cutoff_bounds: the cutoff is NaN");
+        if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "cutoff_bounds: num_vars must be mlp_solution_num_vars");
+        if (!e->solved()) throw MlpError(MLP_EINVAL, "cutoff_bounds: model not solved");
+        const double obj = e->cur_obj_val();                         // internal: min c^.x
+        const double user = e->direction == 1 ? -obj : obj;          // what mlp_solution_objective returns
+        const double g = e->direction == 1 ? user - cutoff : cutoff - user;  // exact: no tolerance
+        if (std::isnan(g)) throw MlpError(MLP_EINVAL, "cutoff_bounds: the gap is NaN");
+        Engine::FixInfo info;
+        if (g < 0.0) {  // the node is worse than the cutoff
+            *pruned = 1;
+            s->fix = info;
+            return;
+        }
+        std::vector<uint32_t> v;
+        std::vector<double> lo, hi;
+        e->cutoff_bounds(g, var_is_int, v, lo, hi, info);
+        *count = (uint64_t)v.size();
+        if (cap < *count) throw MlpError(MLP_EINVAL, "cutoff_bounds: cap is below the count (num_vars always suffices)");
+        if (*count && (!vars || !new_lo || !new_hi)) throw MlpError(MLP_EINVAL, "cutoff_bounds: NULL output");
+        if (*count) {
+            std::memcpy(vars, v.data(), sizeof(uint32_t) * v.size());
+            std::memcpy(new_lo, lo.data(), sizeof(double) * v.size());
+            std::memcpy(new_hi, hi.data(), sizeof(double) * v.size());
+        }
+        s->fix = info;
+    });
+}
+int mlp_solution_fix_vars(mlp_solution** s, const uint32_t* vars, const double* vals, uint64_t n) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        Engine* e = (*s)->eng;
+        if (n && (!vars || !vals)) throw MlpError(MLP_EINVAL, "fix_vars: NULL list");
+        std::vector<int> v;
+        std::vector<double> x;
+        for (uint64_t i = 0; i < n; ++i) {  // (each index is checked as it is read, nothing is sized by n)
+            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "fix_vars: variable out of range");
+            v.push_back((int)vars[i]);
+            x.push_back(vals[i]);
+        }
+        (*s)->fix = Engine::FixInfo();
+        if (n == 0) return;
+        e->pivot_budget = -1;
+        stale(*s);
+        e->fix_vars(v, x, (*s)->fix);
+    }));
+}
+int mlp_solution_unfix_vars(mlp_solution** s, const uint32_t* vars, uint64_t n, uint64_t* unfixed) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        Engine* e = (*s)->eng;
+        if (unfixed) *unfixed = 0;
+        if (n && !vars) throw MlpError(MLP_EINVAL, "unfix_vars: NULL list");
+        std::vector<int> v;
+        for (uint64_t i = 0; i < n; ++i) {
+            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "unfix_vars: variable out of range");
+            v.push_back((int)vars[i]);
+        }
+        (*s)->fix = Engine::FixInfo();
+        if (n == 0) return;
+        e->pivot_budget = -1;
+        stale(*s);
+        const uint64_t k = e->unfix_vars(v, (*s)->fix);
+        if (unfixed) *unfixed = k;
+    }));
+}
+int mlp_solution_fix_info(const mlp_solution* s, mlp_fix_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / fix info");
+        std::memset(out, 0, sizeof(*out));
+        const Engine::FixInfo& f = s->fix;
+        out->requests = f.requests; out->nonbasic = f.nonbasic; out->shifted = f.shifted; out->forced_pivots = f.forced_pivots;
+        out->solves = f.solves; out->unfixed = f.unfixed; out->listed = f.listed; out->listed_fixed = f.listed_fixed; out->pivots = f.pivots;
+        out->bytes = f.bytes; out->device_ms = f.device_ms; out->wall_ms = f.wall_ms;
+    });
+}
+uint64_t mlp_fix_info_size(void) { return (uint64_t)sizeof(mlp_fix_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

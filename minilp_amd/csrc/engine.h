@@ -216,6 +216,21 @@ public:
     };
     void branch_penalties(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, const Duals& du, double* down,
                           double* up, int64_t* down_col, int64_t* up_col, double* frac, int32_t* status, BranchInfo& info);
+    // Reduced-cost bounds from a cutoff and the batched fixing of variables (fixing.inc; include/minilp_hip.h mlp_solution_cutoff_bounds,
+    // mlp_solution_fix_vars, mlp_solution_unfix_vars).  FixInfo describes the last of the three calls.
+    struct FixInfo {
+        uint64_t requests = 0, nonbasic = 0, shifted = 0, forced_pivots = 0, solves = 0, unfixed = 0, listed = 0, listed_fixed = 0, pivots = 0;
+        double bytes = 0, device_ms = 0, wall_ms = 0;
+    };
+    bool solved() const { return primal_feasible && dual_feasible && !budget_exhausted; }
+    // g = cutoff - objective in the internal minimisation sense (>= 0, finite); var_is_int: num_vars marks or nullptr.  The list comes
+    // back in ascending variable number.  Reads the state only, like ranging.
+    void cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint32_t>& vars, std::vector<double>& lo, std::vector<double>& hi,
+                       FixInfo& info);
+    // the model that fix_var(vars[i], vals[i]) for i = 0, 1, ... would leave: the requests non-basic at the basis the call finds are
+    // served together (one FTRAN, none when nothing moves), the basic ones by one forced dual pivot each, feasibility restored once
+    void fix_vars(const std::vector<int>& vars, const std::vector<double>& vals, FixInfo& info);
+    uint64_t unfix_vars(const std::vector<int>& vars, FixInfo& info);  // unfix_var's rule per request, ONE optimize(); returns the released count
     // Reading the tableau of the current basis (tableau.inc; include/minilp_hip.h mlp_solution_binv_rows ...).  Columns:
     // j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by CONSTRAINT (0 / ignored for one
     // without a row), vectors by position have length num_rows().  Internal form A x + s = b: no sign turn for Maximize.  Requests are
@@ -568,6 +583,7 @@ private:
     void optimize();              // solver.rs:487-511
     void restore_feasibility();   // solver.rs:513-547
     void recalc_obj_coeffs();     // solver.rs:1199-1231
+    int fix_var_apply(int var, double val);  // fix_var without its re-solve: forced dual pivot (basic) or shift (non-basic), then the fixed flags; returns the column
     void calc_col_coeffs(int col);                          // solver.rs:671-677
     void calc_row_coeffs(int row, bool with_sweep);         // solver.rs:680-693
     void fetch_values();

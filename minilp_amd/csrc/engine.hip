@@ -2677,6 +2677,13 @@ void Engine::fix_var(int var, double val) {  // solver.rs:378-415
     double t0 = now_s();
     ensure_beta();
     if (val < h_lo[var] || val > h_hi[var]) throw LpFail{1};
+    fix_var_apply(var, val);
+    primal_feasible = false;
+    budget_exhausted = false;
+    restore_feasibility();
+    stats.solve_wall_s += now_s() - t0;
+}
+int Engine::fix_var_apply(int var, double val) {
     int col;
     if (h_var_loc[var] >= 0) {
         // basic: one forced dual pivot towards `val` (solver.rs:384-391)
@@ -2712,10 +2719,7 @@ void Engine::fix_var(int var, double val) {  // solver.rs:378-415
     HIPCHECK(hipMemcpyAsync(d_nbflags.p + col, &f, 1, hipMemcpyHostToDevice, st));
     HIPCHECK(hipStreamSynchronize(st));
     h_nb_fixed[col] = 1;
-    primal_feasible = false;
-    budget_exhausted = false;
-    restore_feasibility();
-    stats.solve_wall_s += now_s() - t0;
+    return col;
 }
 
 bool Engine::unfix_var(int var) {  // solver.rs:418-438
@@ -4247,5 +4251,204 @@ void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_
     info.nnz = indices.size();
     info.bytes = rb.bytes;
     info.device_ms = rb.device_ms;
+}
+
+// ------------------------------------------------------------------ fixing (fixing.inc)
+// The read: nothing is written but private buffers; the reduced costs are the engine's own d on the device, the host reads back the
+// length of the list and then the list.
+void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint32_t>& vars, std::vector<double>& lo, std::vector<double>& hi,
+                           FixInfo& info) {
+    if (sharded()) throw MlpError(-1, "cutoff_bounds is not available on a sharded solution");
+    if (!solved()) throw MlpError(-1, "cutoff_bounds: model not solved (the bound is a weak-duality argument: it needs a dual-feasible basis)");
+    info = FixInfo();
+    vars.clear(); lo.clear(); hi.clear();
+    const int nv = num_vars;
+    if (nv <= 0 || !(g < std::numeric_limits<double>::infinity())) return;  // g = +inf: nothing is tightened
+    sync_view();
+    const long ntiles = cutoff_tiles(nv);
+    const size_t room = (size_t)ntiles * 256;
+    const long nsum = (ntiles + 4095) / 4096;
+    DevBuf<int> tcnt, toff, sums;
+    DevBuf<uint32_t> svar, ovar;
+    DevBuf<double> slo, shi, olo, ohi;
+    DevBuf<uint8_t> dmask;
+    tcnt.ensure((size_t)ntiles, 0, st); toff.ensure((size_t)ntiles, 0, st); sums.ensure((size_t)nsum + 2, 0, st);
+    svar.ensure(room, 0, st); slo.ensure(room, 0, st); shi.ensure(room, 0, st);
+    ovar.ensure(room, 0, st); olo.ensure(room, 0, st); ohi.ensure(room, 0, st);
+    if (var_is_int) dmask.upload(std::vector<uint8_t>(var_is_int, var_is_int + nv), st);
+    CutoffBufs b{};
+    b.mask = var_is_int ? dmask.p : nullptr;
+    b.tcnt = tcnt.p; b.toff = toff.p; b.svar = svar.p; b.slo = slo.p; b.shi = shi.p; b.ovar = ovar.p; b.olo = olo.p; b.ohi = ohi.p;
+    b.nv = nv; b.g = g;
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
+    launch_cutoff_bounds(hview, b, sums.p, st);
+    HIPCHECK(hipEventRecord(ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    int total = 0;
+    HIPCHECK(hipMemcpyAsync(&total, sums.p + nsum, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (total < 0 || total > nv) throw MlpError(-3, "cutoff_bounds: the compaction returned an impossible count");
+    vars.resize((size_t)total); lo.resize((size_t)total); hi.resize((size_t)total);
+    if (total) {
+        HIPCHECK(hipMemcpyAsync(vars.data(), ovar.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(lo.data(), olo.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(hi.data(), ohi.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+    }
+    info.listed = (uint64_t)total;
+    for (int i = 0; i < total; ++i) info.listed_fixed += lo[i] == hi[i] ? 1 : 0;
+    // algorithmic bytes: per variable its location (4), and for a non-basic one its flags, reduced cost and bounds (25; the value of a
+    // marked column and its mark: 9); per tile two counters written, read twice; per entry 20 bytes written, read, written and read back
+    info.bytes = (var_is_int ? 38.0 : 29.0) * nv + 16.0 * (double)ntiles + 80.0 * total;
+    info.device_ms = ev.ms();
+}
+
+// The batched forms.  Checks first, nothing is changed before they pass.
+void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& vals, FixInfo& info) {
+    if (sharded()) throw MlpError(-1, "fix_vars is not available on a sharded solution");
+    info = FixInfo();
+    info.requests = vars.size();
+    if (vars.empty()) return;
+    {
+        std::vector<int> sorted(vars);
+        std::sort(sorted.begin(), sorted.end());
+        if (sorted.front() < 0 || sorted.back() >= num_vars) throw MlpError(-1, "fix_vars: variable out of range");
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "fix_vars: a variable is listed twice");
+    }
+    for (size_t i = 0; i < vars.size(); ++i)
+        if (!(vals[i] >= h_lo[vars[i]] && vals[i] <= h_hi[vars[i]])) throw LpFail{1};
+    cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
+    const double t0 = now_s();
+    const uint64_t it0 = stats.iterations;
+    ensure_beta();
+    // step 1: the requests non-basic at the basis the call finds, in ascending variable number
+    std::vector<std::pair<int, double>> nb;
+    std::vector<size_t> basic;
+    for (size_t i = 0; i < vars.size(); ++i) {
+        if (h_var_loc[vars[i]] < 0) nb.emplace_back(vars[i], vals[i]);
+        else basic.push_back(i);
+    }
+    std::sort(nb.begin(), nb.end());
+    info.nonbasic = nb.size();
+    bool moved = !basic.empty();
+    if (!nb.empty()) {
+        constexpr int R = RG_BATCH;
+        const size_t n = nb.size();
+        std::vector<int> hcol(n), hvar(n);
+        std::vector<double> hval(n);
+        for (size_t i = 0; i < n; ++i) {
+            hvar[i] = nb[i].first;
+            hcol[i] = -1 - h_var_loc[nb[i].first];
+            hval[i] = nb[i].second;
+        }
+        pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+        sync_view();
+        DevBuf<int> dcol, dvar, dcnt;
+        DevBuf<double> dval, ddiff;
+        dcol.upload(hcol, st); dvar.upload(hvar, st); dval.upload(hval, st);
+        ddiff.ensure(n, 0, st); dcnt.ensure(1, 0, st);
+        FixBufs b{};
+        b.col = dcol.p; b.var = dvar.p; b.val = dval.p; b.diff = ddiff.p; b.nshift = dcnt.p; b.n = (long)n;
+        EventPair ev;
+        HIPCHECK(hipEventRecord(ev.e[0], st));
+        launch_fix_diff(hview, b, st);
+        int shifted = 0;
+        HIPCHECK(hipMemcpyAsync(&shifted, dcnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        info.shifted = (uint64_t)shifted;
+        info.bytes = 36.0 * (double)n;
+        DevBuf<double> delta, X, Y, XK, YK, lrh;
+        if (shifted && m_ > 0) {  // r = A delta, ONE FTRAN through the dense right-hand-side path, x_B -= B^-1 r
+            const DevView& dv = hview;
+            const Geom g = geom();
+            const int m = m_, k = fac_on_ ? 0 : k_;
+            ReqContext ctx(*this, std::vector<int>(1, 0), false);
+            const size_t blk = (size_t)m * R + R;
+            delta.ensure((size_t)N_ + 1, 0, st); X.ensure(blk, 0, st); Y.ensure(blk, 0, st);
+            if (!fac_on_ && k > 0) {
+                XK.ensure((size_t)k * R + R, 0, st); YK.ensure((size_t)k * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
+            }
+            TabBufs tb{};
+            static_cast<SolveBufs&>(tb) = ctx.sb;
+            tb.X = X.p; tb.Y = Y.p; tb.XK = XK.p; tb.YK = YK.p; tb.lrh = lrh.p;
+            b.delta = delta.p; b.X = X.p; b.Y = Y.p;
+            launch_fix_rhs(dv, b, N_, st);
+            launch_tab_solve(dv, g, tb, 0, 1, st);
+            launch_fix_apply(dv, b, st);
+            info.solves = 1;
+            // the blocks X and Y, delta and the CSR pass, then the solve as tab_dense counts it
+            info.bytes += 32.0 * (double)m * R + 8.0 * (double)N_ + 20.0 * (double)h_rcol.size() + 16.0 * m +
+                          (fac_on_ ? (24.0 + 16.0 * ctx.J) * m : 8.0 * (double)k * k + 16.0 * ctx.J * k + 32.0 * (double)k * R + 20.0 * (double)h_rcol.size());
+            moved = true;
+        }
+        launch_fix_commit(hview, b, shifted ? 1 : 0, st);
+        HIPCHECK(hipEventRecord(ev.e[1], st));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(st));
+        info.device_ms = ev.ms();
+        for (size_t i = 0; i < n; ++i) h_nb_fixed[hcol[i]] = 1;
+        if (shifted) values_dirty = true;
+    }
+    // step 2: the basic requests in list order, one forced dual pivot each (the columns fixed above cannot enter)
+    for (size_t i : basic) {
+        fix_var_apply(vars[i], vals[i]);
+        info.forced_pivots += 1;
+    }
+    // step 3: ONE re-solve (none when nothing moved at a primal-feasible point: only flags were written)
+    if (moved || !primal_feasible) {
+        primal_feasible = false;
+        budget_exhausted = false;
+        restore_feasibility();
+    }
+    info.pivots = stats.iterations - it0;
+    stats.solve_wall_s += now_s() - t0;
+    info.wall_ms = (now_s() - t0) * 1e3;
+}
+
+uint64_t Engine::unfix_vars(const std::vector<int>& vars, FixInfo& info) {
+    if (sharded()) throw MlpError(-1, "unfix_vars is not available on a sharded solution");
+    info = FixInfo();
+    info.requests = vars.size();
+    for (int j : vars)
+        if (j < 0 || j >= num_vars) throw MlpError(-1, "unfix_vars: variable out of range");
+    std::vector<int> hcol, hvar;  // unfix_var's rule: a basic or not-fixed variable is skipped
+    for (int j : vars) {
+        if (h_var_loc[j] >= 0) continue;
+        const int col = -1 - h_var_loc[j];
+        if (!h_nb_fixed[col]) continue;
+        h_nb_fixed[col] = 0;
+        hcol.push_back(col);
+        hvar.push_back(j);
+    }
+    if (hcol.empty()) return 0;
+    cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
+    const double t0 = now_s();
+    const uint64_t it0 = stats.iterations;
+    sync_view();
+    DevBuf<int> dcol, dvar;
+    dcol.upload(hcol, st); dvar.upload(hvar, st);
+    FixBufs b{};
+    b.col = dcol.p; b.var = dvar.p; b.n = (long)hcol.size();
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
+    launch_fix_release(hview, b, st);
+    HIPCHECK(hipEventRecord(ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    info.device_ms = ev.ms();
+    info.bytes = 33.0 * (double)hcol.size();
+    info.unfixed = hcol.size();
+    dual_feasible = false;
+    budget_exhausted = false;
+    try {
+        optimize();
+    } catch (LpFail&) {
+        throw MlpError(-1, "unfix_vars: optimize failed (solver.rs:433 unwrap)");
+    }
+    info.pivots = stats.iterations - it0;
+    stats.solve_wall_s += now_s() - t0;
+    info.wall_ms = (now_s() - t0) * 1e3;
+    return info.unfixed;
 }
 }  // namespace mlp

@@ -607,6 +607,40 @@ void launch_branch_heads(const DevView& dv, const int* req, double* f, int nbat,
 // ranging_blocks(g, 0, N) workgroups = rows of pval / pcol
 void launch_branch_batch(const DevView& dv, const Geom& g, const RangingBufs& b, const BranchBufs& bb, int nreq, const int* h_req,
                          hipStream_t st);
+// reduced-cost bounds from a cutoff (fixing.inc): one classifying pass over the structural variables with a deterministic compaction
+struct CutoffBufs {
+    const uint8_t* mask;  // nv: 1 = integer variable; nullptr: no bound is floored
+    int* tcnt;            // cutoff_tiles(nv): listed variables of each tile
+    int* toff;            // cutoff_tiles(nv): their exclusive scan
+    uint32_t* svar;       // cutoff_tiles(nv) x 256 staging: each tile's entries at the head of its own stretch
+    double* slo;
+    double* shi;
+    uint32_t* ovar;       // the list, ascending by variable (room for nv entries)
+    double* olo;
+    double* ohi;
+    int nv;               // structural variables
+    double g;             // cutoff - objective in the internal minimisation sense, >= 0 and finite
+};
+long cutoff_tiles(int nv);
+// sums: the scan's scratch, cutoff_tiles(nv) / 4096 + 2 ints; sums[ceil(cutoff_tiles(nv) / 4096)] = length of the list
+void launch_cutoff_bounds(const DevView& dv, const CutoffBufs& b, int* sums, hipStream_t st);
+// the non-basic requests of fix_vars, served together, and the released columns of unfix_vars (fixing.inc)
+struct FixBufs {
+    const int* col;     // n: non-basic position of a request (the requests in ascending variable number)
+    const int* var;     // n: its variable
+    const double* val;  // n: the value asked for
+    double* diff;       // n: val - xN
+    int* nshift;        // 1: requests with diff != 0
+    double* delta;      // N: diff by variable, 0 elsewhere
+    double* X;          // [m][RG_BATCH]: column 0 = A delta by row (the block of TabBufs)
+    const double* Y;    // [m][RG_BATCH]: column 0 = B^-1 A delta by position
+    long n;
+};
+void launch_fix_diff(const DevView& dv, const FixBufs& b, hipStream_t st);            // diff, nshift
+void launch_fix_rhs(const DevView& dv, const FixBufs& b, int N, hipStream_t st);      // delta, X (before launch_tab_solve)
+void launch_fix_apply(const DevView& dv, const FixBufs& b, hipStream_t st);           // x_B -= Y (after it)
+void launch_fix_commit(const DevView& dv, const FixBufs& b, int shifted, hipStream_t st);  // objective (if shifted), xN, flags
+void launch_fix_release(const DevView& dv, const FixBufs& b, hipStream_t st);         // flags from the value against the bounds
 // Sparse rows out of a dense block, one batch of at most RG_BATCH basic positions (tableau.inc, cuts.inc, gmi.inc).  Phase 1,
 // launch_rows_generate: the rows of B^-1 (b.blk, b.req, the SolveBufs part as for ranging), one pass over A that leaves the dense block
 // dense[N][RG_BATCH] by variable, the scanned offsets off[RG_BATCH * cut_segments(N)] (cnt: same size, sums: the scan's scratch), the row
