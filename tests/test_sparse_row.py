@@ -14,7 +14,7 @@ from tests.common import GEN, X_ATOL, check_feasible, obj_close
 pytestmark = pytest.mark.gpu
 
 CASES = [("sparse", (700, 600, 12, 6)), ("sparse", (2500, 2000, 10, 4)), ("cover", (700, 900, 12, 5)), ("twophase", (600, 600, 12, 44)),
-         ("dense", (150, 100, 3))]
+         ("dense", (150, 100, 3)), ("bounded", (700, 600, 12, 6))]     # bounded: 9 bound flips, columns at upper bounds (tests/bounded_lp.py)
 
 
 @pytest.mark.parametrize("fam,args", CASES, ids=str)
