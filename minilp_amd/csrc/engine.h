@@ -457,7 +457,6 @@ private:
     DevBuf<double> d_work;  // alpha_q | tau | rv (2m) | hS  — one memset per batch
     DevBuf<double> d_alpha_r, d_helper;
     DevBuf<int2> d_nb_rng;
-    int sweep_variant = 0;
     int sw_balanced = 1;  // MLP_STREAM_BALANCED=0: fixed 128-row strips in the streaming pass (A/B runs); N > 1: that many blocks
     int rt_device = 0;
     void acquire_runtime();  // streams, events, pinned Ctl mirror: recycled across Solutions

@@ -317,7 +317,6 @@ Geom Engine::geom() const {
     double avg = num_vars > 0 ? (double)(h_rcol.size() - (size_t)m_) / (double)num_vars : 1.0;  // structural columns
     g.lanes = avg >= 40.0 ? 64 : (avg >= 6.0 ? 16 : 4);
     g.sweep_one = avg < 3.0 ? 1 : 0;  // (the 400 000-column transport solve 15.63 s against 15.82-15.95 with four lanes per two-entry column)
-    g.sweep_variant = sweep_variant;
     g.big = (cap_ > 4096 || force_big_tiles) ? 1 : 0;
     const int lr = lr_force >= 0 ? lr_force : (cap_ >= 8192 ? 32 : 0);  // as in sync_view
     g.head_fused = (!fac_on_ && lr == 0 && max_col_nnz_ <= HEAD_LIST_CAP && max_row_nnz_ <= HEAD_LIST_CAP) ? 1 : 0;
@@ -572,7 +571,7 @@ DevView* Engine::sync_view() {
     v.mail_fanout = live ? mail_fanout : 0;
     {   // exchange buffers of the row-sharded streaming pass (peer transport, large-nucleus delayed-update mode only)
         const size_t mb = kMailBoxBytesPerRank * (size_t)std::max(shard_world, 1);
-        v.wshard = (live && mail_fanout > 1 && own_box && v.lrJ > 0 && geom().big && stream_strips_enabled() &&
+        v.wshard = (live && mail_fanout > 1 && own_box && v.lrJ > 0 && geom().big &&
                     !no_wshard && (size_t)cap_ <= xb_cap_) ? 1 : 0;
         v.xbuf = own_box ? reinterpret_cast<double*>(static_cast<uint8_t*>(own_box) + mb) : nullptr;
         for (int r = 0; r < MAX_WORLD; ++r)
@@ -580,7 +579,7 @@ DevView* Engine::sync_view() {
         v.xb_cap = (int)xb_cap_; v.pad3 = 0;
     }
     v.sw_nbal = 0; v.sw_pad = 0;
-    if (sw_balanced && v.lrJ > 0 && geom().big && stream_strips_enabled())
+    if (sw_balanced && v.lrJ > 0 && geom().big)
         v.sw_nbal = sw_balanced > 1 ? sw_balanced : stream_coresident_blocks();
     v.nb_lo = live ? (int)((long)num_vars * shard_rank / shard_world) : 0;
     v.nb_hi = live ? (int)((long)num_vars * (shard_rank + 1) / shard_world) : num_vars;

@@ -429,7 +429,6 @@ struct Geom {
     int m, n, cap;
     int lanes;  // lanes per CSC column in the pull kernels (4, 16 or 64; from the average column length)
     int sweep_one;  // average column below 3 entries: the CSC-pull tableau row takes ONE lane per column (a quarter of the workgroups; sums in storage order)
-    int sweep_variant;  // 0 (the lane / gather-chain variants of round 1 are gone as a choice)
     int big;            // fused W pass: 64-row x 1024-column blocks, non-temporal (cap > 4096, or forced by MLP_BIGTILE)
     int head_fused;     // stage heads run inside the consuming kernel (delayed-update mode off, every column / row fits the LDS list)
     int str;            // sparse tableau row instead of the sweep over all of A (nucleus of at most MLP_STR_K columns, one GPU)
@@ -440,6 +439,8 @@ struct Geom {
     int ratio_list;     // the grid form of the primal Harris test may run as ONE grid pass (list form): off when the spin limit of the in-kernel wait is <= 0
     int fp;             // large nucleus, lazy primal iteration: the F product of the FTRAN is PULLED inside the ratio test's launch (fpull.inc)
 };
+// Large tiles in the delayed-update mode: the pass over the nucleus inverse is k_stream_w's strip tiling (its partials lie by strip)
+static inline bool strip_tiled(const DevView& dv, const Geom& g) { return dv.lrJ && g.big; }
 
 // ---- launch wrappers (all asynchronous on `st`; the DevView is passed to the kernels by value) ----
 void launch_clear_work(const DevView& dv, hipStream_t st);  // alpha_q, tau, rv := 0 (one memset)
@@ -494,7 +495,6 @@ void launch_mail_deliver(const DevView& dv, const void* stage, hipStream_t st);
 // sampled iterations: stamp (t0, t1) at the start / end of the next kernel of a slot (1 tableau-row sweep, 2 pass over the
 // nucleus inverse, 3 fold) instead of bracketing its launch; (nullptr, nullptr) disarms
 void arm_kernel_timing(int slot, hipEvent_t t0, hipEvent_t t1);
-bool stream_strips_enabled();
 bool fold_fuses_v(const DevView& dv, int with_v, int with_tau, int fold_only);  // a folding pivot's fold also produces the v partials (its streaming pass is skipped)
 int stream_coresident_blocks();  // blocks of the default k_stream_w instance the device holds at once (0: unknown)
 void launch_structure_update(const DevView& dv, const Geom& g, hipStream_t st);

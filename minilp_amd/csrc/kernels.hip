@@ -2828,13 +2828,7 @@ __global__ void __launch_bounds__(BLK) k_sweep(DevView v, int n_sweep, int build
 // up in band order (fixed summation order, no atomics).
 typedef unsigned int uint4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef double dbl2u __attribute__((ext_vector_type(2), aligned(8)));
-// VORD: the columns are visited in VARIABLE order (the storage order of the band-major copy) instead of non-basic
-// POSITION order.  After many pivots nb_vars is a random permutation, so position order turns the read of the copy into
-// 80-byte gathers out of 128-byte lines: the PMC counters show 521 MB of HBM traffic per launch at pivot 240 000 against
-// 150 MB at pivot 200, for the same 116 MB copy.  In variable order the copy is read front to back; basic variables are
-// skipped (var_loc >= 0) and the partials are scattered to band_part[b][position] (16-byte stores).  Unsharded solves
-// only: a rank of a sharded solve owns a range of POSITIONS, which in variable order would be a scattered subset.
-template <int MODE, bool VORD>
+template <int MODE>
 __global__ void __launch_bounds__(BAND_THREADS) k_sweep_band(DevView v, int chunks) {
     Ctl* c = v.ctl;
     if (c->halt || c->it.status != ITER_PIVOT) return;
@@ -2855,8 +2849,8 @@ __global__ void __launch_bounds__(BAND_THREADS) k_sweep_band(DevView v, int chun
     // deterministic blocked push leaves behind in LDS read as NaNs; three entries of a tableau row came out non-finite.)
     for (int t = nrows + tid; t < BAND_ROWS; t += BAND_THREADS) s_rv[t] = make_double2(0.0, 0.0);
     __syncthreads();
-    const int base = VORD ? 0 : v.nb_lo;
-    const int span = VORD ? v.m + v.n : v.nb_hi - v.nb_lo;  // variables, or this rank's non-basic positions
+    const int base = v.nb_lo;
+    const int span = v.nb_hi - v.nb_lo;  // this rank's non-basic positions
     const int per = (span + chunks - 1) / chunks;
     const int c_lo = base + chunk * per;
     const int c_hi = min(base + span, c_lo + per);
@@ -2866,7 +2860,7 @@ __global__ void __launch_bounds__(BAND_THREADS) k_sweep_band(DevView v, int chun
     for (int j0 = c_lo + tid; j0 < c_hi; j0 += CPT * BAND_THREADS) {
     int vars[CPT], poss[CPT], begs[CPT], ends[CPT];
     bool pkd[CPT];
-    const int* pkp = (!VORD && v.pk_ptr) ? v.pk_ptr + (size_t)b * (size_t)(v.n + 1) : nullptr;
+    const int* pkp = v.pk_ptr ? v.pk_ptr + (size_t)b * (size_t)(v.n + 1) : nullptr;
 #pragma unroll
     for (int u = 0; u < CPT; ++u) {
         const int i = j0 + u * BAND_THREADS;
@@ -2874,24 +2868,16 @@ __global__ void __launch_bounds__(BAND_THREADS) k_sweep_band(DevView v, int chun
         poss[u] = -1;
         pkd[u] = false;
         if (i < c_hi) {
-            if (!VORD && pkp && v.pk_valid[i]) {  // packed copy: the segment of index i, straight from its offsets
+            if (pkp && v.pk_valid[i]) {  // packed copy: the segment of index i, straight from its offsets
                 pkd[u] = true;
                 vars[u] = 0;
                 poss[u] = i;
                 continue;
             }
-            if (VORD) {
-                const int loc = v.var_loc[i];
-                if (loc < 0) {  // non-basic: position -1 - loc
-                    vars[u] = i;
-                    poss[u] = -1 - loc;
-                }
-            } else {
-                // locality order: index i of the pass serves position nb_order[i] (positions sorted by the variable
-                // they hold, refreshed by the host now and then), and the partials are indexed by i
-                vars[u] = v.nb_vars[v.nb_order ? v.nb_order[i] : i];
-                poss[u] = i;
-            }
+            // locality order: index i of the pass serves position nb_order[i] (positions sorted by the variable
+            // they hold, refreshed by the host now and then), and the partials are indexed by i
+            vars[u] = v.nb_vars[v.nb_order ? v.nb_order[i] : i];
+            poss[u] = i;
         }
     }
 #pragma unroll
@@ -5287,19 +5273,13 @@ static void launch_sweep_banded(const DevView& dv, const Geom& g, int mode, int 
     const size_t lds = sizeof(double2) * (size_t)BAND_ROWS;
     if (!attr_set) {  // more than the default 64 KB of LDS per workgroup
         // (a failure here makes the launches below fail, which Engine::pull_ctl reports through hipGetLastError)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<0, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_sweep_band<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    // column order of the pass
-    // Measured (round 2): variable order does NOT pay — late window 77.5 us against 73.4 us in position order, early window
-    // 112.4 against 103.9 us per pivot: the 16-byte partial stores scattered by position cost what the sequential read
-    // saves. Position order it is.
-    const bool vord = false;  // (variable order of the pass: measured slower — 112.4 against 103.9 us per pivot — and removed as a choice)
+    // (column order of the pass: position order.  Variable order was measured slower — 112.4 against 103.9 us per pivot: the 16-byte partial
+    // stores scattered by position cost what the sequential read saves — and is removed as a choice)
     // One workgroup per CU (LDS-bound): all blocks of the launch must fit the 256 CUs at once, or a second,
     // almost empty round of workgroups doubles the kernel time (260 workgroups: 43 us, 247: 36 us).  In the
     // primal iteration the per-band partials are summed by k_update_pivot itself (inline_combine) and the
@@ -5308,15 +5288,9 @@ static void launch_sweep_banded(const DevView& dv, const Geom& g, int mode, int 
     int chunks = (256 - struct_blocks) / dv.nbands;
     if (chunks < 1) chunks = 1;
     const dim3 gr(dv.nbands * chunks + struct_blocks), b(BAND_THREADS);
-    if (vord) {
-        if (mode == 0) LAUNCH_T(1, (k_sweep_band<0, true>), gr, b, lds, st, dv, chunks);
-        else if (mode == 1) LAUNCH_T(1, (k_sweep_band<1, true>), gr, b, lds, st, dv, chunks);
-        else LAUNCH_T(1, (k_sweep_band<2, true>), gr, b, lds, st, dv, chunks);
-    } else {
-        if (mode == 0) LAUNCH_T(1, (k_sweep_band<0, false>), gr, b, lds, st, dv, chunks);
-        else if (mode == 1) LAUNCH_T(1, (k_sweep_band<1, false>), gr, b, lds, st, dv, chunks);
-        else LAUNCH_T(1, (k_sweep_band<2, false>), gr, b, lds, st, dv, chunks);
-    }
+    if (mode == 0) LAUNCH_T(1, k_sweep_band<0>, gr, b, lds, st, dv, chunks);
+    else if (mode == 1) LAUNCH_T(1, k_sweep_band<1>, gr, b, lds, st, dv, chunks);
+    else LAUNCH_T(1, k_sweep_band<2>, gr, b, lds, st, dv, chunks);
     if (inline_combine) return;
     const int nc = blocks_for(dv.nb_hi - dv.nb_lo);
     const dim3 gc(nc + (with_struct ? blocks_for(g.cap) : 0));
@@ -5338,8 +5312,6 @@ bool launch_sweep(const DevView& dv, const Geom& g, int mode, int with_struct, h
         else LAUNCH_T(1, (k_sweep<G, U, 2>), gr, b, 0, st, dv, n_sweep, 0);                                   \
     } while (0)
     if (g.sweep_one) { SWEEP(1, 4); }
-    else if (g.sweep_variant == 1) { LANES_SWITCH(g.lanes, SWEEP(4, 4), SWEEP(16, 4), SWEEP(32, 4)); }
-    else if (g.sweep_variant == 2) { LANES_SWITCH(g.lanes, SWEEP(4, 8), SWEEP(8, 8), SWEEP(32, 8)); }
     else { LANES_SWITCH(g.lanes, SWEEP(4, 4), SWEEP(16, 4), SWEEP(16, 8)); }
 #undef SWEEP
     return mode == 0 && list && dv.ar_list != nullptr;  // (k_sweep MODE 0 listed the non-zeros of alpha_r)
@@ -5409,42 +5381,30 @@ void launch_ratio_dual(const DevView& dv, const Geom& g, hipStream_t st, int lis
 }
 // rows per tile of the fused pass: 8 while W is small (more blocks in flight, 14 vs 20 us at
 // k = 1 800), 16 from cap 8192 on (half the v partials; measured 5.0-5.2 TB/s at k = 6 500 either way)
-// row tiles per block of the large-nucleus tiling
-constexpr int FW_RL = 1;  // measured: 4 row tiles per block slow the stream down (251 vs 163 us at k = 10 000) and the v reduce is not the bottleneck
-static inline int fw_rows(const Geom& g) { return g.big ? 16 * FW_RL : 8; }
+// (one row tile per block: 4 of them slow the stream down, 251 vs 163 us at k = 10 000, and the v reduce is not the bottleneck)
+static inline int fw_rows(const Geom& g) { return g.big ? 16 : 8; }
 // 1-D grid of the tiled large-nucleus passes: enough blocks to fill the chip a few times over
 constexpr int FW_TILE_BLOCKS = 4096;
-// strip geometry of k_stream_w (columns x rows per block, rows per step)
-struct SwGeom { int ch, rb, rs; };
-static constexpr SwGeom kSwGeoms[] = {{512, 512, 8}, {1024, 256, 4}, {1024, 128, 4}, {512, 256, 8}, {1024, 64, 4}, {512, 128, 4}};
-static int stream_variant() {
-    return 2;  // 1 024 columns x 128 rows, 4 rows per step (the other shapes were A/B runs of round 2: tools/stream_bench.hip)
-}
-static int sw_ch() { return kSwGeoms[stream_variant()].ch; }
-static int sw_rb() { return kSwGeoms[stream_variant()].rb; }
-bool stream_strips_enabled();
-static bool stream_strips() { return stream_strips_enabled(); }
+// strip geometry of k_stream_w: 1 024 columns x 128 rows per block, 4 rows per step (the other shapes were A/B runs: tools/stream_bench.hip)
+constexpr int STRIP_CH = 1024, STRIP_RB = 128, STRIP_RS = 4;
 int stream_coresident_blocks() {
     static int n = -1;
     if (n < 0) {
         int dev = 0, per_cu = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k_stream_w<true, 1024, 128, 4>), BLK, 0) == hipSuccess &&
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k_stream_w<true, STRIP_CH, STRIP_RB, STRIP_RS>), BLK, 0) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
             n = (per_cu < 3 ? per_cu : 3) * cus;  // measured: 3 per CU beats 4 (733 vs 740 us per pivot at k = 20 500); a
         else                                      // count that is not a multiple of the CUs loads them unevenly (759 us)
             n = 0;
     }
-    return (stream_variant() == 2) ? n : 0;
-}
-bool stream_strips_enabled() {
-    return true;
+    return n;
 }
 // A folding pivot of the lazy primal iteration (v only, no tau), unsharded: the fold kernel produces the v partials of the
 // freshly folded inverse itself and the streaming pass of that pivot is skipped (one read of the inverse less in every
 // lrJ pivots: 0.49 ms of 1.92 ms at k = 20 500).
 bool fold_fuses_v(const DevView& dv, int with_v, int with_tau, int fold_only) {
-    return with_v && !with_tau && !fold_only && !dv.wshard && dv.lrJ > 0 && stream_strips_enabled();
+    return with_v && !with_tau && !fold_only && !dv.wshard && dv.lrJ > 0;
 }
 static void launch_fused_lr(const DevView& dv, const Geom& g, int with_v, int fold_only, hipStream_t st, int with_tau = 1) {
     const int rows = fw_rows(g);
@@ -5470,11 +5430,11 @@ static void launch_fused_lr(const DevView& dv, const Geom& g, int with_v, int fo
     if (dv.lrJ <= 16) LAUNCH_T(3, k_fold_w2<16>, dim3(nf), b, 0, st, dv, fold_only ? 1 : 2, fuse);
     else LAUNCH_T(3, k_fold_w2<LR_MAX>, dim3(nf), b, 0, st, dv, fold_only ? 1 : 2, fuse);
     if (!fold_only) {
-        long tiles = (long)((g.cap + sw_rb() - 1) / sw_rb()) * ((g.cap + sw_ch() - 1) / sw_ch());
+        long tiles = (long)((g.cap + STRIP_RB - 1) / STRIP_RB) * ((g.cap + STRIP_CH - 1) / STRIP_CH);
         if (dv.sw_nbal > tiles) tiles = dv.sw_nbal;  // balanced strips: one tile per co-resident block
         const int nt = (int)(tiles < SW_MAX_BLOCKS ? tiles : SW_MAX_BLOCKS);
-        if (with_v) LAUNCH_T(2, (k_stream_w<true, 1024, 128, 4>), dim3(nt + LR_MAX), b, 0, st, dv, with_tau, fuse);
-        else if (with_tau) LAUNCH_T(2, (k_stream_w<false, 1024, 128, 4>), dim3(nt + LR_MAX), b, 0, st, dv, 1, 0);
+        if (with_v) LAUNCH_T(2, (k_stream_w<true, STRIP_CH, STRIP_RB, STRIP_RS>), dim3(nt + LR_MAX), b, 0, st, dv, with_tau, fuse);
+        else if (with_tau) LAUNCH_T(2, (k_stream_w<false, STRIP_CH, STRIP_RB, STRIP_RS>), dim3(nt + LR_MAX), b, 0, st, dv, 1, 0);
     }
 }
 void launch_fold_lowrank(const DevView& dv, const Geom& g, hipStream_t st) {
@@ -5499,16 +5459,16 @@ void launch_fused_w(const DevView& dv, const Geom& g, int with_v, hipStream_t st
     } else {
         const long tiles_cap = (long)nstripes * nchunks;
         const int nb = (int)(tiles_cap < FW_TILE_BLOCKS ? tiles_cap : FW_TILE_BLOCKS);
-        if (with_v && with_tau) LAUNCH_T(2, (k_fused_w<16, true, true, true, true, false, FW_RL, true>), dim3(nb), b, 0, st, dv);
-        else if (with_v) LAUNCH_T(2, (k_fused_w<16, false, true, true, true, false, FW_RL, true>), dim3(nb), b, 0, st, dv);
-        else if (with_tau) LAUNCH_T(2, (k_fused_w<16, true, false, true, true, false, FW_RL, true>), dim3(nb), b, 0, st, dv);
-        else LAUNCH_T(2, (k_fused_w<16, false, false, true, true, false, FW_RL, true>), dim3(nb), b, 0, st, dv);
+        if (with_v && with_tau) LAUNCH_T(2, (k_fused_w<16, true, true, true, true, false, 1, true>), dim3(nb), b, 0, st, dv);
+        else if (with_v) LAUNCH_T(2, (k_fused_w<16, false, true, true, true, false, 1, true>), dim3(nb), b, 0, st, dv);
+        else if (with_tau) LAUNCH_T(2, (k_fused_w<16, true, false, true, true, false, 1, true>), dim3(nb), b, 0, st, dv);
+        else LAUNCH_T(2, (k_fused_w<16, false, false, true, true, false, 1, true>), dim3(nb), b, 0, st, dv);
     }
 }
 bool rk_rides_post(const DevView& dv, const Geom& g) {
     const char* e = std::getenv("MLP_RK_RIDE");
     if (e && e[0] == '0') return false;
-    return dv.lrJ && fw_rows(g) != 8 && FW_RL == 1 && stream_strips() && !dv.wshard && dv.world <= 1;
+    return strip_tiled(dv, g) && !dv.wshard && dv.world <= 1;
 }
 int launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t st, int classic, int skip_push, int with_tau, int touch, int rk_ride) {
     // touch: also build the touched-column list of the sparse tableau row in this launch (extra blocks); returns 1 when it
@@ -5516,15 +5476,11 @@ int launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t 
     if (!with_tau) skip_push = 1;  // lazy dual steepest edge: no tau, hence no push of -F tau_K
     if (!with_tau && !with_v) return 0;
     const int touch_asked = touch;
-    if (!classic && dv.lrJ && fw_rows(g) != 8 && FW_RL == 1 && stream_strips()) {  // partials of k_stream_w's strips
-#define POSTX(RB, CH)                                                                                             \
-    if (sw_rb() == RB && sw_ch() == CH) hipLaunchKernelGGL((k_post_exchange<RB, CH>), dim3(blocks_for(g.cap)), dim3(BLK), 0, st, dv, with_v, with_tau);
-        if (dv.wshard) {  // row-sharded pass: exchange the partials first (k_post_fused then reads the exchange buffer)
-            POSTX(512, 512) POSTX(256, 1024) POSTX(128, 1024) POSTX(256, 512) POSTX(128, 512) POSTX(64, 1024)
-        }
-#undef POSTX
+    if (!classic && strip_tiled(dv, g)) {  // partials of k_stream_w's strips
+        // row-sharded pass: exchange the partials first (k_post_fused then reads the exchange buffer)
+        if (dv.wshard) hipLaunchKernelGGL((k_post_exchange<STRIP_RB, STRIP_CH>), dim3(blocks_for(g.cap)), dim3(BLK), 0, st, dv, with_v, with_tau);
 #define POSTS2(G, RB, CH)                                                                                         \
-    if (sw_rb() == RB && sw_ch() == CH) {                                                                         \
+    {                                                                                                             \
         if (with_v && rk_ride) {                                                                                  \
             const int n_tail = n_push + blocks_for(g.cap, 32);                                                    \
             int n_rk = blocks_for((long)g.cap * 4);                                                               \
@@ -5536,7 +5492,7 @@ int launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t 
 #define POSTS(G)                                                                                                  \
     do {                                                                                                          \
         int n_push = with_tau ? blocks_for((long)g.cap * G) : 0;                                                  \
-        POSTS2(G, 512, 512); POSTS2(G, 256, 1024); POSTS2(G, 128, 1024); POSTS2(G, 256, 512); POSTS2(G, 128, 512); POSTS2(G, 64, 1024);  \
+        POSTS2(G, STRIP_RB, STRIP_CH);  \
     } while (0)
         LANES_SWITCH(g.lanes, POSTS(4), POSTS(16), POSTS(64));
 #undef POSTS
@@ -5553,7 +5509,7 @@ int launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t 
             hipLaunchKernelGGL((k_post_fused<G, true, 8>), dim3(n_tail + blocks_for((long)(g.cap + 1) * 64)), dim3(BLK), 0, st, dv, n_push, n_tail); \
             touch = 0;                                                                                            \
         } else if (with_v && fw_rows(g) == 8) hipLaunchKernelGGL((k_post_fused<G, true, 8>), dim3(n_push + blocks_for(g.cap, 32)), dim3(BLK), 0, st, dv, n_push); \
-        else if (with_v) hipLaunchKernelGGL((k_post_fused<G, true, 16 * FW_RL>), dim3(n_push + blocks_for(g.cap, 32)), dim3(BLK), 0, st, dv, n_push); \
+        else if (with_v) hipLaunchKernelGGL((k_post_fused<G, true, 16>), dim3(n_push + blocks_for(g.cap, 32)), dim3(BLK), 0, st, dv, n_push); \
         else hipLaunchKernelGGL((k_post_fused<G, false, 16>), dim3(n_push), dim3(BLK), 0, st, dv, n_push);        \
     } while (0)
     LANES_SWITCH(g.lanes, POSTF(4), POSTF(16), POSTF(64));
@@ -5671,7 +5627,7 @@ void launch_recalc_basic_vals(const DevView& dv, const Geom& g, const double* rh
     // Large-nucleus regime: the dense-rhs FTRAN x_K = W0 r_K is ONE streaming read of the nucleus inverse through the
     // strip kernel of the pivot loop (k_stream_w, tau side only; the caller has folded the pending terms).  A sharded
     // solve keeps the replicated classic pass (no exchange outside the pivot loop).
-    const bool strips = dv.lrJ && fw_rows(g) != 8 && FW_RL == 1 && stream_strips() && !dv.wshard;
+    const bool strips = strip_tiled(dv, g) && !dv.wshard;
     if (g.cap > 0) {
         if (strips) {
             launch_fused_lr(dv, g, 0, 0, st, 1);
