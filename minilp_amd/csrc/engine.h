@@ -147,6 +147,27 @@ struct Stats {
     uint64_t kase[5] = {0, 0, 0, 0, 0};  // partition-change cases: nuc->nuc, grow, shrink, col swap, same-row
 };
 
+// What ONE iteration launches, decided once (Engine::plan_iteration) for a (phase, DevView, Geom, environment) and read by every stage
+// (Engine::launch_stage).  Plain values; a plan is never compared and never part of a graph's key (get_graph compares Geom).
+enum class IterForm : int { Plain, PrimalHead, SmallBasis, MediumRide, LargeRide, ShardedPull, Factor };  // each one's rule: plan_iteration
+enum class FtranEntry : int { Fused, GatherLrh, PrepGather };  // head inside the gather kernel | delayed-update mode: the same | head launch + gather
+enum class RowForm : int { Inside, Sparse, Sweep };            // Inside: the update kernel's workgroups pull the touched columns (no launch)
+struct IterPlan {
+    int phase, pse, dse, lazy, wtau, inl, fac;
+    IterForm form;
+    FtranEntry ftran;
+    int ftran_ys, ftran_fpk;        // gather: + y_S by row (t_K ride) | no blocked push, the product is pulled in the ratio test's launch
+    int tk_ride, rk_inside;         // launch_ratio_primal
+    int btran, btran_rhs;           // a BTRAN launch exists | its with_rhs
+    int sb_tk_inside;               // launch_small_basis
+    int post_touch, post_rk_ride;   // launch_post_fused
+    int basis_lists_touched;        // the BASIS stage (or the head) carries the touched-column list: the sparse row launches no k_row_touch
+    RowForm row;
+    int row_lists;                  // the dual ROW stage lists the non-zeros of alpha_r: the dual Harris test walks the list
+    int pull_inside, with_struct;   // launch_update_pivot (pull_inside also gives k_primal_head its list / applies arguments)
+    int fac_fused, fac_rho_part, fac_pair;  // compact factor: single-purpose launches inside the solves | MLP_FACTOR_RHO_PART | paired solves
+};
+
 class Engine {
 public:
     Engine();
@@ -306,10 +327,8 @@ private:
     // nucleus stays within ph_kmax slots for the whole batch (the batch is cut short for that); MLP_PRIMAL_HEAD_K overrides the bound (0: off)
     int ph_kmax = -1;                        // -1: primal_head_kmax(longest column)
     bool ph_now = false;
-    bool touch_done = false;                 // the BASIS stage of the iteration being recorded carried the touched-column list
     bool str_now = false, str_clean = false; // geometry of the batch being run; alpha_r / helper are zero outside touched entries
     DevBuf<int> d_ar_list;   // non-basic positions with alpha_r != 0 (dual iteration, CSC-pull tableau row): the dual Harris test walks the list
-    bool ar_built_ = false;  // the ROW stage of the iteration being launched listed them
     DevBuf<int> d_str_list;
     // hypersparse single-workgroup iteration (hyper.inc)
     int hyper_mode = -1;                     // MLP_HYPER: 1 on wherever the kernel applies, 0 off, -1 auto (<= 16 non-zeros per row on average)
@@ -367,7 +386,6 @@ private:
     bool fac_enter(int bump_limit = -1);     // switch to the compact factor (false: the basis does not peel; nothing changed)
     void fac_make_room(int need);
     void fac_leave();                        // back to the explicit nucleus inverse (re-inversion from A)
-    void launch_stage_fac(int phase, int stage, bool with_events);
     void ensure_hyper();         // sharded solve with another rank on this GPU (or unknown): same
     // Lazy dual steepest edge: the primal loop never reads beta, so its iterations skip tau = B^-1 rho (solver.rs:1157)
     // and the beta recurrence; beta is rebuilt exactly from the basis inverse (k_exact_beta) when something next needs it
@@ -554,8 +572,9 @@ private:
     DevBuf<double> d_cval_alt;
     void append_rows_on_device(const std::vector<Constraint>& cs, size_t old_nnz);  // R >= 1 rows, one CSC re-layout
 
-    void record_iteration(int phase, bool with_events);  // enqueue the kernel sequence of ONE iteration
-    void launch_stage(int phase, int stage, bool with_events);
+    IterPlan plan_iteration(int phase) const;                       // the ONLY place that combines the launch predicates (kernels.h)
+    void record_iteration(const IterPlan& pl, bool with_events);    // enqueue the kernel sequence of ONE iteration
+    void launch_stage(const IterPlan& pl, int stage, bool with_events);
   public:
     // engine-level stepping (include/minilp_hip.h: mlp_engine_open / mlp_engine_stage)
     struct StepInfo {
@@ -578,7 +597,8 @@ private:
 
   private:
     int run_loop(int phase);                             // batches of replays until terminal / budget
-    int process_records(int phase, int launched);
+    int process_records();
+    void watch_drift(bool pivoted);  // drift monitor of the inverse, after the records of a batch
     void optimize();              // solver.rs:487-511
     void restore_feasibility();   // solver.rs:513-547
     void recalc_obj_coeffs();     // solver.rs:1199-1231

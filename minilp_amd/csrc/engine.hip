@@ -1432,20 +1432,33 @@ double Engine::cur_obj_val() {
 //   dual  : BTRAN -> ROW -> RATIO (+ FTRAN head) -> FTRAN (+ plan) -> BASIS -> APPLY
 static const int kStageOrder[2][6] = {{STAGE_FTRAN, STAGE_RATIO, STAGE_BTRAN, STAGE_BASIS, STAGE_ROW, STAGE_APPLY},
                                       {STAGE_BTRAN, STAGE_ROW, STAGE_RATIO, STAGE_FTRAN, STAGE_BASIS, STAGE_APPLY}};
-void Engine::launch_stage(int phase, int stage, bool with_events) {
+// The launches of one iteration, decided ONCE for the current view, geometry and environment: the only place where the launch predicates
+// of kernels.h are combined.  The stages below read the plan; nothing they launch reports back.
+IterPlan Engine::plan_iteration(int phase) const {
     const DevView& dv = hview;
     const Geom g = geom();
     const int pse = enable_pse ? 1 : 0;
+    IterPlan pl{};
+    pl.phase = phase, pl.pse = pse, pl.fac = dv.fac_on ? 1 : 0;
+    if (pl.fac) {  // compact factor of the basis (factor.inc): the same stages over level-scheduled solves
+        pl.form = IterForm::Factor, pl.row = RowForm::Sweep;
+        pl.dse = enable_dse ? 1 : 0;
+        pl.inl = (dv.banded && phase == 0 && !stepping) ? 1 : 0;
+        pl.row_lists = (phase == 1 && sweep_lists(dv, 0, 1)) ? 1 : 0;  // (the dual ROW stage asks the sweep for the list of the non-zeros of alpha_r)
+        // A dual iteration without primal steepest edge, run whole (not stepped): the three single-purpose launches around the solves —
+        // the leaving row's scalars, the plan after the FTRAN, the new rank-1 term — ride inside the solves (16.8 us of 170 per pivot on the
+        // 200 000-row transport instance, profiles/r05c_transport_first60k_kernel_stats.csv); bit-identical (MLP_FACTOR_FUSE=0: A/B, tests)
+        static const bool fuse_env = !(std::getenv("MLP_FACTOR_FUSE") && std::getenv("MLP_FACTOR_FUSE")[0] == '0');
+        static const bool rho_part_env = !(std::getenv("MLP_FACTOR_RHO_PART") && std::getenv("MLP_FACTOR_RHO_PART")[0] == '0');
+        pl.fac_pair = fac_pair_ ? 1 : 0, pl.fac_rho_part = rho_part_env ? 1 : 0;
+        pl.fac_fused = (fuse_env && phase == 1 && !pse && pl.dse && fac_pair_ && !stepping) ? 1 : 0;
+        return pl;
+    }
     const bool lazy = lazy_now(phase);                       // primal iteration: no tau, no beta update (ensure_beta() later)
-    const int dse = (enable_dse && !lazy) ? 1 : 0;
-    const int wtau = lazy ? 0 : 1;
+    pl.lazy = lazy ? 1 : 0, pl.dse = (enable_dse && !lazy) ? 1 : 0, pl.wtau = lazy ? 0 : 1;
     // banded sweep, primal iteration: k_update_pivot sums the per-band partials itself (no combine launch);
     // the host-paced stepping API keeps the separate combine so that row_coeffs is readable after STAGE_ROW
-    const int inl = (dv.banded && phase == 0 && !stepping && !g.str) ? 1 : 0;
-    if (dv.fac_on) {  // compact factor of the basis (factor.inc): the same stages over level-scheduled solves
-        launch_stage_fac(phase, stage, with_events);
-        return;
-    }
+    pl.inl = (dv.banded && phase == 0 && !stepping && !g.str) ? 1 : 0;
     // small nucleus (first capacity of the inverse), lazy primal iteration: BTRAN, pass over W, v tail and touched-column list are
     // ONE launch (k_small_basis) issued at the BASIS stage; the BTRAN stage is empty.  MLP_SMALL_BASIS=0: the three launches.
     // ... and for a nucleus of a few dozen columns the whole chain FTRAN -> ratio test -> BTRAN -> inverse update -> touched columns -> partition
@@ -1467,103 +1480,138 @@ void Engine::launch_stage(int phase, int stage, bool with_events) {
     // medium nucleus (eager update, heads inside their kernels): t_K rides in the ratio launch and its final block forms rho_K — the BTRAN stage
     // is empty.  MLP_BTRAN_RIDE=0: k_btran.
     const bool btr = !phead && !smallb && !tkr && !fpl && phase == 0 && pse && lazy && !stepping && shard_world == 1 && !shard_is_live() && btran_rides_ratio(dv, g);
-    if (stage == STAGE_BASIS) touch_done = false;
+    pl.form = phead ? IterForm::PrimalHead : smallb ? IterForm::SmallBasis : btr ? IterForm::MediumRide : tkr ? IterForm::LargeRide
+              : fpl ? IterForm::ShardedPull : IterForm::Plain;
+    // FTRAN entry: K2 head inside the gather kernel (one launch) | delayed-update mode: the head inside the gather too (round 5) | head + gather
+    if (phase == 0 && g.head_fused) pl.ftran = FtranEntry::Fused;
+    else if (phase == 0 && !stepping && max_col_nnz_ <= HEAD_LIST_CAP && (fpl || ftran_head_rides_gather(dv, g))) pl.ftran = FtranEntry::GatherLrh;
+    else pl.ftran = FtranEntry::PrepGather;
+    pl.ftran_ys = tkr ? 1 : 0, pl.ftran_fpk = fpl ? 1 : 0;
+    pl.tk_ride = tkr ? 1 : ((tkr_s || btr) ? 2 : 0), pl.rk_inside = btr ? 1 : 0;
+    pl.btran = (phead || smallb || rkr || btr) ? 0 : 1;
+    pl.btran_rhs = (phase == 0 && !tkr && !fpl) ? pse : 0;  // tK = alpha_K - F^T y_S in the BTRAN launch (unless it rode in the ratio launch)
+    pl.sb_tk_inside = tkr_s ? 0 : 1;
+    pl.post_touch = (g.str && phase == 0) ? 1 : 0, pl.post_rk_ride = rkr ? 1 : 0;
+    pl.basis_lists_touched = (phead || smallb || post_fused_lists_touched(dv, g, pse, 0, pl.post_touch)) ? 1 : 0;  // (head | k_small_basis | v tail)
+    // small-nucleus primal head: the update kernel's workgroups pull the touched columns of their own positions (1), and the head also applies the
+    // basic side of the pivot and position q (2)
+    pl.pull_inside = (phead && g.str && update_pulls_inside(dv, g)) ? (head_applies(dv, g) ? 2 : 1) : 0;
+    pl.row = !g.str ? RowForm::Sweep : (pl.pull_inside ? RowForm::Inside : RowForm::Sparse);
+    pl.row_lists = (phase == 1 && !g.str && sweep_lists(dv, 0, 1)) ? 1 : 0;  // (the dual ROW stage asks the sweep for the list of the non-zeros of alpha_r)
+    pl.with_struct = (phase == 1 && !pse) ? 1 : 0;  // dual path without PSE: the partition change rides in the update launch
+    return pl;
+}
+void Engine::launch_stage(const IterPlan& pl, int stage, bool with_events) {
+    const DevView& dv = hview;
+    const Geom g = geom();
+    const int phase = pl.phase, pse = pl.pse;
+    const bool phead = pl.form == IterForm::PrimalHead;
+    if (phead && (stage == STAGE_RATIO || stage == STAGE_BTRAN || stage == STAGE_BASIS)) return;  // (all inside the head)
+    // Compact factor (pl.fac): the heads, ratio tests, tableau row and update are the kernels of the default path (their partition-specific parts
+    // are switched off by DevView.fac_on); the solves are k_fac_solve, and the pivot's eta transformation is appended as a rank-1 term just
+    // before the update kernel zeroes alpha_q and rho behind itself.
+    const bool fused = pl.fac_fused, pair = pl.fac_pair;
+    const int dse = pl.dse, rho_whole = pl.fac_rho_part ? 0 : 8;
+    // sampled iteration: an event on the launch stream | the next kernel of a slot stamps the pair ev[e], ev[e + 1] itself (e < 0: disarm)
+    const auto stamp = [&](int e) { if (with_events) HIPCHECK(hipEventRecord(ev[e], st)); };
+    const auto time_slot = [&](int slot, int e) { if (with_events) arm_kernel_timing(slot, e < 0 ? nullptr : ev[e], e < 0 ? nullptr : ev[e + 1]); };
     // The pricing decision (q for primal, r for dual) is already in Ctl: it was taken by the
     // previous iteration's update kernel, or by the standalone pricing kernel at batch start.
     switch (stage) {
     case STAGE_FTRAN:
-        if (with_events) HIPCHECK(hipEventRecord(ev[6], st));
-        if (phead) {
-            if (with_events) arm_kernel_timing(2, ev[2], ev[3]);  // (sampled iteration: the head is timed kernel-exactly in the slot of the pass over W, which it contains)
-            launch_primal_head(dv, g, st);
-            if (with_events) arm_kernel_timing(2, nullptr, nullptr);
-            touch_done = true;
-            if (with_events) HIPCHECK(hipEventRecord(ev[7], st));
+        stamp(6);
+        if (pl.fac) {
+            if (phase == 0) launch_ftran_prep(dv, 1, st);            // entering column's scalars; the column becomes the right-hand side
+            // alpha_q = B^-1 a_q; in a dual iteration rho is known already, so tau = B^-1 rho (solver.rs:1157) shares the walk over the levels
+            if (phase == 1 && dse && pair) launch_fac_solve2(dv, g, 0, 0, 0, 1, 1, st, fused ? 6 : 0);
+            else launch_fac_solve(dv, g, 0, 0, 0, nullptr, 0, st);
+            stamp(7);
+            if (phase == 1 && !fused) launch_post_ftran(dv, g, pse, st);       // ||alpha_q||^2 + 1, plan (1 / alpha_q[r])
             break;
         }
-        if (phase == 0 && g.head_fused) {
-            launch_ftran_fused(dv, g, 1, st);              // K2 head inside the gather kernel (one launch)
-        } else if (phase == 0 && !stepping && max_col_nnz_ <= HEAD_LIST_CAP && (fpl || ftran_head_rides_gather(dv, g))) {
-            launch_ftran_gather_lrh(dv, g, st, tkr ? 1 : 0, fpl ? 1 : 0);  // delayed-update mode: the head inside the gather too (round 5)
-        } else {
-            if (phase == 0) launch_ftran_prep(dv, 1, st);  // K2 head: entering column scalars, singleton rows, list
-            launch_ftran_gather(dv, g, st, tkr ? 1 : 0);   // K2: alpha_q = B^-1 a_q (dual: the head ran in RATIO); t_K ride: + y_S by row
+        if (phead) {
+            time_slot(2, 2);  // (sampled iteration: the head is timed kernel-exactly in the slot of the pass over W, which it contains)
+            launch_primal_head(dv, st, pl.pull_inside ? 0 : 1, pl.pull_inside == 2 ? 1 : 0);
+            time_slot(2, -1);
+            stamp(7);
+            break;
         }
-        if (with_events && !fpl) HIPCHECK(hipEventRecord(ev[7], st));  // (fpl: the F product of this FTRAN runs inside the ratio test's launch — stamped there)
+        if (pl.ftran == FtranEntry::Fused) launch_ftran_fused(dv, g, 1, st);
+        else if (pl.ftran == FtranEntry::GatherLrh) launch_ftran_gather_lrh(dv, g, st, pl.ftran_ys, pl.ftran_fpk);
+        else {
+            if (phase == 0) launch_ftran_prep(dv, 1, st);  // K2 head: entering column scalars, singleton rows, list
+            launch_ftran_gather(dv, g, st, pl.ftran_ys);   // K2: alpha_q = B^-1 a_q (dual: the head ran in RATIO); t_K ride: + y_S by row
+        }
+        if (!pl.ftran_fpk) stamp(7);  // (pulled F product: it runs inside the ratio test's launch — stamped there)
         if (phase == 1) {
             launch_post_ftran(dv, g, pse, st);         // alpha_sq, y_S, partition plan
             if (pse) launch_btran_rhs(dv, g, st);      // tK
         }
         break;
     case STAGE_RATIO:
-        if (phead) break;
-        if (fpl) {
+        if (pl.ftran_fpk) {
             // pull of -F alpha_K (+ y_S) with K5 p1 | K5 p2 (+ K3 head + plan) | t_K; sampled iteration: the FTRAN bracket closes behind the
             // first of the two launches, which completes alpha_q
             launch_fpull_ratio(dv, g, st, with_events ? ev[7] : nullptr);
-        } else if (phase == 0) launch_ratio_primal(dv, g, pse, st, tkr ? 1 : ((tkr_s || btr) ? 2 : 0), btr ? 1 : 0);  // K5 p1 (+ ||alpha||^2, y_S), p2 (+ K3 head + plan) [| t_K]
-        else launch_ratio_dual(dv, g, st, ar_built_ ? 1 : 0);  // K7 p1, p2 (+ K2 head); over the listed non-zeros of alpha_r when the tableau row listed them
-        break;
+        } else if (phase == 0) launch_ratio_primal(dv, g, pse, st, pl.tk_ride, pl.rk_inside);  // K5 p1 (+ ||alpha||^2, y_S), p2 (+ K3 head + plan) [| t_K]
+        else launch_ratio_dual(dv, g, st, pl.row_lists);  // K7 p1, p2 (+ K2 head); over the listed non-zeros of alpha_r when the tableau row listed them
+        break;                                            // (compact factor: its finaliser scatters the entering column for the FTRAN)
     case STAGE_BTRAN:
-        if (phead || smallb || rkr || btr) break;
-        if (phase == 1 && g.head_fused) {
+        if (pl.fac) {
+            if (phase == 1 && !fused) launch_btran_prep(dv, 1, 0, st);         // leaving row's scalars
+            // rho = B^-T e_r, ||rho||^2; in a primal iteration alpha_q is known already, so v = B^-T alpha_q (solver.rs:1114) shares the walk
+            if (phase == 0 && pse && pair) launch_fac_solve2(dv, g, 1, 0, 0, 1, 1, st, rho_whole);
+            else launch_fac_solve(dv, g, 1, 0, 0, nullptr, 0, st, (fused ? 1 : 0) | rho_whole);
+        } else if (!pl.btran) break;
+        else if (phase == 1 && g.head_fused) {
             launch_btran_fused(dv, g, 0, 1, st);                  // K3 head inside the BTRAN kernel (one launch)
         } else {
             if (phase == 1) launch_btran_prep(dv, 1, 0, st);      // K3 head (device-driven by it.r)
-            launch_btran(dv, g, (phase == 0 && !tkr && !fpl) ? pse : 0, st);    // K3: rho, rK, ||rho||^2  |  tK = alpha_K - F^T y_S (unless it rode in the ratio launch)
+            launch_btran(dv, g, pl.btran_rhs, st);                // K3: rho, rK, ||rho||^2  |  tK
         }
         break;
     case STAGE_BASIS:
-        if (phead) {
-            touch_done = true;  // (the head listed the touched columns)
+        if (pl.fac) {
+            if (pse && !(phase == 0 && pair)) launch_fac_solve(dv, g, 1, 1, 1, nullptr, 0, st);   // v = B^-T alpha_q      (solver.rs:1114)
+            if (dse && !(phase == 1 && pair)) launch_fac_solve(dv, g, 0, 1, 1, nullptr, 0, st);   // tau = B^-1 rho        (solver.rs:1157)
             break;
         }
-        if (smallb) {
-            if (with_events) arm_kernel_timing(2, ev[2], ev[3]);  // (sampled iteration: the slot of the pass over the nucleus inverse)
-            launch_small_basis(dv, g, st, tkr_s ? 0 : 1);
-            if (with_events) arm_kernel_timing(2, nullptr, nullptr);
-            touch_done = true;
+        if (pl.form == IterForm::SmallBasis) {
+            time_slot(2, 2);  // (sampled iteration: the slot of the pass over the nucleus inverse)
+            launch_small_basis(dv, g, st, pl.sb_tk_inside);
+            time_slot(2, -1);
             break;
         }
-        if (with_events) {  // sampled iteration: the pass over the nucleus inverse and the fold are timed kernel-exactly
-            arm_kernel_timing(2, ev[2], ev[3]);
-            arm_kernel_timing(3, ev[10], ev[11]);
-        }
-        launch_fused_w(dv, g, pse, st, wtau);                 // tauK / vK partials + eta update of W
-        if (with_events) {
-            arm_kernel_timing(2, nullptr, nullptr);
-            arm_kernel_timing(3, nullptr, nullptr);
-        }
+        time_slot(2, 2), time_slot(3, 10);  // sampled iteration: the pass over the nucleus inverse and the fold are timed kernel-exactly
+        launch_fused_w(dv, g, pse, st, pl.wtau);              // tauK / vK partials + eta update of W
+        time_slot(2, -1), time_slot(3, -1);
         // tau by position (F push)  |  v reduce + scatter  |  (sparse tableau row, primal: its touched-column list)
-        touch_done = launch_post_fused(dv, g, pse, st, 0, 0, wtau, (g.str && phase == 0) ? 1 : 0, rkr ? 1 : 0) != 0;
+        launch_post_fused(dv, g, pse, st, 0, 0, pl.wtau, pl.post_touch, pl.post_rk_ride);
         break;
     case STAGE_ROW:
-        ar_built_ = false;
-        if (g.str) {  // small nucleus: the columns that meet supp(rho) only (k_row_touch + k_row_pull)
-            if (with_events) HIPCHECK(hipEventRecord(ev[0], st));  // (sampled iteration: the two launches bracketed together)
-            if (phead && update_pulls_inside(dv, g)) {  // the update kernel's workgroups pull the touched columns of their own positions
-                if (with_events) HIPCHECK(hipEventRecord(ev[1], st));
-                break;
-            }
-            if (phase == 0) launch_row_sparse(dv, g, pse ? 1 : 0, phead ? 0 : 1, touch_done ? 0 : 1, st);  // (the head applied the partition change itself)
+        if (pl.row == RowForm::Inside) stamp(0), stamp(1);  // the update kernel's workgroups pull the touched columns of their own positions
+        else if (pl.row == RowForm::Sparse) {  // small nucleus: the columns that meet supp(rho) only (k_row_touch + k_row_pull)
+            stamp(0);  // (sampled iteration: the two launches bracketed together)
+            if (phase == 0) launch_row_sparse(dv, g, pse, phead ? 0 : 1, pl.basis_lists_touched ? 0 : 1, st);  // (the head applied the partition change itself)
             else launch_row_sparse(dv, g, 0, 0, 1, st);
-            if (with_events) HIPCHECK(hipEventRecord(ev[1], st));
-            break;
+            stamp(1);
+        } else {
+            if (!pl.fac) time_slot(1, 0);  // sampled iteration: the sweep kernel is timed kernel-exactly
+            if (phase == 0) launch_sweep(dv, g, pse, pl.fac ? 0 : 1, st, pl.inl);  // K4 (+ PSE helper in the same pass)  |  partition change
+            else launch_sweep(dv, g, 0, 0, st, 0, 1);  // K4: alpha_r = rho^T N (+ the list of its non-zeros: CSC-pull form)
+            if (!pl.fac) time_slot(1, -1);
         }
-        if (with_events) arm_kernel_timing(1, ev[0], ev[1]);  // sampled iteration: the sweep kernel is timed kernel-exactly
-        if (phase == 0) launch_sweep(dv, g, pse ? 1 : 0, 1, st, inl);  // K4 (+ PSE helper in the same pass)  |  partition change
-        else ar_built_ = launch_sweep(dv, g, 0, 0, st, 0, 1);  // K4: alpha_r = rho^T N (+ the list of its non-zeros: CSC-pull form)
-        if (with_events) arm_kernel_timing(1, nullptr, nullptr);
         break;
     case STAGE_APPLY:
         if (phase == 1 && pse) {  // dual path: PSE helper  |  partition change
-            if (g.str) launch_row_sparse(dv, g, 2, 1, 0, st);  // (on the columns the ROW stage listed)
-            else launch_sweep(dv, g, 2, 1, st);
+            if (pl.row == RowForm::Sparse) launch_row_sparse(dv, g, 2, 1, 0, st);  // (on the columns the ROW stage listed)
+            else launch_sweep(dv, g, 2, pl.fac ? 0 : 1, st);
         }
-        if (with_events) HIPCHECK(hipEventRecord(ev[4], st));
+        stamp(4);
+        if (pl.fac && !fused) launch_fac_append(dv, st);
         // K8 + zero the work vectors + price the next iteration (dual path without PSE: | partition change)
-        launch_update_pivot(dv, g, phase, dse, pse, st, inl, (phase == 1 && !pse) ? 1 : 0, (phead && g.str && update_pulls_inside(dv, g)) ? (head_applies(dv, g) ? 2 : 1) : 0);
-        if (with_events) HIPCHECK(hipEventRecord(ev[5], st));
+        launch_update_pivot(dv, g, phase, dse, pse, st, pl.inl, pl.with_struct, pl.pull_inside);
+        stamp(5);
         break;
     default:
         throw MlpError(-1, "unknown stage");
@@ -1573,16 +1621,16 @@ static bool use_graph_env() {
     const char* ng = std::getenv("MLP_NO_GRAPH");
     return !(ng && ng[0] == '1');
 }
-void Engine::record_iteration(int phase, bool with_events) {
+void Engine::record_iteration(const IterPlan& pl, bool with_events) {
     if (with_events) HIPCHECK(hipEventRecord(ev[8], st));
     // MLP_DEBUG_SYNC=1 with MLP_NO_GRAPH=1 (eager launches): synchronise after every stage and name it — a device fault is then
     // reported at the stage it belongs to
     static const bool debug_sync = std::getenv("MLP_DEBUG_SYNC") != nullptr && !use_graph_env();
     for (int i = 0; i < 6; ++i) {
-        launch_stage(phase, kStageOrder[phase][i], with_events);
+        launch_stage(pl, kStageOrder[pl.phase][i], with_events);
         if (debug_sync) {
             const hipError_t e = hipStreamSynchronize(st);
-            std::fprintf(stderr, "[mlp] phase %d stage %d: %s\n", phase, kStageOrder[phase][i], hipGetErrorString(e));
+            std::fprintf(stderr, "[mlp] phase %d stage %d: %s\n", pl.phase, kStageOrder[pl.phase][i], hipGetErrorString(e));
         }
     }
     if (with_events) HIPCHECK(hipEventRecord(ev[9], st));
@@ -1657,7 +1705,7 @@ int Engine::step_open(StepInfo* out) {
     int status = h_ctl->it.status;
     step_pos = 0;
     if (status != ITER_PIVOT) {
-        process_records(phase, 1);
+        process_records();
         status = step_finish(phase, status);
     }
     fill_step_info(out, phase);
@@ -1678,7 +1726,7 @@ int Engine::step_stage(int stage, StepInfo* out) {
     }
     stepping = true;   // (stepped iterations keep the beta recurrence: every stage's vector is inspectable, tau included)
     batch_lazy = false;
-    launch_stage(phase, stage, false);
+    launch_stage(plan_iteration(phase), stage, false);  // (a pure function of state that no stage of a stepped iteration changes: RATIO sees what ROW launched)
     stepping = false;
     pull_ctl();
     step_pos += 1;
@@ -1686,16 +1734,15 @@ int Engine::step_stage(int stage, StepInfo* out) {
     if (stage == STAGE_APPLY) {
         // replay the bookkeeping of the iteration just closed; the ring may already hold the terminal
         // record of the NEXT pricing decision (optimal / feasible), which process_records returns
-        int res = process_records(phase, 1);
-        if (h_ctl->max_pivot_err > stats.max_pivot_err) stats.max_pivot_err = h_ctl->max_pivot_err;
+        int res = process_records();
         step_pos = 0;
         status = res;
         if (res != ITER_PIVOT) status = step_finish(phase, res);
-        else if (!(h_ctl->max_pivot_err <= refresh_tol) && (k_ > 0 || fac_on_)) rebuild_inverse();
+        watch_drift(res == ITER_PIVOT);
         h_ctl->it.status = status;
     } else if (status != ITER_PIVOT && status != ITER_FLIP) {
         // UNBOUNDED / INFEASIBLE / SINGULAR decided inside the iteration
-        process_records(phase, 1);
+        process_records();
         status = step_finish(phase, status);
     }
     fill_step_info(out, phase);
@@ -1719,7 +1766,8 @@ hipGraphExec_t Engine::get_graph(int phase, int multi) {
     HIPCHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     try {
         const int iters = multi ? graph_iters : 1;
-        for (int i = 0; i < iters; ++i) record_iteration(phase, false);
+        const IterPlan pl = plan_iteration(phase);  // one plan per capture
+        for (int i = 0; i < iters; ++i) record_iteration(pl, false);
     } catch (...) {
         hipGraph_t junk = nullptr;
         (void)hipStreamEndCapture(st, &junk);
@@ -1734,8 +1782,7 @@ hipGraphExec_t Engine::get_graph(int phase, int multi) {
 
 // Consume the per-pivot records of a batch: statistics, trace and the host mirror of the basis
 // bookkeeping (solver.rs:1088-1091).  Returns the terminal status or ITER_PIVOT to continue.
-int Engine::process_records(int phase, int launched) {
-    (void)launched;
+int Engine::process_records() {
     int n = std::min(h_ctl->ring_n, RING);
     int result = ITER_PIVOT;
     for (int i = 0; i < n; ++i) {
@@ -1773,8 +1820,12 @@ int Engine::process_records(int phase, int launched) {
             result = r.status;
         }
     }
-    (void)phase;
     return result;
+}
+// drift monitor: the pivot element from FTRAN and from the tableau row must agree; re-invert when they disagree by more than refresh_tol
+void Engine::watch_drift(bool pivoted) {
+    if (h_ctl->max_pivot_err > stats.max_pivot_err) stats.max_pivot_err = h_ctl->max_pivot_err;
+    if (pivoted && !(h_ctl->max_pivot_err <= refresh_tol) && (k_ > 0 || fac_on_)) rebuild_inverse();
 }
 
 int Engine::run_loop(int phase) {
@@ -1828,7 +1879,7 @@ int Engine::run_loop(int phase) {
             str_clean = false;  // (the kernel writes alpha_r on its touched columns without zeroing them)
             pull_ctl();
             const uint64_t before = stats.iterations;
-            int res = process_records(phase, B);
+            int res = process_records();
             stats.hyper_iters += stats.iterations - before;
             if (h_ctl->hyper_bail) {
                 // the kernel declined an iteration (a list did not fit its LDS capacities, or the update was too much work for
@@ -1849,8 +1900,7 @@ int Engine::run_loop(int phase) {
             } else if (stats.iterations - before >= 16) {
                 hyper_bail_streak = 0;
             }
-            if (h_ctl->max_pivot_err > stats.max_pivot_err) stats.max_pivot_err = h_ctl->max_pivot_err;
-            if (res == ITER_PIVOT && !(h_ctl->max_pivot_err <= refresh_tol) && (k_ > 0 || fac_on_)) rebuild_inverse();
+            watch_drift(res == ITER_PIVOT);
             if (res != ITER_PIVOT) return res;
             continue;
         }
@@ -1905,13 +1955,10 @@ int Engine::run_loop(int phase) {
         // kernels per pivot, 43 us per pivot on the clock), between two kernels of one graph ~1.4)
         // (second session of round 5: the compact factor too — a batch between two refactorisations is 32 or 64 pivots, three to six graphs
         // of ten iterations instead of one graph launch, and ~8 us of idle device, per pivot)
-        const bool fac_multi = true;
-        const bool multi = graph_now && (long_run || cold_start_) && graph_iters > 1 && (!fac_on_ || fac_multi);
+        const bool multi = graph_now && (long_run || cold_start_) && graph_iters > 1;
         int B = graph_now ? (multi ? RING : batch) : 1;
         if (pivot_budget > 0 && (int64_t)B > pivot_budget) B = (int)pivot_budget;
         if (hyper_gap > 0 && B > hyper_gap) B = hyper_gap;
-        bool use_multi = multi;  // whole multi-iteration graphs first, the remainder of the batch as one-iteration graphs
-        const bool graph_batch = graph_now;
         {   // small-nucleus primal head: the batch must end before the nucleus can outgrow the kernel's slots
             const int kmax = std::min(ph_kmax >= 0 ? ph_kmax : primal_head_kmax(std::max(max_col_nnz_, 1)), primal_head_kmax(std::max(max_col_nnz_, 1)));
             bool ph = str_now && phase == 0 && enable_pse && batch_lazy && shard_world == 1 && !stepping && !fac_on_ && kmax > 0 &&
@@ -1948,9 +1995,9 @@ int Engine::run_loop(int phase) {
         launch_clear_work(dv, st);
         if (phase == 0) launch_price_primal(dv, geom(), enable_pse ? 1 : 0, st);  // opens the first iteration
         else launch_price_dual(dv, geom(), enable_dse ? 1 : 0, st);
-        if (graph_batch) {
-            const int nfull = use_multi ? B / graph_iters : 0;
-            hipGraphExec_t gm = (use_multi && (nfull > 0 || cold_start_)) ? get_graph(phase, 1) : nullptr;  // (cold solve: captured ahead of its first use)
+        if (graph_now) {
+            const int nfull = multi ? B / graph_iters : 0;  // whole multi-iteration graphs first, the remainder of the batch as one-iteration graphs
+            hipGraphExec_t gm = (multi && (nfull > 0 || cold_start_)) ? get_graph(phase, 1) : nullptr;  // (cold solve: captured ahead of its first use)
             hipGraphExec_t g1 = (B - nfull * graph_iters > 0 || !gm) ? get_graph(phase, 0) : nullptr;
             for (int i = 0; i < nfull; ++i) HIPCHECK(hipGraphLaunch(gm, st));
             for (int i = nfull * graph_iters; i < B; ++i) HIPCHECK(hipGraphLaunch(g1, st));
@@ -1959,14 +2006,14 @@ int Engine::run_loop(int phase) {
             if (sample)
                 for (auto& e : ev)
                     if (!e) HIPCHECK(hipEventCreate(&e));
-            record_iteration(phase, sample);
+            record_iteration(plan_iteration(phase), sample);
         }
         const size_t nnz_before = nnz_nonbasic;
         const int k_before = k_;
         const size_t nnz_nuc_before = sample ? nnz_nucleus_cols() : 0;
         pump_until_idle();  // (pump transports: deliver the exchanges of the batch while it runs)
         pull_ctl();
-        int res = process_records(phase, B);
+        int res = process_records();
         if (sample && h_ctl->ring_n >= 1 && h_ctl->ring[0].status == ITER_PIVOT) {
             float ms = 0.f;
             if (geom().str) {
@@ -2017,9 +2064,7 @@ int Engine::run_loop(int phase) {
             }
             (void)hipGetLastError();  // an event pair that was not recorded this iteration is not an error
         }
-        // drift monitor: the pivot element from FTRAN and from the tableau row must agree
-        if (h_ctl->max_pivot_err > stats.max_pivot_err) stats.max_pivot_err = h_ctl->max_pivot_err;
-        if (res == ITER_PIVOT && !(h_ctl->max_pivot_err <= refresh_tol) && (k_ > 0 || fac_on_)) rebuild_inverse();
+        watch_drift(res == ITER_PIVOT);
         if (res == ITER_STALL && !ratio_two && shard_world == 1 && !(phase == 1 && h_ctl->forced)) {
             // The in-kernel wait between the two Harris passes timed out: the grid was not co-resident (another process
             // holds the CUs, or the occupancy estimate was wrong for this partition).  Nothing of the iteration has been
@@ -2458,60 +2503,6 @@ void Engine::fac_leave() {
     HIPCHECK(hipMemsetAsync(&d_ctl.p->nlow, 0, 2 * sizeof(int), st));
     HIPCHECK(hipStreamSynchronize(st));
 }
-// One stage of an iteration on the compact factor: the heads, ratio tests, tableau row and update are the kernels of the default
-// path (their partition-specific parts are switched off by DevView.fac_on); the solves are k_fac_solve, and the pivot's eta
-// transformation is appended as a rank-1 term just before the update kernel zeroes alpha_q and rho behind itself.
-void Engine::launch_stage_fac(int phase, int stage, bool with_events) {
-    const DevView& dv = hview;
-    const Geom g = geom();
-    const int pse = enable_pse ? 1 : 0, dse = enable_dse ? 1 : 0;
-    const int inl = (dv.banded && phase == 0 && !stepping) ? 1 : 0;
-    // A dual iteration without primal steepest edge, run whole (not stepped): the three single-purpose launches around the solves —
-    // the leaving row's scalars, the plan after the FTRAN, the new rank-1 term — ride inside the solves (16.8 us of 170 per pivot on the
-    // 200 000-row transport instance, profiles/r05c_transport_first60k_kernel_stats.csv); bit-identical (MLP_FACTOR_FUSE=0: A/B, tests)
-    static const bool fuse_env = !(std::getenv("MLP_FACTOR_FUSE") && std::getenv("MLP_FACTOR_FUSE")[0] == '0');
-    const bool fused = fuse_env && phase == 1 && !pse && dse && fac_pair_ && !stepping;
-    static const bool rho_part_env = !(std::getenv("MLP_FACTOR_RHO_PART") && std::getenv("MLP_FACTOR_RHO_PART")[0] == '0');
-    switch (stage) {
-    case STAGE_FTRAN:
-        if (with_events) HIPCHECK(hipEventRecord(ev[6], st));
-        if (phase == 0) launch_ftran_prep(dv, 1, st);            // entering column's scalars; the column becomes the right-hand side
-        // alpha_q = B^-1 a_q; in a dual iteration rho is known already, so tau = B^-1 rho (solver.rs:1157) shares the walk over the levels
-        if (phase == 1 && dse && fac_pair_) launch_fac_solve2(dv, g, 0, 0, 0, 1, 1, st, fused ? 6 : 0);
-        else launch_fac_solve(dv, g, 0, 0, 0, nullptr, 0, st);
-        if (with_events) HIPCHECK(hipEventRecord(ev[7], st));
-        if (phase == 1 && !fused) launch_post_ftran(dv, g, pse, st);       // ||alpha_q||^2 + 1, plan (1 / alpha_q[r])
-        break;
-    case STAGE_RATIO:
-        if (phase == 0) launch_ratio_primal(dv, g, pse, st);
-        else launch_ratio_dual(dv, g, st, ar_built_ ? 1 : 0);    // (its finaliser scatters the entering column for the FTRAN)
-        break;
-    case STAGE_BTRAN:
-        if (phase == 1 && !fused) launch_btran_prep(dv, 1, 0, st);         // leaving row's scalars
-        // rho = B^-T e_r, ||rho||^2; in a primal iteration alpha_q is known already, so v = B^-T alpha_q (solver.rs:1114) shares the walk
-        if (phase == 0 && pse && fac_pair_) launch_fac_solve2(dv, g, 1, 0, 0, 1, 1, st, rho_part_env ? 0 : 8);
-        else launch_fac_solve(dv, g, 1, 0, 0, nullptr, 0, st, (fused ? 1 : 0) | (rho_part_env ? 0 : 8));
-        break;
-    case STAGE_BASIS:
-        if (pse && !(phase == 0 && fac_pair_)) launch_fac_solve(dv, g, 1, 1, 1, nullptr, 0, st);   // v = B^-T alpha_q      (solver.rs:1114)
-        if (dse && !(phase == 1 && fac_pair_)) launch_fac_solve(dv, g, 0, 1, 1, nullptr, 0, st);   // tau = B^-1 rho        (solver.rs:1157)
-        break;
-    case STAGE_ROW:
-        if (phase == 0) launch_sweep(dv, g, pse ? 1 : 0, 0, st, inl);
-        else ar_built_ = launch_sweep(dv, g, 0, 0, st, 0, 1);
-        break;
-    case STAGE_APPLY:
-        if (phase == 1 && pse) launch_sweep(dv, g, 2, 0, st);
-        if (with_events) HIPCHECK(hipEventRecord(ev[4], st));
-        if (!fused) launch_fac_append(dv, st);
-        launch_update_pivot(dv, g, phase, dse, pse, st, inl, 0);
-        if (with_events) HIPCHECK(hipEventRecord(ev[5], st));
-        break;
-    default:
-        throw MlpError(-1, "unknown stage");
-    }
-}
-
 // ------------------------------------------------------------------ loops (solver.rs:470-547)
 void Engine::initial_solve() {
     double t0 = now_s();
@@ -2699,11 +2690,11 @@ int Engine::fix_var_apply(int var, double val) {
         launch_clear_work(dv, st);
         launch_set_iter(dv, ITER_PIVOT, -1, row, val, 1, st);
         batch_lazy = false;
-        record_iteration(1, false);
+        record_iteration(plan_iteration(1), false);
         pull_ctl();
         int64_t keep = pivot_budget;
         pivot_budget = -1;
-        int res = process_records(1, 1);
+        int res = process_records();
         pivot_budget = keep;
         if (res == ITER_INFEASIBLE) throw LpFail{1};
         if (res != ITER_PIVOT) throw MlpError(-2, "fix_var: forced pivot failed");

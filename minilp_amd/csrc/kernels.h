@@ -441,6 +441,14 @@ struct Geom {
 };
 // Large tiles in the delayed-update mode: the pass over the nucleus inverse is k_stream_w's strip tiling (its partials lie by strip)
 static inline bool strip_tiled(const DevView& dv, const Geom& g) { return dv.lrJ && g.big; }
+// rows per tile of the fused pass: 8 while W is small (more blocks in flight, 14 vs 20 us at
+// k = 1 800), 16 from cap 8192 on (half the v partials; measured 5.0-5.2 TB/s at k = 6 500 either way)
+// (one row tile per block: 4 of them slow the stream down, 251 vs 163 us at k = 10 000, and the v reduce is not the bottleneck)
+static inline int fw_rows(const Geom& g) { return g.big ? 16 : 8; }
+// launch_post_fused lists the touched columns of the sparse tableau row itself (no k_row_touch): the plain tail, v reduce, 8-row tiles, list asked
+static inline bool post_fused_lists_touched(const DevView& dv, const Geom& g, int with_v, int classic, int touch) { return (classic || !strip_tiled(dv, g)) && with_v && fw_rows(g) == 8 && touch; }
+// launch_sweep lists the non-zeros of alpha_r (DevView.ar_list) for the dual Harris test: k_sweep MODE 0, not the banded form
+static inline bool sweep_lists(const DevView& dv, int mode, int list) { return !dv.banded && mode == 0 && list && dv.ar_list != nullptr; }
 
 // ---- launch wrappers (all asynchronous on `st`; the DevView is passed to the kernels by value) ----
 void launch_clear_work(const DevView& dv, hipStream_t st);  // alpha_q, tau, rv := 0 (one memset)
@@ -468,7 +476,7 @@ void launch_post_ftran(const DevView& dv, const Geom& g, int use_pse, hipStream_
 void launch_btran_prep(const DevView& dv, int derive_dual, int plan_after, hipStream_t st);  // BTRAN head (one wave)
 void launch_btran(const DevView& dv, const Geom& g, int with_rhs, hipStream_t st, int after_fold = 0);  // rho, rK, rho_sq [| tK]
 void launch_btran_rhs(const DevView& dv, const Geom& g, hipStream_t st);                  // tK alone
-bool launch_sweep(const DevView& dv, const Geom& g, int mode, int with_struct, hipStream_t st, int inline_combine = 0, int list = 0);  // K4 [| partition change]; true: mode 0 and the non-zeros of alpha_r were listed (DevView.ar_list)
+void launch_sweep(const DevView& dv, const Geom& g, int mode, int with_struct, hipStream_t st, int inline_combine = 0, int list = 0);  // K4 [| partition change]; list: see sweep_lists
 // sparse tableau row: touched-column list, then the pull of alpha_r / helper on the listed columns (| partition change)
 void launch_row_sparse(const DevView& dv, const Geom& g, int mode, int with_struct, int touch, hipStream_t st);
 // small nucleus (first capacity), lazy primal iteration: BTRAN + pass over W + v tail + touched-column list in ONE launch
@@ -478,11 +486,11 @@ void launch_small_basis(const DevView& dv, const Geom& g, hipStream_t st, int tk
 // the pricing decision and the tableau row in ONE launch of one workgroup (primal_head.inc)
 bool primal_head_supported(const DevView& dv, const Geom& g);
 int primal_head_kmax(int longest_column);  // largest nucleus the kernel serves for a model whose longest column has that many entries (0: none)
-void launch_primal_head(const DevView& dv, const Geom& g, hipStream_t st);
+void launch_primal_head(const DevView& dv, hipStream_t st, int list, int applies);  // list: the touched columns as a list (k_row_pull follows); applies: head_applies
 void launch_init_nb_rng(const DevView& dv, const Geom& g, hipStream_t st);
 void launch_ratio_dual(const DevView& dv, const Geom& g, hipStream_t st, int list_ok = 0); // K7 p1, p2 (+FTRAN head); list_ok: the tableau row of this iteration listed its non-zeros
 void launch_fused_w(const DevView& dv, const Geom& g, int with_v, hipStream_t st, int with_tau = 1);  // tauK/vK partials + eta update of W
-int launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t st, int classic = 0, int skip_push = 0, int with_tau = 1, int touch = 0, int rk_ride = 0);
+void launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t st, int classic = 0, int skip_push = 0, int with_tau = 1, int touch = 0, int rk_ride = 0);  // touch: see post_fused_lists_touched
 bool rk_rides_post(const DevView& dv, const Geom& g);  // (strip-tiled tail of the large-nucleus pass: the form that carries the rho_K blocks)
 void launch_exact_beta(const DevView& dv, hipStream_t st);  // beta_p = ||e_p^T B^-1||^2 for every basic position (lazy dual steepest edge)
 // hypersparse iteration (hyper.inc): up to max_iters dual iterations (no primal steepest edge) in ONE launch of one workgroup

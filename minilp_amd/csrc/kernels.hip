@@ -1410,16 +1410,15 @@ static void launch_blocked_push(const DevView& dv, int which, hipStream_t st, in
     // (a band form of this push — LDS blocks of the band-major copy — was measured in round 2: 34.6 + 9.5 us against 34.8 + 6.4 us,
     // neither bound by its traffic; removed.  Round 6: in the lazy primal iteration the product is PULLED instead: fpull.inc)
     // slot chunks: as many as keep (row blocks x chunks) within one round of workgroups (3 per CU by LDS), at most PB_CHUNKS
-    const int want = 0;
+    static_assert(PB_CHUNKS_DEFAULT <= PB_CHUNKS, "the partial-sum buffer holds PB_CHUNKS chunks");
     int chunks = PB_CHUNKS_DEFAULT;  // (24 measured best: 727 / 731 / 732 / 746 us per pivot at k = 20 500 for 24 / 30 / 36 / 48)
-    if (chunks > PB_CHUNKS) chunks = PB_CHUNKS;
     if (dv.pb_det) {  // fixed-point limbs: order-independent
         static bool det_attr = false;
         if (!det_attr) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_push_stage1_det), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PBD_LDS);
             det_attr = true;
         }
-        if (want <= 0) chunks = PBD_CHUNKS_DEFAULT;  // (two workgroups per CU by LDS: row blocks x chunks should fit one round)
+        chunks = PBD_CHUNKS_DEFAULT;  // (two workgroups per CU by LDS: row blocks x chunks should fit one round)
         hipLaunchKernelGGL(k_push_stage1_det, dim3(dv.pb_rb, chunks), dim3(BLK), PBD_LDS, st, dv, which);
     } else hipLaunchKernelGGL(k_push_stage1, dim3(dv.pb_rb, chunks), dim3(BLK), 0, st, dv, which);
     hipLaunchKernelGGL(k_push_combine, dim3((dv.m + BLK - 1) / BLK), dim3(BLK), 0, st, dv, which, chunks, ys);
@@ -5152,27 +5151,20 @@ static bool ratio_one_enabled() {  // MLP_RATIO_ONE=0: the grid forms at any siz
     const char* e = std::getenv("MLP_RATIO_ONE");  // (read per launch: tests switch it inside one process)
     return !(e && e[0] == '0');
 }
-// t_K rides in the ratio launch (k_ratio_primal_fused, n_ratio > 0): the one-launch grid form of the test is the one that runs,
-// the blocked F push is on (its combine leaves y_S by row) and the delayed-update mode is on (large nucleus)
-bool tk_rides_ratio(const DevView& dv, const Geom& g) {
+// t_K rides in the ratio launch (k_ratio_primal_fused, n_ratio > 0): the one-launch grid form of the test is the one that runs, ...
+static bool tk_ride_grid_runs(const DevView& dv, const Geom& g) {
     const char* e = std::getenv("MLP_TK_RIDE");
     if (e && e[0] == '0') return false;
-    if (dv.world > 1 || !dv.pb_on || !dv.lrJ || g.ratio_two || g.cap <= 0) return false;
+    if (dv.world > 1 || g.ratio_two || g.cap <= 0) return false;
     if (g.m <= 16384 && ratio_one_enabled()) return false;
     const int nb = grid_for(g.m);
     const int max_coresident = coresident_half(reinterpret_cast<const void*>(k_ratio_primal_fused), 0);
     return nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m;
 }
+// ... the blocked F push is on (its combine leaves y_S by row) and the delayed-update mode is on (large nucleus)
+bool tk_rides_ratio(const DevView& dv, const Geom& g) { return dv.pb_on && dv.lrJ && tk_ride_grid_runs(dv, g); }
 // ... and for a small nucleus (k_small_basis): the grid form of the test runs (in its sparse form block 0 alone works), t_K with y_S on the fly
-bool tk_rides_ratio_small(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_TK_RIDE");
-    if (e && e[0] == '0') return false;
-    if (dv.world > 1 || g.ratio_two || g.cap <= 0 || !dv.rowinfo) return false;
-    if (g.m <= 16384 && ratio_one_enabled()) return false;
-    const int nb = grid_for(g.m);
-    const int max_coresident = coresident_half(reinterpret_cast<const void*>(k_ratio_primal_fused), 0);
-    return nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m;
-}
+bool tk_rides_ratio_small(const DevView& dv, const Geom& g) { return dv.rowinfo && tk_ride_grid_runs(dv, g); }
 // Pulled F product (fpull.inc): two launches, neither with an in-kernel wait.  The first reduces over one block per 32 items (m rows + cap
 // slots): its partials travel through a buffer of their own (DevView.fpk_part), which every block of the second launch folds for itself.
 // The second launch holds PT = 4 positions per thread of its grid_for(m) ratio blocks and has no stride loop: beyond 4 * BLK * 512 =
@@ -5298,23 +5290,23 @@ static void launch_sweep_banded(const DevView& dv, const Geom& g, int mode, int 
     else if (mode == 1) hipLaunchKernelGGL(k_band_combine<1>, gc, dim3(BLK), 0, st, dv, nc);
     else hipLaunchKernelGGL(k_band_combine<2>, gc, dim3(BLK), 0, st, dv, nc);
 }
-bool launch_sweep(const DevView& dv, const Geom& g, int mode, int with_struct, hipStream_t st, int inline_combine, int list) {
+void launch_sweep(const DevView& dv, const Geom& g, int mode, int with_struct, hipStream_t st, int inline_combine, int list) {
     if (dv.banded) {
         launch_sweep_banded(dv, g, mode, with_struct, inline_combine, st);
-        return false;
+        return;
     }
+    const int lists = sweep_lists(dv, mode, list) ? 1 : 0;  // (k_sweep MODE 0 lists the non-zeros of alpha_r)
 #define SWEEP(G, U)                                                                                               \
     do {                                                                                                          \
         int n_sweep = blocks_for((long)(dv.nb_hi - dv.nb_lo) * G);                                                \
         dim3 gr(n_sweep + (with_struct ? blocks_for(g.cap) : 0)), b(BLK);                                         \
-        if (mode == 0) LAUNCH_T(1, (k_sweep<G, U, 0>), gr, b, 0, st, dv, n_sweep, list);                         \
+        if (mode == 0) LAUNCH_T(1, (k_sweep<G, U, 0>), gr, b, 0, st, dv, n_sweep, lists);                        \
         else if (mode == 1) LAUNCH_T(1, (k_sweep<G, U, 1>), gr, b, 0, st, dv, n_sweep, 0);                    \
         else LAUNCH_T(1, (k_sweep<G, U, 2>), gr, b, 0, st, dv, n_sweep, 0);                                   \
     } while (0)
     if (g.sweep_one) { SWEEP(1, 4); }
     else { LANES_SWITCH(g.lanes, SWEEP(4, 4), SWEEP(16, 4), SWEEP(16, 8)); }
 #undef SWEEP
-    return mode == 0 && list && dv.ar_list != nullptr;  // (k_sweep MODE 0 listed the non-zeros of alpha_r)
 }
 void launch_row_sparse(const DevView& dv, const Geom& g, int mode, int with_struct, int touch, hipStream_t st) {
     if (touch) hipLaunchKernelGGL(k_row_touch, dim3(blocks_for((long)(g.cap + 1) * 64)), dim3(BLK), 0, st, dv);
@@ -5355,10 +5347,8 @@ int primal_head_kmax(int longest_column) {
     const int by_list = PH_AQ_CAP / longest_column - 1;  // supp(alpha_q) <= (k + 1) columns' worth of rows
     return by_list < PH_KMAX ? by_list : PH_KMAX;
 }
-void launch_primal_head(const DevView& dv, const Geom& g, hipStream_t st) {
-    // (the touched columns as a LIST only when k_row_pull follows; the update kernel that pulls them itself reads the stamps)
-    LAUNCH_T(2, k_primal_head, dim3(1), dim3(PH_T), 0, st, dv, update_pulls_inside(dv, g) ? 0 : 1, head_applies(dv, g) ? 1 : 0);
-}
+// (list: the touched columns as a LIST only when k_row_pull follows; the update kernel that pulls them itself reads the stamps)
+void launch_primal_head(const DevView& dv, hipStream_t st, int list, int applies) { LAUNCH_T(2, k_primal_head, dim3(1), dim3(PH_T), 0, st, dv, list, applies); }
 void launch_init_nb_rng(const DevView& dv, const Geom& g, hipStream_t st) {
     hipLaunchKernelGGL(k_init_nb_rng, dim3(blocks_for(g.n)), dim3(BLK), 0, st, dv);
 }
@@ -5379,10 +5369,6 @@ void launch_ratio_dual(const DevView& dv, const Geom& g, hipStream_t st, int lis
     hipLaunchKernelGGL(k_ratio_dual_p1, dim3(grid_for(g.n)), dim3(BLK), 0, st, dv);
     hipLaunchKernelGGL(k_ratio_dual_p2, dim3(grid_for(g.n)), dim3(BLK), 0, st, dv);  // + FTRAN head
 }
-// rows per tile of the fused pass: 8 while W is small (more blocks in flight, 14 vs 20 us at
-// k = 1 800), 16 from cap 8192 on (half the v partials; measured 5.0-5.2 TB/s at k = 6 500 either way)
-// (one row tile per block: 4 of them slow the stream down, 251 vs 163 us at k = 10 000, and the v reduce is not the bottleneck)
-static inline int fw_rows(const Geom& g) { return g.big ? 16 : 8; }
 // 1-D grid of the tiled large-nucleus passes: enough blocks to fill the chip a few times over
 constexpr int FW_TILE_BLOCKS = 4096;
 // strip geometry of k_stream_w: 1 024 columns x 128 rows per block, 4 rows per step (the other shapes were A/B runs: tools/stream_bench.hip)
@@ -5470,44 +5456,38 @@ bool rk_rides_post(const DevView& dv, const Geom& g) {
     if (e && e[0] == '0') return false;
     return strip_tiled(dv, g) && !dv.wshard && dv.world <= 1;
 }
-int launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t st, int classic, int skip_push, int with_tau, int touch, int rk_ride) {
-    // touch: also build the touched-column list of the sparse tableau row in this launch (extra blocks); returns 1 when it
-    // did, 0 when the caller still has to launch k_row_touch on its own
+void launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t st, int classic, int skip_push, int with_tau, int touch, int rk_ride) {
+    // touch: also build the touched-column list of the sparse tableau row in this launch (extra blocks) where
+    // post_fused_lists_touched says so; where it does not, the caller still has to launch k_row_touch on its own
     if (!with_tau) skip_push = 1;  // lazy dual steepest edge: no tau, hence no push of -F tau_K
-    if (!with_tau && !with_v) return 0;
-    const int touch_asked = touch;
+    if (!with_tau && !with_v) return;
     if (!classic && strip_tiled(dv, g)) {  // partials of k_stream_w's strips
         // row-sharded pass: exchange the partials first (k_post_fused then reads the exchange buffer)
         if (dv.wshard) hipLaunchKernelGGL((k_post_exchange<STRIP_RB, STRIP_CH>), dim3(blocks_for(g.cap)), dim3(BLK), 0, st, dv, with_v, with_tau);
-#define POSTS2(G, RB, CH)                                                                                         \
-    {                                                                                                             \
+#define POSTS(G)                                                                                                  \
+    do {                                                                                                          \
+        int n_push = with_tau ? blocks_for((long)g.cap * G) : 0;                                                  \
         if (with_v && rk_ride) {                                                                                  \
             const int n_tail = n_push + blocks_for(g.cap, 32);                                                    \
             int n_rk = blocks_for((long)g.cap * 4);                                                               \
             if (n_rk > 1024) n_rk = 1024;                                                                         \
-            hipLaunchKernelGGL((k_post_fused<G, true, RB, CH>), dim3(n_tail + n_rk), dim3(BLK), 0, st, dv, n_push, -1, fold_fuses_v(dv, with_v, with_tau, 0) ? 1 : 0, n_tail); \
-        } else if (with_v) hipLaunchKernelGGL((k_post_fused<G, true, RB, CH>), dim3(n_push + blocks_for(g.cap, 32)), dim3(BLK), 0, st, dv, n_push, -1, fold_fuses_v(dv, with_v, with_tau, 0) ? 1 : 0, -1); \
-        else hipLaunchKernelGGL((k_post_fused<G, false, RB, CH>), dim3(n_push), dim3(BLK), 0, st, dv, n_push);    \
-    }
-#define POSTS(G)                                                                                                  \
-    do {                                                                                                          \
-        int n_push = with_tau ? blocks_for((long)g.cap * G) : 0;                                                  \
-        POSTS2(G, STRIP_RB, STRIP_CH);  \
+            hipLaunchKernelGGL((k_post_fused<G, true, STRIP_RB, STRIP_CH>), dim3(n_tail + n_rk), dim3(BLK), 0, st, dv, n_push, -1, fold_fuses_v(dv, with_v, with_tau, 0) ? 1 : 0, n_tail); \
+        } else if (with_v) hipLaunchKernelGGL((k_post_fused<G, true, STRIP_RB, STRIP_CH>), dim3(n_push + blocks_for(g.cap, 32)), dim3(BLK), 0, st, dv, n_push, -1, fold_fuses_v(dv, with_v, with_tau, 0) ? 1 : 0, -1); \
+        else hipLaunchKernelGGL((k_post_fused<G, false, STRIP_RB, STRIP_CH>), dim3(n_push), dim3(BLK), 0, st, dv, n_push); \
     } while (0)
         LANES_SWITCH(g.lanes, POSTS(4), POSTS(16), POSTS(64));
 #undef POSTS
-#undef POSTS2
         if (dv.pb_on && !skip_push) launch_blocked_push(dv, 1, st);
         else if (dv.det_pull && with_tau) launch_pull_F(dv, g, 1, st);
-        return 0;
+        return;
     }
+    const bool lists = post_fused_lists_touched(dv, g, with_v, classic, touch);
 #define POSTF(G)                                                                                                  \
     do {                                                                                                          \
         int n_push = with_tau ? blocks_for((long)g.cap * G) : 0;                                                  \
-        if (with_v && fw_rows(g) == 8 && touch) {                                                                 \
+        if (lists) {                                                                                              \
             const int n_tail = n_push + blocks_for(g.cap, 32);                                                    \
             hipLaunchKernelGGL((k_post_fused<G, true, 8>), dim3(n_tail + blocks_for((long)(g.cap + 1) * 64)), dim3(BLK), 0, st, dv, n_push, n_tail); \
-            touch = 0;                                                                                            \
         } else if (with_v && fw_rows(g) == 8) hipLaunchKernelGGL((k_post_fused<G, true, 8>), dim3(n_push + blocks_for(g.cap, 32)), dim3(BLK), 0, st, dv, n_push); \
         else if (with_v) hipLaunchKernelGGL((k_post_fused<G, true, 16>), dim3(n_push + blocks_for(g.cap, 32)), dim3(BLK), 0, st, dv, n_push); \
         else hipLaunchKernelGGL((k_post_fused<G, false, 16>), dim3(n_push), dim3(BLK), 0, st, dv, n_push);        \
@@ -5516,7 +5496,6 @@ int launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t 
 #undef POSTF
     if (dv.pb_on && !skip_push) launch_blocked_push(dv, 1, st);
     else if (dv.det_pull && with_tau) launch_pull_F(dv, g, 1, st);
-    return (touch_asked && !touch) ? 1 : 0;
 }
 void launch_structure_update(const DevView& dv, const Geom& g, hipStream_t st) {
     hipLaunchKernelGGL(k_struct_update, dim3(blocks_for(g.cap)), dim3(BLK), 0, st, dv);
