@@ -4,7 +4,7 @@ minimise, print the objective and the non-zero variables.
 
     python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--tableau VAR] [--gomory-rounds K]
                                  [--gmi-rounds K [--continuous NAME,...]] [--branch-penalties [--continuous NAME,...]]
-                                 [--cutoff VALUE [--continuous NAME,...]]
+                                 [--cutoff VALUE [--tighten] [--continuous NAME,...]]
 
 --ranging adds a sensitivity table: per variable its value, basis status, reduced cost and cost range; per row its dual value and
 rhs range (rows in file order).  --tableau VAR prints the tableau row of the basic variable VAR (by name): its non-zero coefficients on the
@@ -17,7 +17,8 @@ skipped and the counters after each round.  --branch-penalties prints, for every
 LP optimum, the one-pivot bounds of its down and up branch (plain, and with Tomlin's strengthening: every structural variable is integer
 unless listed in --continuous, the slacks are continuous), the child bounds they give and the columns that would enter.  --cutoff VALUE
 prints the bounds that the reduced costs imply once an incumbent of objective VALUE is known (Solution.cutoff_bounds; every structural
-variable is integer unless listed in --continuous): per tightened variable its bounds and whether it can be fixed.
+variable is integer unless listed in --continuous): per tightened variable its bounds and whether it can be fixed.  --tighten then applies
+all of them to the solution on the device (Solution.tighten_by_reduced_cost) and prints the count and the objective, which does not move.
 
 Runs on the MI355X engine (libminilp_hip.so); there is no CPU back end.  `run(B, ...)` takes the module that
 provides the reference's API so that the tests can drive the same code with their checker."""
@@ -29,7 +30,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False, cutoff=None):
+def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False, cutoff=None, tighten=False):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -108,6 +109,9 @@ def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0,
             print("cutoff %.12g: the LP bound %.12g is already worse, nothing to tighten" % (cutoff, sol.objective()))
         else:
             print("cutoff %.12g: %d variables tightened, %d of them fixed, %s" % (cutoff, len(cv), int((clo == chi).sum()), sol.fix_info()))
+            if tighten:
+                sol, count, _ = sol.tighten_by_reduced_cost(cutoff, marks)
+                print("tightened: %d bounds applied on the device, objective %.12g unchanged, %s" % (count, sol.objective(), sol.bounds_info()))
             print("%-12s %14s %14s   %s" % ("variable", "lower", "upper", ""))
             for v, a, b in zip(cv, clo, chi):
                 print("%-12s %14.8g %14.8g   %s" % (names[int(v)], a, b, "fixed" if a == b else ""))
@@ -167,10 +171,12 @@ def main():
                     help="print the one-pivot branching bounds of the fractional basic variables (Solution.branch_penalties)")
     ap.add_argument("--cutoff", type=float, default=None, metavar="VALUE",
                     help="print the bounds the reduced costs imply for an incumbent of objective VALUE (Solution.cutoff_bounds)")
+    ap.add_argument("--tighten", action="store_true",
+                    help="with --cutoff: apply the listed bounds to the solution (Solution.tighten_by_reduced_cost)")
     a = ap.parse_args()
     import minilp_amd as B
     return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau, a.gmi_rounds, [nm for nm in a.continuous.split(",") if nm],
-               a.branch_penalties, a.cutoff)
+               a.branch_penalties, a.cutoff, a.tighten)
 
 
 if __name__ == "__main__":

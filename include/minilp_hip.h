@@ -51,6 +51,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * additive in the same way. */
 /* Still version 5: the reduced-cost bounds and the batched fixing (mlp_solution_cutoff_bounds, mlp_solution_fix_vars,
  * mlp_solution_unfix_vars, mlp_fix_info with its own mlp_fix_info_size()) are additive in the same way. */
+/* Still version 5: the bound changes (mlp_solution_set_var_bounds, mlp_solution_tighten_by_reduced_cost, mlp_solution_var_bounds,
+ * mlp_bounds_info with its own mlp_bounds_info_size()) are additive in the same way. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -551,6 +553,57 @@ typedef struct mlp_fix_info {
 } mlp_fix_info;
 int mlp_solution_fix_info(const mlp_solution* s, mlp_fix_info* out);
 uint64_t mlp_fix_info_size(void);
+
+/* ---- New bounds for the structural variables of a solved model ------------------------------------------------------------------------------
+ * mlp_solution_set_var_bounds gives the listed structural variables the bounds [lo[i], hi[i]] (the user's terms: no sign is turned for
+ *   Maximize) and re-solves with the dual simplex from the basis it finds.  The model keeps its rows: nothing is appended, nothing is
+ *   re-inverted.  It needs a solved model (primal and dual feasible, no exhausted pivot budget), as mlp_solution_cutoff_bounds does: the
+ *   path rests on a dual-feasible basis and never re-enters the primal loop.
+ *   Checked before anything changes, each MLP_EINVAL: a variable out of range or listed twice; a NaN bound, lo = +inf or hi = -inf; a
+ *   column fixed by mlp_solution_fix_var(s) whose value lies outside [lo, hi] (a fixed column otherwise keeps its value and its
+ *   MLP_NB_FIXED status, only its bounds change; mlp_solution_unfix_var(s) later rebuilds its status against the new bounds); a
+ *   solution that is not solved.  lo > hi is status 1 (Infeasible), like a value outside the bounds in mlp_solution_fix_vars.  Then
+ *     1. one classifying pass over the requests (the host sorts them by variable; only private buffers are written).  A BASIC column
+ *        gets no target: only its bounds move.  A NON-BASIC, not fixed column keeps its side: at lower -> target lo, at upper -> target
+ *        hi, both flags set (lo == hi before the call) -> lower if the internal d_j >= 0, else upper, MLP_NB_FREE ->
+ *        clamp(xN_j, lo, hi); diff_j = target_j - xN_j, and the new flags come from the target against lo / hi.
+ *        REFUSAL: if the new bound on the side a non-basic column sits at is infinite, the column would have to change sides and the
+ *        basis would lose dual feasibility; the dual path cannot serve such a request.  If the pass counts one, the call is MLP_EINVAL
+ *        with nothing changed (mlp_last_error says how many).  Unfix or re-solve from a Problem with the new bounds instead.
+ *     2. if any diff_j != 0: r = sum_j diff_j a_j is formed on the device in an order that does not depend on the order of the list,
+ *        ONE FTRAN follows, x_B -= B^-1 r; the objective moves by sum_j diff_j d_j (ascending variable number, a fixed tree); xN_j,
+ *        the flags and the bounds are written.  Two calls with the same list in different orders leave bit-identical state.
+ *     3. ONE dual re-solve after a shift, or when a basic value now violates its bounds (an Infeasible verdict is status 1).  When
+ *        nothing moved and no basic value violates, values and objective keep their bits and there is no pivot.
+ *   A basis blob saved after the call carries no bounds: mlp_problem_solve_from_basis needs a Problem that has the bounds wanted.
+ * mlp_solution_tighten_by_reduced_cost is mlp_solution_cutoff_bounds (the same gap, marks, *pruned and refusals) with EVERY entry
+ *   applied, without the list leaving the device; the host reads back the count (*tightened) only.  A listed column is non-basic at the
+ *   bound that does not move, so nothing shifts: no FTRAN, no re-solve, values and objective keep their bits.  An entry with
+ *   new_lo == new_hi keeps its plain at-bound status; it is not marked MLP_NB_FIXED (that is what fix_vars is for).  A second call at
+ *   the same cutoff tightens nothing.  *pruned = 1 changes nothing.
+ * mlp_solution_var_bounds reads the current bounds of the listed variables (vars == NULL: all of them, n = mlp_solution_num_vars).
+ * The two mutators: n == 0 is a successful no-op; any non-zero status frees the solution and sets *s = NULL; a sharded solution is
+ *   MLP_EINVAL; a pivot budget is lifted; cached duals and ranges are dropped.
+ * mlp_bounds_info: what the last of the two mutators on this solution did (zeros before the first).  Only grows at its end;
+ *   mlp_bounds_info_size() is its size as the library was built. */
+int mlp_solution_set_var_bounds(mlp_solution** s, const uint32_t* vars, const double* lo, const double* hi, uint64_t n);
+int mlp_solution_tighten_by_reduced_cost(mlp_solution** s, double cutoff, const uint8_t* var_is_int, uint32_t num_vars,
+                                         uint64_t* tightened, int* pruned);
+int mlp_solution_var_bounds(const mlp_solution* s, const uint32_t* vars, uint64_t n, double* lo, double* hi);
+typedef struct mlp_bounds_info {
+    uint64_t requests;   /* set_var_bounds: variables listed; tighten_by_reduced_cost: entries applied */
+    uint64_t basic;      /* of them basic at the basis the call found (only their bounds move) */
+    uint64_t nonbasic;   /* of them non-basic */
+    uint64_t shifted;    /* ... of them whose value moved with its bound */
+    uint64_t solves;     /* FTRANs of the shift, 0 or 1 */
+    uint64_t tightened;  /* tighten_by_reduced_cost: entries applied */
+    uint64_t pivots;     /* iterations of the dual re-solve */
+    double bytes;        /* algorithmic bytes of the device work (without the re-solve) */
+    double device_ms;    /* its time on the device (HIP events around the launches) */
+    double wall_ms;      /* the whole call on the host, re-solve included */
+} mlp_bounds_info;
+int mlp_solution_bounds_info(const mlp_solution* s, mlp_bounds_info* out);
+uint64_t mlp_bounds_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

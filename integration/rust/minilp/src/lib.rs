@@ -614,6 +614,50 @@ impl Solution {
         (sol, released as usize)
     }
 
+    /// New bounds `(variable, lo, hi)` for variables of a solved model, then one dual re-solve from the current basis (none when
+    /// nothing moves).  A non-basic variable keeps its side and moves with its bound; making that bound infinite is refused
+    /// (extension: no counterpart in the reference; semantics in `minilp_hip.h`).
+    ///
+    /// # Errors
+    ///
+    /// Will return an error if `lo > hi` for a variable or the problem becomes infeasible with the new bounds.
+    ///
+    /// # Panics
+    ///
+    /// Will panic if a variable is listed twice.
+    pub fn set_var_bounds(self, bounds: &[(Variable, f64, f64)]) -> Result<Self, Error> {
+        assert!(bounds.iter().all(|x| x.0 .0 < self.num_vars));
+        let mut seen: Vec<usize> = bounds.iter().map(|x| x.0 .0).collect();
+        seen.sort_unstable();
+        assert!(seen.windows(2).all(|w| w[0] != w[1]), "set_var_bounds: a variable is listed twice");
+        let vars: Vec<u32> = bounds.iter().map(|x| x.0 .0 as u32).collect();
+        let lo: Vec<f64> = bounds.iter().map(|x| x.1).collect();
+        let hi: Vec<f64> = bounds.iter().map(|x| x.2).collect();
+        self.consume(|s| unsafe { sys::mlp_solution_set_var_bounds(s, vars.as_ptr(), lo.as_ptr(), hi.as_ptr(), vars.len() as u64) })
+    }
+
+    /// [`cutoff_bounds`](Self::cutoff_bounds) with every entry applied to the bounds on the device; returns the solution, how many
+    /// bounds were tightened and whether this LP is already worse than the cutoff (then nothing changes).  Values and objective
+    /// keep their bits (extension).
+    pub fn tighten_by_reduced_cost(self, cutoff: f64, integer_vars: Option<&[bool]>) -> (Self, usize, bool) {
+        let vm: Option<Vec<u8>> = integer_vars.map(|m| m.iter().map(|&b| b as u8).collect());
+        let (vp, vn) = vm.as_ref().map_or((std::ptr::null(), self.num_vars as u32), |m| (m.as_ptr(), m.len() as u32));
+        let (mut count, mut pruned): (u64, std::os::raw::c_int) = (0, 0);
+        let sol = self
+            .consume(|s| unsafe { sys::mlp_solution_tighten_by_reduced_cost(s, cutoff, vp, vn, &mut count, &mut pruned) })
+            .expect("tighten_by_reduced_cost moves no value: it cannot make the problem infeasible");
+        (sol, count as usize, pruned != 0)
+    }
+
+    /// Bounds `(lo, hi)` of a variable as the solution holds them now (extension).
+    pub fn var_bounds(&self, var: Variable) -> (f64, f64) {
+        assert!(var.0 < self.num_vars);
+        let (v, mut lo, mut hi) = (var.0 as u32, 0.0f64, 0.0f64);
+        let st = unsafe { sys::mlp_solution_var_bounds(self.raw, &v, 1, &mut lo, &mut hi) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        (lo, hi)
+    }
+
     /// Add a Gomory cut constraint to the problem and return the solution.  (`lib.rs:419-423`)
     ///
     /// # Errors

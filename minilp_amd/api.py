@@ -86,6 +86,11 @@ class MlpFixInfo(C.Structure):  # include/minilp_hip.h: mlp_fix_info (only grows
                 ("pivots", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class MlpBoundsInfo(C.Structure):  # include/minilp_hip.h: mlp_bounds_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("basic", C.c_uint64), ("nonbasic", C.c_uint64), ("shifted", C.c_uint64), ("solves", C.c_uint64),
+                ("tightened", C.c_uint64), ("pivots", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -234,6 +239,13 @@ def lib():
     sig("mlp_solution_fix_vars", i32, C.POINTER(vp), pu32, pdbl, u64)
     sig("mlp_solution_unfix_vars", i32, C.POINTER(vp), pu32, u64, pu64)
     sig("mlp_solution_fix_info", i32, vp, C.POINTER(MlpFixInfo))
+    sig("mlp_bounds_info_size", u64)
+    if L.mlp_bounds_info_size() != C.sizeof(MlpBoundsInfo):
+        raise ImportError(f"{_SO}: mlp_bounds_info is {L.mlp_bounds_info_size()} bytes, this binding {C.sizeof(MlpBoundsInfo)}: rebuild it")
+    sig("mlp_solution_set_var_bounds", i32, C.POINTER(vp), pu32, pdbl, pdbl, u64)
+    sig("mlp_solution_tighten_by_reduced_cost", i32, C.POINTER(vp), dbl, pu8, u32, pu64, C.POINTER(i32))
+    sig("mlp_solution_var_bounds", i32, vp, pu32, u64, pdbl, pdbl)
+    sig("mlp_solution_bounds_info", i32, vp, C.POINTER(MlpBoundsInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -767,6 +779,45 @@ class Solution:
         r = MlpFixInfo()
         _raise(lib().mlp_solution_fix_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in MlpFixInfo._fields_}
+
+    # ---- new bounds for structural variables (include/minilp_hip.h: mlp_solution_set_var_bounds ...; semantics there)
+    def set_var_bounds(self, vars, lo, hi):
+        """New bounds [lo[i], hi[i]] for the listed structural variables of a solved model, then one dual re-solve from the current
+        basis (none when nothing moves).  A non-basic variable keeps its side and moves with its bound; making that bound infinite is
+        refused.  lo > hi raises Infeasible."""
+        v = self._var_list(vars, "set_var_bounds")
+        a = np.ascontiguousarray(list(lo), dtype=np.float64).reshape(-1)
+        b = np.ascontiguousarray(list(hi), dtype=np.float64).reshape(-1)
+        if len(a) != len(v) or len(b) != len(v):
+            raise InternalError(-1, "set_var_bounds: vars, lo and hi differ in length")
+        h = self._take()
+        _raise(lib().mlp_solution_set_var_bounds(C.byref(h), _p(v, C.c_uint32), _p(a, C.c_double), _p(b, C.c_double), len(v)))
+        return Solution(h)
+
+    def tighten_by_reduced_cost(self, cutoff, integer_vars=None):
+        """cutoff_bounds with every entry applied to the bounds on the device.  Returns (Solution, count, pruned); values and objective
+        keep their bits, and a pruned LP is left as it is."""
+        n = self.num_vars
+        vm = None if integer_vars is None else self._int_mask(integer_vars, n)
+        h = self._take()
+        count, pruned = C.c_uint64(), C.c_int()
+        _raise(lib().mlp_solution_tighten_by_reduced_cost(C.byref(h), float(cutoff), None if vm is None else _p(vm, C.c_uint8),
+                                                          n if vm is None else len(vm), C.byref(count), C.byref(pruned)))
+        return Solution(h), int(count.value), bool(pruned.value)
+
+    def var_bounds(self, vars=None):
+        """(lo, hi) of the listed structural variables as the solution holds them now; vars=None: all of them."""
+        v = None if vars is None else self._var_list(vars, "var_bounds")
+        n = self.num_vars if v is None else len(v)
+        lo, hi = np.zeros(n), np.zeros(n)
+        _raise(lib().mlp_solution_var_bounds(self._h, None if v is None else _p(v, C.c_uint32), n, _p(lo, C.c_double), _p(hi, C.c_double)))
+        return lo, hi
+
+    def bounds_info(self):
+        """Counters of the last set_var_bounds / tighten_by_reduced_cost call (mlp_bounds_info) as a dict."""
+        r = MlpBoundsInfo()
+        _raise(lib().mlp_solution_bounds_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpBoundsInfo._fields_}
 
     def cut_info(self):
         """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""

@@ -25,6 +25,7 @@ struct mlp_solution {
     Engine::GmiInfo gmi;          // of the last mlp_solution_add_gmi_cuts call
     Engine::BranchInfo branch;    // of the last mlp_solution_branch_penalties call
     Engine::FixInfo fix;          // of the last mlp_solution_cutoff_bounds / mlp_solution_fix_vars / mlp_solution_unfix_vars call
+    Engine::BoundsInfo bounds;    // of the last mlp_solution_set_var_bounds / mlp_solution_tighten_by_reduced_cost call
     std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
     std::vector<uint32_t> tab_indices;
     std::vector<double> tab_values;
@@ -736,6 +737,75 @@ int mlp_solution_fix_info(const mlp_solution* s, mlp_fix_info* out) {
     });
 }
 uint64_t mlp_fix_info_size(void) { return (uint64_t)sizeof(mlp_fix_info); }
+
+// ---- new bounds for structural variables (bounds.inc)
+int mlp_solution_set_var_bounds(mlp_solution** s, const uint32_t* vars, const double* lo, const double* hi, uint64_t n) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        Engine* e = (*s)->eng;
+        if (n && (!vars || !lo || !hi)) throw MlpError(MLP_EINVAL, "set_var_bounds: NULL list");
+        std::vector<int> v;
+        std::vector<double> l, h;
+        for (uint64_t i = 0; i < n; ++i) {  // (each index is checked as it is read, nothing is sized by n)
+            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "set_var_bounds: variable out of range");
+            v.push_back((int)vars[i]);
+            l.push_back(lo[i]);
+            h.push_back(hi[i]);
+        }
+        (*s)->bounds = Engine::BoundsInfo();
+        if (n == 0) return;
+        if (!e->solved()) throw MlpError(MLP_EINVAL, "set_var_bounds: model not solved");
+        e->pivot_budget = -1;
+        stale(*s);
+        e->set_var_bounds(v, l, h, (*s)->bounds);
+    }));
+}
+int mlp_solution_tighten_by_reduced_cost(mlp_solution** s, double cutoff, const uint8_t* var_is_int, uint32_t num_vars, uint64_t* tightened,
+                                         int* pruned) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        Engine* e = (*s)->eng;
+        if (e->transport != "none") throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost is not available on a sharded solution");
+        if (!tightened || !pruned) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: NULL tightened / pruned");
+        *tightened = 0;
+        *pruned = 0;
+        if (std::isnan(cutoff)) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: the cutoff is NaN");
+        if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: num_vars must be mlp_solution_num_vars");
+        if (!e->solved()) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: model not solved");
+        const double obj = e->cur_obj_val();                                 // the gap exactly as mlp_solution_cutoff_bounds forms it
+        const double user = e->direction == 1 ? -obj : obj;
+        const double g = e->direction == 1 ? user - cutoff : cutoff - user;
+        if (std::isnan(g)) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: the gap is NaN");
+        (*s)->bounds = Engine::BoundsInfo();
+        if (g < 0.0) {  // the node is worse than the cutoff: nothing changes
+            *pruned = 1;
+            return;
+        }
+        e->pivot_budget = -1;
+        stale(*s);
+        *tightened = e->tighten_by_reduced_cost(g, var_is_int, (*s)->bounds);
+    }));
+}
+int mlp_solution_var_bounds(const mlp_solution* s, const uint32_t* vars, uint64_t n, double* lo, double* hi) {
+    return guarded([&] {
+        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+        if (!vars && n != (uint64_t)s->eng->num_vars) throw MlpError(MLP_EINVAL, "var_bounds: without a list the length must be the number of variables");
+        if (n && (!lo || !hi)) throw MlpError(MLP_EINVAL, "var_bounds: NULL output");
+        s->eng->var_bounds(vars, n, lo, hi);
+    });
+}
+int mlp_solution_bounds_info(const mlp_solution* s, mlp_bounds_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / bounds info");
+        std::memset(out, 0, sizeof(*out));
+        const Engine::BoundsInfo& f = s->bounds;
+        out->requests = f.requests; out->basic = f.basic; out->nonbasic = f.nonbasic; out->shifted = f.shifted; out->solves = f.solves;
+        out->tightened = f.tightened; out->pivots = f.pivots; out->bytes = f.bytes; out->device_ms = f.device_ms; out->wall_ms = f.wall_ms;
+    });
+}
+uint64_t mlp_bounds_info_size(void) { return (uint64_t)sizeof(mlp_bounds_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

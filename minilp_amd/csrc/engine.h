@@ -252,6 +252,18 @@ public:
     // served together (one FTRAN, none when nothing moves), the basic ones by one forced dual pivot each, feasibility restored once
     void fix_vars(const std::vector<int>& vars, const std::vector<double>& vals, FixInfo& info);
     uint64_t unfix_vars(const std::vector<int>& vars, FixInfo& info);  // unfix_var's rule per request, ONE optimize(); returns the released count
+    // New bounds for structural variables of a solved model (bounds.inc; include/minilp_hip.h mlp_solution_set_var_bounds,
+    // mlp_solution_tighten_by_reduced_cost).  BoundsInfo describes the last of the two mutators.
+    struct BoundsInfo {
+        uint64_t requests = 0, basic = 0, nonbasic = 0, shifted = 0, solves = 0, tightened = 0, pivots = 0;
+        double bytes = 0, device_ms = 0, wall_ms = 0;
+    };
+    // every non-basic request keeps its side and moves with its bound (one FTRAN for all, none when nothing moves), a basic request
+    // only gets its bounds; ONE dual re-solve when a value moved or a basic value now violates its bounds
+    void set_var_bounds(const std::vector<int>& vars, const std::vector<double>& lo, const std::vector<double>& hi, BoundsInfo& info);
+    // cutoff_bounds with every entry applied on the device (g as there); the host reads back the count only
+    uint64_t tighten_by_reduced_cost(double g, const uint8_t* var_is_int, BoundsInfo& info);
+    void var_bounds(const uint32_t* vars, uint64_t n, double* lo, double* hi);  // vars == nullptr: all num_vars of them
     // Reading the tableau of the current basis (tableau.inc; include/minilp_hip.h mlp_solution_binv_rows ...).  Columns:
     // j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by CONSTRAINT (0 / ignored for one
     // without a row), vectors by position have length num_rows().  Internal form A x + s = b: no sign turn for Maximize.  Requests are
@@ -303,6 +315,14 @@ private:
     // --- host mirror (integer bookkeeping + the matrix for rebuilds)
     int m_ = 0, N_ = 0, k_ = 0, cap_ = 0;
     std::vector<double> h_obj, h_lo, h_hi, h_rhs;
+    // tighten_by_reduced_cost writes bounds on the device without the list leaving it: h_lo / h_hi of the structural variables are then
+    // read back on first use.  Every host reader of h_lo / h_hi after set-up calls host_bounds() first.
+    bool bounds_mirror_stale_ = false;
+    void host_bounds();
+    struct CutoffRun;  // the private device buffers of one run of launch_cutoff_bounds
+    struct ShiftBufs;  // the blocks of the shift that fix_vars and set_var_bounds share
+    double shift_basic_values(FixBufs& b, ShiftBufs& w);
+    void cutoff_launch(double g, const uint8_t* var_is_int, CutoffRun& r);
     std::vector<int> h_cons_row;  // constraint (Problem / Solution::add_constraint order) -> row; -1 for one without terms (no row)
     std::vector<int> h_rptr, h_rcol;
     std::vector<double> h_rval;

@@ -623,6 +623,7 @@ void Engine::build_csc() {  // counting transpose of the CSR: ascending row inde
     }
 }
 void Engine::upload_matrix() {
+    host_bounds();
     d_cptr.upload(h_cptr, st); d_crow.upload(h_crow, st); d_cval.upload(h_cval, st);
     d_rptr.upload(h_rptr, st); d_rcol.upload(h_rcol, st); d_rval.upload(h_rval, st);
     d_lo.upload(h_lo, st); d_hi.upload(h_hi, st); d_obj.upload(h_obj, st);
@@ -2666,6 +2667,7 @@ void Engine::fix_var(int var, double val) {  // solver.rs:378-415
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
     double t0 = now_s();
     ensure_beta();
+    host_bounds();
     if (val < h_lo[var] || val > h_hi[var]) throw LpFail{1};
     fix_var_apply(var, val);
     primal_feasible = false;
@@ -2719,6 +2721,7 @@ bool Engine::unfix_var(int var) {  // solver.rs:418-438
     if (!h_nb_fixed[col]) return false;
     h_nb_fixed[col] = 0;
     fetch_values();
+    host_bounds();
     double cur = h_xN[col];
     uint8_t f = (uint8_t)((cur == h_lo[var] ? NB_AT_MIN : 0) | (cur == h_hi[var] ? NB_AT_MAX : 0));
     HIPCHECK(hipMemcpyAsync(d_nbflags.p + col, &f, 1, hipMemcpyHostToDevice, st));
@@ -3458,6 +3461,7 @@ void Engine::load_basis(const uint8_t* blob, size_t len) {
     h_nb_vars = nv;
     h_var_loc = loc;
     h_nb_fixed.assign(nn, 0);
+    host_bounds();
     std::vector<double> loB(mm), hiB(mm);
     for (size_t r = 0; r < mm; ++r) { loB[r] = h_lo[bv[r]]; hiB[r] = h_hi[bv[r]]; }
     nnz_nonbasic = 0;
@@ -3543,6 +3547,7 @@ Engine* Engine::clone() {
     Engine* e = owner.get();
     e->num_vars = num_vars; e->direction = direction;
     e->m_ = m_; e->N_ = N_;
+    host_bounds();
     e->h_obj = h_obj; e->h_lo = h_lo; e->h_hi = h_hi; e->h_rhs = h_rhs;
     e->h_cons_row = h_cons_row;
     e->h_rptr = h_rptr; e->h_rcol = h_rcol; e->h_rval = h_rval;
@@ -3649,8 +3654,8 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
         tmp.assign(t.begin(), t.end());
     } else if (w == "cur_obj_val") tmp = {cur_obj_val()};
     else if (w == "orig_obj_coeffs") tmp = h_obj;
-    else if (w == "orig_var_mins") tmp = h_lo;
-    else if (w == "orig_var_maxs") tmp = h_hi;
+    else if (w == "orig_var_mins") { host_bounds(); tmp = h_lo; }
+    else if (w == "orig_var_maxs") { host_bounds(); tmp = h_hi; }
     else if (w == "orig_rhs") tmp = h_rhs;
     else if (w == "csr_indptr") tmp.assign(h_rptr.begin(), h_rptr.end());    // A with the slack identity, by row (the oracle's names)
     else if (w == "csr_indices") tmp.assign(h_rcol.begin(), h_rcol.end());
@@ -4244,6 +4249,35 @@ void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_
 }
 
 // ------------------------------------------------------------------ fixing (fixing.inc)
+// One run of launch_cutoff_bounds on private buffers (nothing is read back here): the list lies in ovar / olo / ohi, its length at count();
+// ev.e[0] is recorded in front of the launches, the caller records ev.e[1] behind its own.
+struct Engine::CutoffRun {
+    EventPair ev;
+    DevBuf<int> tcnt, toff, sums;
+    DevBuf<uint32_t> svar, ovar;
+    DevBuf<double> slo, shi, olo, ohi;
+    DevBuf<uint8_t> dmask;
+    CutoffBufs b{};
+    long ntiles = 0, nsum = 0;
+    const int* count() const { return sums.p + nsum; }
+};
+void Engine::cutoff_launch(double g, const uint8_t* var_is_int, CutoffRun& r) {
+    const int nv = num_vars;
+    sync_view();
+    r.ntiles = cutoff_tiles(nv);
+    const size_t room = (size_t)r.ntiles * 256;
+    r.nsum = (r.ntiles + 4095) / 4096;
+    r.tcnt.ensure((size_t)r.ntiles, 0, st); r.toff.ensure((size_t)r.ntiles, 0, st); r.sums.ensure((size_t)r.nsum + 2, 0, st);
+    r.svar.ensure(room, 0, st); r.slo.ensure(room, 0, st); r.shi.ensure(room, 0, st);
+    r.ovar.ensure(room, 0, st); r.olo.ensure(room, 0, st); r.ohi.ensure(room, 0, st);
+    if (var_is_int) r.dmask.upload(std::vector<uint8_t>(var_is_int, var_is_int + nv), st);
+    CutoffBufs& b = r.b;
+    b.mask = var_is_int ? r.dmask.p : nullptr;
+    b.tcnt = r.tcnt.p; b.toff = r.toff.p; b.svar = r.svar.p; b.slo = r.slo.p; b.shi = r.shi.p; b.ovar = r.ovar.p; b.olo = r.olo.p; b.ohi = r.ohi.p;
+    b.nv = nv; b.g = g;
+    HIPCHECK(hipEventRecord(r.ev.e[0], st));
+    launch_cutoff_bounds(hview, b, r.sums.p, st);
+}
 // The read: nothing is written but private buffers; the reduced costs are the engine's own d on the device, the host reads back the
 // length of the list and then the list.
 void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint32_t>& vars, std::vector<double>& lo, std::vector<double>& hi,
@@ -4254,29 +4288,15 @@ void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint
     vars.clear(); lo.clear(); hi.clear();
     const int nv = num_vars;
     if (nv <= 0 || !(g < std::numeric_limits<double>::infinity())) return;  // g = +inf: nothing is tightened
-    sync_view();
-    const long ntiles = cutoff_tiles(nv);
-    const size_t room = (size_t)ntiles * 256;
-    const long nsum = (ntiles + 4095) / 4096;
-    DevBuf<int> tcnt, toff, sums;
-    DevBuf<uint32_t> svar, ovar;
-    DevBuf<double> slo, shi, olo, ohi;
-    DevBuf<uint8_t> dmask;
-    tcnt.ensure((size_t)ntiles, 0, st); toff.ensure((size_t)ntiles, 0, st); sums.ensure((size_t)nsum + 2, 0, st);
-    svar.ensure(room, 0, st); slo.ensure(room, 0, st); shi.ensure(room, 0, st);
-    ovar.ensure(room, 0, st); olo.ensure(room, 0, st); ohi.ensure(room, 0, st);
-    if (var_is_int) dmask.upload(std::vector<uint8_t>(var_is_int, var_is_int + nv), st);
-    CutoffBufs b{};
-    b.mask = var_is_int ? dmask.p : nullptr;
-    b.tcnt = tcnt.p; b.toff = toff.p; b.svar = svar.p; b.slo = slo.p; b.shi = shi.p; b.ovar = ovar.p; b.olo = olo.p; b.ohi = ohi.p;
-    b.nv = nv; b.g = g;
-    EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
-    launch_cutoff_bounds(hview, b, sums.p, st);
-    HIPCHECK(hipEventRecord(ev.e[1], st));
+    CutoffRun r;
+    cutoff_launch(g, var_is_int, r);
+    HIPCHECK(hipEventRecord(r.ev.e[1], st));
     HIPCHECK(hipGetLastError());
+    const long ntiles = r.ntiles;
+    const DevBuf<uint32_t>& ovar = r.ovar;
+    const DevBuf<double>&olo = r.olo, &ohi = r.ohi;
     int total = 0;
-    HIPCHECK(hipMemcpyAsync(&total, sums.p + nsum, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&total, r.count(), sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
     if (total < 0 || total > nv) throw MlpError(-3, "cutoff_bounds: the compaction returned an impossible count");
     vars.resize((size_t)total); lo.resize((size_t)total); hi.resize((size_t)total);
@@ -4291,7 +4311,36 @@ void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint
     // algorithmic bytes: per variable its location (4), and for a non-basic one its flags, reduced cost and bounds (25; the value of a
     // marked column and its mark: 9); per tile two counters written, read twice; per entry 20 bytes written, read, written and read back
     info.bytes = (var_is_int ? 38.0 : 29.0) * nv + 16.0 * (double)ntiles + 80.0 * total;
-    info.device_ms = ev.ms();
+    info.device_ms = r.ev.ms();
+}
+
+// The shift that fix_vars and set_var_bounds share: b.var / b.diff hold the moves of non-basic columns; r = A delta, ONE FTRAN through the
+// dense right-hand-side path of whichever representation of B^-1 is live, x_B -= B^-1 r.  Nothing is synchronised: w must outlive the
+// stream's work.  Returns the algorithmic bytes.
+struct Engine::ShiftBufs {
+    DevBuf<double> delta, X, Y, XK, YK, lrh;
+};
+double Engine::shift_basic_values(FixBufs& b, ShiftBufs& w) {
+    constexpr int R = RG_BATCH;
+    const DevView& dv = hview;
+    const Geom g = geom();
+    const int m = m_, k = fac_on_ ? 0 : k_;
+    ReqContext ctx(*this, std::vector<int>(1, 0), false);
+    const size_t blk = (size_t)m * R + R;
+    w.delta.ensure((size_t)N_ + 1, 0, st); w.X.ensure(blk, 0, st); w.Y.ensure(blk, 0, st);
+    if (!fac_on_ && k > 0) {
+        w.XK.ensure((size_t)k * R + R, 0, st); w.YK.ensure((size_t)k * R + R, 0, st); w.lrh.ensure((size_t)LR_MAX * R, 0, st);
+    }
+    TabBufs tb{};
+    static_cast<SolveBufs&>(tb) = ctx.sb;
+    tb.X = w.X.p; tb.Y = w.Y.p; tb.XK = w.XK.p; tb.YK = w.YK.p; tb.lrh = w.lrh.p;
+    b.delta = w.delta.p; b.X = w.X.p; b.Y = w.Y.p;
+    launch_fix_rhs(dv, b, N_, st);
+    launch_tab_solve(dv, g, tb, 0, 1, st);
+    launch_fix_apply(dv, b, st);
+    // the blocks X and Y, delta and the CSR pass, then the solve as tab_dense counts it
+    return 32.0 * (double)m * R + 8.0 * (double)N_ + 20.0 * (double)h_rcol.size() + 16.0 * m +
+           (fac_on_ ? (24.0 + 16.0 * ctx.J) * m : 8.0 * (double)k * k + 16.0 * ctx.J * k + 32.0 * (double)k * R + 20.0 * (double)h_rcol.size());
 }
 
 // The batched forms.  Checks first, nothing is changed before they pass.
@@ -4306,6 +4355,7 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
         if (sorted.front() < 0 || sorted.back() >= num_vars) throw MlpError(-1, "fix_vars: variable out of range");
         if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "fix_vars: a variable is listed twice");
     }
+    host_bounds();
     for (size_t i = 0; i < vars.size(); ++i)
         if (!(vals[i] >= h_lo[vars[i]] && vals[i] <= h_hi[vars[i]])) throw LpFail{1};
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
@@ -4323,7 +4373,6 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
     info.nonbasic = nb.size();
     bool moved = !basic.empty();
     if (!nb.empty()) {
-        constexpr int R = RG_BATCH;
         const size_t n = nb.size();
         std::vector<int> hcol(n), hvar(n);
         std::vector<double> hval(n);
@@ -4348,28 +4397,10 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
         HIPCHECK(hipStreamSynchronize(st));
         info.shifted = (uint64_t)shifted;
         info.bytes = 36.0 * (double)n;
-        DevBuf<double> delta, X, Y, XK, YK, lrh;
-        if (shifted && m_ > 0) {  // r = A delta, ONE FTRAN through the dense right-hand-side path, x_B -= B^-1 r
-            const DevView& dv = hview;
-            const Geom g = geom();
-            const int m = m_, k = fac_on_ ? 0 : k_;
-            ReqContext ctx(*this, std::vector<int>(1, 0), false);
-            const size_t blk = (size_t)m * R + R;
-            delta.ensure((size_t)N_ + 1, 0, st); X.ensure(blk, 0, st); Y.ensure(blk, 0, st);
-            if (!fac_on_ && k > 0) {
-                XK.ensure((size_t)k * R + R, 0, st); YK.ensure((size_t)k * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
-            }
-            TabBufs tb{};
-            static_cast<SolveBufs&>(tb) = ctx.sb;
-            tb.X = X.p; tb.Y = Y.p; tb.XK = XK.p; tb.YK = YK.p; tb.lrh = lrh.p;
-            b.delta = delta.p; b.X = X.p; b.Y = Y.p;
-            launch_fix_rhs(dv, b, N_, st);
-            launch_tab_solve(dv, g, tb, 0, 1, st);
-            launch_fix_apply(dv, b, st);
+        ShiftBufs w;
+        if (shifted && m_ > 0) {
+            info.bytes += shift_basic_values(b, w);
             info.solves = 1;
-            // the blocks X and Y, delta and the CSR pass, then the solve as tab_dense counts it
-            info.bytes += 32.0 * (double)m * R + 8.0 * (double)N_ + 20.0 * (double)h_rcol.size() + 16.0 * m +
-                          (fac_on_ ? (24.0 + 16.0 * ctx.J) * m : 8.0 * (double)k * k + 16.0 * ctx.J * k + 32.0 * (double)k * R + 20.0 * (double)h_rcol.size());
             moved = true;
         }
         launch_fix_commit(hview, b, shifted ? 1 : 0, st);
@@ -4440,5 +4471,146 @@ uint64_t Engine::unfix_vars(const std::vector<int>& vars, FixInfo& info) {
     stats.solve_wall_s += now_s() - t0;
     info.wall_ms = (now_s() - t0) * 1e3;
     return info.unfixed;
+}
+// ------------------------------------------------------------------ bounds (bounds.inc)
+void Engine::host_bounds() {
+    if (!bounds_mirror_stale_) return;
+    HIPCHECK(hipMemcpyAsync(h_lo.data(), d_lo.p, sizeof(double) * (size_t)num_vars, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(h_hi.data(), d_hi.p, sizeof(double) * (size_t)num_vars, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    bounds_mirror_stale_ = false;
+}
+void Engine::var_bounds(const uint32_t* vars, uint64_t n, double* lo, double* hi) {
+    host_bounds();
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t j = vars ? vars[i] : (uint32_t)i;
+        if (j >= (uint32_t)num_vars) throw MlpError(-1, "var_bounds: variable out of range");
+        lo[i] = h_lo[j];
+        hi[i] = h_hi[j];
+    }
+}
+
+// Checks first, nothing is changed before they pass (the classification writes private buffers only).
+void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<double>& lo, const std::vector<double>& hi, BoundsInfo& info) {
+    if (sharded()) throw MlpError(-1, "set_var_bounds is not available on a sharded solution");
+    if (!solved()) throw MlpError(-1, "set_var_bounds: model not solved (the re-solve is the dual one: it needs a dual-feasible basis)");
+    info = BoundsInfo();
+    info.requests = vars.size();
+    if (vars.empty()) return;
+    const size_t n = vars.size();
+    const double inf = std::numeric_limits<double>::infinity();
+    std::vector<size_t> ord(n);  // the requests in ascending variable number
+    for (size_t i = 0; i < n; ++i) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return vars[a] < vars[b]; });
+    if (vars[ord.front()] < 0 || vars[ord.back()] >= num_vars) throw MlpError(-1, "set_var_bounds: variable out of range");
+    for (size_t i = 1; i < n; ++i)
+        if (vars[ord[i]] == vars[ord[i - 1]]) throw MlpError(-1, "set_var_bounds: a variable is listed twice");
+    for (size_t i = 0; i < n; ++i)
+        if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] == inf || hi[i] == -inf)
+            throw MlpError(-1, "set_var_bounds: a bound is NaN, a lower bound +inf or an upper bound -inf");
+    bool any_fixed = false;
+    for (size_t i = 0; i < n; ++i) any_fixed = any_fixed || (h_var_loc[vars[i]] < 0 && h_nb_fixed[-1 - h_var_loc[vars[i]]]);
+    if (any_fixed) {
+        fetch_values();
+        for (size_t i = 0; i < n; ++i) {
+            const int loc = h_var_loc[vars[i]];
+            if (loc < 0 && h_nb_fixed[-1 - loc] && !(h_xN[-1 - loc] >= lo[i] && h_xN[-1 - loc] <= hi[i]))
+                throw MlpError(-1, "set_var_bounds: the value of a column fixed by fix_var lies outside the new bounds (unfix it first)");
+        }
+    }
+    for (size_t i = 0; i < n; ++i)
+        if (lo[i] > hi[i]) throw LpFail{1};
+    const double t0 = now_s();
+    const uint64_t it0 = stats.iterations;
+    host_bounds();
+    std::vector<int> hvar(n);
+    std::vector<double> hlo(n), hhi(n);
+    for (size_t i = 0; i < n; ++i) {
+        hvar[i] = vars[ord[i]];
+        hlo[i] = lo[ord[i]];
+        hhi[i] = hi[ord[i]];
+    }
+    // step 1: the classification
+    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    DevBuf<int> dvar, dcnt;
+    DevBuf<double> dlo, dhi, dtarget, ddiff;
+    DevBuf<uint8_t> dflags;
+    dvar.upload(hvar, st); dlo.upload(hlo, st); dhi.upload(hhi, st);
+    dtarget.ensure(n, 0, st); ddiff.ensure(n, 0, st); dflags.ensure(n, 0, st); dcnt.ensure(3, 0, st);
+    BoundBufs b{};
+    b.var = dvar.p; b.lo = dlo.p; b.hi = dhi.p; b.target = dtarget.p; b.diff = ddiff.p; b.flags = dflags.p; b.cnt = dcnt.p;
+    b.var_lo = d_lo.p; b.var_hi = d_hi.p; b.n = (long)n;
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
+    launch_bounds_classify(hview, b, st);
+    int cnt[3] = {0, 0, 0};
+    HIPCHECK(hipMemcpyAsync(cnt, dcnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (cnt[2])
+        throw MlpError(-1, "set_var_bounds: " + std::to_string(cnt[2]) + " request(s) make infinite the bound a non-basic column sits at; the "
+                           "column would have to change sides, which the dual re-solve cannot serve");
+    const int shifted = cnt[0];
+    info.shifted = (uint64_t)shifted;
+    info.basic = (uint64_t)cnt[1];
+    info.nonbasic = n - info.basic;
+    info.bytes = 58.0 * (double)n;  // per request: variable, location, bounds, flags, value, reduced cost read; target, diff, flags written
+    // from here on the state changes
+    cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
+    // step 2: the shift (r = A delta, ONE FTRAN through the dense right-hand-side path, x_B -= B^-1 r) and the commit
+    ShiftBufs w;
+    if (shifted && m_ > 0) {
+        FixBufs fb{};
+        fb.var = dvar.p; fb.diff = ddiff.p; fb.n = (long)n;
+        info.bytes += shift_basic_values(fb, w);
+        info.solves = 1;
+    }
+    launch_bounds_commit(hview, b, shifted ? 1 : 0, st);
+    HIPCHECK(hipEventRecord(ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    info.device_ms = ev.ms();
+    info.bytes += 41.0 * (double)n;
+    for (size_t i = 0; i < n; ++i) {
+        h_lo[hvar[i]] = hlo[i];
+        h_hi[hvar[i]] = hhi[i];
+    }
+    if (shifted) values_dirty = true;
+    // step 3: ONE dual re-solve after a shift, or when a basic value now violates its bounds
+    budget_exhausted = false;
+    if (shifted || (cnt[1] && !basic_values_feasible())) {
+        ensure_beta();  // (only in front of a re-solve: a call that moves nothing leaves every bit of the state)
+        primal_feasible = false;
+        restore_feasibility();
+    }
+    info.pivots = stats.iterations - it0;
+    stats.solve_wall_s += now_s() - t0;
+    info.wall_ms = (now_s() - t0) * 1e3;
+}
+
+uint64_t Engine::tighten_by_reduced_cost(double g, const uint8_t* var_is_int, BoundsInfo& info) {
+    if (sharded()) throw MlpError(-1, "tighten_by_reduced_cost is not available on a sharded solution");
+    if (!solved()) throw MlpError(-1, "tighten_by_reduced_cost: model not solved (the bound is a weak-duality argument: it needs a dual-feasible basis)");
+    info = BoundsInfo();
+    const int nv = num_vars;
+    if (nv <= 0 || !(g < std::numeric_limits<double>::infinity())) return 0;  // g = +inf: nothing is tightened
+    const double t0 = now_s();
+    CutoffRun r;
+    cutoff_launch(g, var_is_int, r);
+    launch_bounds_apply_list(hview, r.b, r.count(), d_lo.p, d_hi.p, st);
+    HIPCHECK(hipEventRecord(r.ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    int total = 0;
+    HIPCHECK(hipMemcpyAsync(&total, r.count(), sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    if (total < 0 || total > nv) throw MlpError(-3, "tighten_by_reduced_cost: the compaction returned an impossible count");
+    if (total) bounds_mirror_stale_ = true;
+    cold_start_ = false;
+    info.requests = info.nonbasic = info.tightened = (uint64_t)total;
+    // the read as cutoff_bounds counts it without the trip to the host (60 per entry), then per entry 20 bytes read, 16 written, 4 of location
+    info.bytes = (var_is_int ? 38.0 : 29.0) * nv + 16.0 * (double)r.ntiles + 100.0 * total;
+    info.device_ms = r.ev.ms();
+    info.wall_ms = (now_s() - t0) * 1e3;
+    return (uint64_t)total;
 }
 }  // namespace mlp

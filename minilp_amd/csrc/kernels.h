@@ -649,6 +649,24 @@ void launch_fix_rhs(const DevView& dv, const FixBufs& b, int N, hipStream_t st);
 void launch_fix_apply(const DevView& dv, const FixBufs& b, hipStream_t st);           // x_B -= Y (after it)
 void launch_fix_commit(const DevView& dv, const FixBufs& b, int shifted, hipStream_t st);  // objective (if shifted), xN, flags
 void launch_fix_release(const DevView& dv, const FixBufs& b, hipStream_t st);         // flags from the value against the bounds
+// new bounds for structural variables (bounds.inc): the requests in ascending variable number; the shift itself runs through
+// launch_fix_rhs / launch_tab_solve / launch_fix_apply with a FixBufs on (var, diff)
+struct BoundBufs {
+    const int* var;     // n: variable of a request
+    const double* lo;   // n: its new bounds
+    const double* hi;
+    double* target;     // n: value of a non-basic request after the call
+    double* diff;       // n: target - xN (0: basic, fixed by fix_var, or already there)
+    uint8_t* flags;     // n: flags of a non-basic request after the call
+    int* cnt;           // 3: requests with diff != 0, basic requests, requests whose side has an infinite new bound
+    double* var_lo;     // N: the bounds by variable (DevView holds them read-only)
+    double* var_hi;
+    long n;
+};
+void launch_bounds_classify(const DevView& dv, const BoundBufs& b, hipStream_t st);             // target, diff, flags, cnt
+void launch_bounds_commit(const DevView& dv, const BoundBufs& b, int shifted, hipStream_t st);  // objective (if shifted), xN, flags, bounds
+// the list of launch_cutoff_bounds written to the bounds; count: its length on the device (sums[ceil(cutoff_tiles(nv) / 4096)])
+void launch_bounds_apply_list(const DevView& dv, const CutoffBufs& c, const int* count, double* var_lo, double* var_hi, hipStream_t st);
 // Sparse rows out of a dense block, one batch of at most RG_BATCH basic positions (tableau.inc, cuts.inc, gmi.inc).  Phase 1,
 // launch_rows_generate: the rows of B^-1 (b.blk, b.req, the SolveBufs part as for ranging), one pass over A that leaves the dense block
 // dense[N][RG_BATCH] by variable, the scanned offsets off[RG_BATCH * cut_segments(N)] (cnt: same size, sums: the scan's scratch), the row

@@ -5648,6 +5648,7 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
 #include "gmi.inc"  // a round of Gomory mixed-integer cuts: the pass of the Gomory round with the per-column classification at its end (side-effect free)
 #include "tableau.inc" // reading the tableau: 16 rows of B^-1 A as sparse rows, 16 solves with dense right-hand sides per pass over W0 (side-effect free)
 #include "fixing.inc"  // reduced-cost bounds from a cutoff (one classifying pass, deterministic compaction; side-effect free) and the kernels of fix_vars / unfix_vars
+#include "bounds.inc"  // new bounds for structural variables: classification, commit, and the device-to-device list of the reduced-cost bounds
 
 void launch_gauss_jordan(double* Kd, double* Winv, int k, int ld, int* d_flag, double* d_scratch, hipStream_t st) {
     if (k <= 0) return;
