@@ -158,6 +158,7 @@ struct IterPlan {
     FtranEntry ftran;
     int ftran_ys, ftran_fpk;        // gather: + y_S by row (t_K ride) | no blocked push, the product is pulled in the ratio test's launch
     int tk_ride, rk_inside;         // launch_ratio_primal
+    int v_ride;                     // ... its riders also form the v partials; the BASIS stage is launch_eta_vtail alone (MediumRide only)
     int btran, btran_rhs;           // a BTRAN launch exists | its with_rhs
     int sb_tk_inside;               // launch_small_basis
     int post_touch, post_rk_ride;   // launch_post_fused

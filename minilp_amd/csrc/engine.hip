@@ -1493,6 +1493,9 @@ IterPlan Engine::plan_iteration(int phase) const {
     pl.btran_rhs = (phase == 0 && !tkr && !fpl) ? pse : 0;  // tK = alpha_K - F^T y_S in the BTRAN launch (unless it rode in the ratio launch)
     pl.sb_tk_inside = tkr_s ? 0 : 1;
     pl.post_touch = (g.str && phase == 0) ? 1 : 0, pl.post_rk_ride = rkr ? 1 : 0;
+    // ... and the v partials of the pass over W ride in the ratio launch as well: the BASIS stage is ONE launch, the v tail beside the eta update
+    // (not where the v tail's launch also lists the touched columns of the sparse tableau row).  MLP_V_RIDE=0: the two launches.
+    pl.v_ride = (btr && !pl.post_touch && v_rides_ratio(dv, g)) ? 1 : 0;
     pl.basis_lists_touched = (phead || smallb || post_fused_lists_touched(dv, g, pse, 0, pl.post_touch)) ? 1 : 0;  // (head | k_small_basis | v tail)
     // small-nucleus primal head: the update kernel's workgroups pull the touched columns of their own positions (1), and the head also applies the
     // basic side of the pivot and position q (2)
@@ -1554,7 +1557,7 @@ void Engine::launch_stage(const IterPlan& pl, int stage, bool with_events) {
             // pull of -F alpha_K (+ y_S) with K5 p1 | K5 p2 (+ K3 head + plan) | t_K; sampled iteration: the FTRAN bracket closes behind the
             // first of the two launches, which completes alpha_q
             launch_fpull_ratio(dv, g, st, with_events ? ev[7] : nullptr);
-        } else if (phase == 0) launch_ratio_primal(dv, g, pse, st, pl.tk_ride, pl.rk_inside);  // K5 p1 (+ ||alpha||^2, y_S), p2 (+ K3 head + plan) [| t_K]
+        } else if (phase == 0) launch_ratio_primal(dv, g, pse, st, pl.tk_ride, pl.rk_inside, pl.v_ride);  // K5 p1 (+ ||alpha||^2, y_S), p2 (+ K3 head + plan) [| t_K [+ v partials]]
         else launch_ratio_dual(dv, g, st, pl.row_lists);  // K7 p1, p2 (+ K2 head); over the listed non-zeros of alpha_r when the tableau row listed them
         break;                                            // (compact factor: its finaliser scatters the entering column for the FTRAN)
     case STAGE_BTRAN:
@@ -1580,6 +1583,12 @@ void Engine::launch_stage(const IterPlan& pl, int stage, bool with_events) {
         if (pl.form == IterForm::SmallBasis) {
             time_slot(2, 2);  // (sampled iteration: the slot of the pass over the nucleus inverse)
             launch_small_basis(dv, g, st, pl.sb_tk_inside);
+            time_slot(2, -1);
+            break;
+        }
+        if (pl.v_ride) {  // the v partials rode in the ratio launch: v tail | eta update of W
+            time_slot(2, 2);
+            launch_eta_vtail(dv, g, st);
             time_slot(2, -1);
             break;
         }
@@ -3685,6 +3694,9 @@ uint64_t Engine::state(const char* what, double* out, uint64_t cap) {
     } else if (w == "btran_ride") {  // medium nucleus without a BTRAN launch: [would be in effect at this size, iterations whose rho_K the ratio test's final block formed]
         pull_ctl();
         tmp = {(double)(btran_rides_ratio(hview, geom()) ? 1 : 0), (double)h_ctl->rk_rides};
+    } else if (w == "v_ride") {  // ... whose v partials rode in the ratio launch too: [would be in effect at this size, iterations whose v tail ran beside the eta update]
+        pull_ctl();
+        tmp = {(double)(v_rides_ratio(hview, geom()) ? 1 : 0), (double)h_ctl->v_rides};
     } else if (w == "golive_checks") {  // fingerprint comparisons passed at the go-live point of the deferred sharding
         tmp = {(double)golive_checks_};
     } else if (w == "shard_live") {

@@ -128,6 +128,7 @@ struct Ctl {
     int rk_rides;      // lazy primal iterations whose rho_K was formed by the ratio test's final block: no BTRAN launch (state("btran_ride")[1])
     int rl_decisions;  // primal Harris tests decided by the list form (one grid pass; state("ratio_list")[1])
     int rl_overflows;  // ... of which a block's list did not fit and the final block re-scanned every position (state("ratio_list")[2])
+    int v_rides;       // lazy primal iterations whose v partials rode in the ratio launch: v tail and eta update in one launch (state("v_ride")[1])
 };
 
 // Sharded pricing: one 64-byte mailbox record per (kind, parity, rank) in host
@@ -466,9 +467,11 @@ void launch_fpull_ratio(const DevView& dv, const Geom& g, hipStream_t st, hipEve
 void launch_fpk_build(const DevView& dv, hipStream_t st);   // the packed copy from the CSR of A and the current maps (fpk_in cleared beforehand)
 void launch_btran_fused(const DevView& dv, const Geom& g, int with_rhs, int derive_dual, hipStream_t st);  // BTRAN head + gather (dual iteration)
 constexpr int HEAD_LIST_CAP = 1024;  // entries an in-kernel stage head can hold (longest column / row of A)
-void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride = 0, int rk_inside = 0);  // K5 p1 (+alpha_sq, y_S), p2 (+BTRAN head, plan) [| t_K blocks]
+void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride = 0, int rk_inside = 0, int v_ride = 0);  // K5 p1 (+alpha_sq, y_S), p2 (+BTRAN head, plan) [| t_K blocks | t_K + v partials]
 bool tk_rides_ratio(const DevView& dv, const Geom& g);
 bool btran_rides_ratio(const DevView& dv, const Geom& g);  // medium nucleus: t_K rides in the ratio launch and its final block forms rho_K (no BTRAN launch)
+bool v_rides_ratio(const DevView& dv, const Geom& g);      // ... and the v partials of the pass over W ride there too (launch_eta_vtail is then the BASIS stage)
+void launch_eta_vtail(const DevView& dv, const Geom& g, hipStream_t st);  // v tail | eta update of W, one launch (the v partials rode in the ratio launch)
 int ratio_list_cap(const DevView& dv, const Geom& g);   // list form of the grid test: entries per block, -1 when the publish-wait form runs
 int ratio_primal_form(const DevView& dv, const Geom& g);  // 0 one block, 1 fused grid (one launch), 2 two launches with stride loops
 bool tk_rides_ratio_small(const DevView& dv, const Geom& g);  // the same for a small nucleus (k_small_basis), y_S formed on the fly  // large nucleus, lazy primal iteration: t_K is formed by blocks riding behind the ratio blocks

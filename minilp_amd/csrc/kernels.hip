@@ -1732,12 +1732,90 @@ __device__ __forceinline__ void tk_ride_body(const DevView& v, const Ctl* c, int
     acc = group_sum<G>(acc);
     if (gl == 0) v.tK[slot] = v.alpha_q[p] - acc;
 }
+// Medium nucleus (launch_ratio_primal, v_ride): v_K = W^T t_K needs neither the leaving row nor rho — W is the inverse from BEFORE this
+// pivot, t_K needs alpha_q only — so the v half of the pass over W rides behind the ratio blocks too.  One rider block per tile of
+// k_fused_w<8> (8 rows x FW_TC columns of the capacity-sized tiling, stripes fastest): it forms t_K of its eight slots with
+// tk_ride_body<G, true>'s sums (G lanes per slot, lane-strided, group_sum; every chunk's block forms them again — a few hundred entries —
+// and the chunk-0 block stores them), keeps them in LDS and accumulates the tile's v partials as k_fused_w<8, false, true, true> does:
+// the same columns per thread, rows ascending, rows past k skipped; W is only read, v.part_v is stored last.  Riders wait for nobody and take no ticket; an iteration that turns out a flip or unbounded leaves only
+// scratch (tK, part_v) behind.
+template <int G>
+__device__ __forceinline__ void v_ride_body(const DevView& v, const Ctl* c, int block, int nstripes) {
+    const int k = c->k, ld = v.ld;
+    const int stripe = block % nstripes, chunk = block / nstripes;
+    const int row0 = stripe * 8, col0 = chunk * FW_TC;
+    if (row0 >= k || col0 >= k) return;  // (the grid is sized by the capacity)
+    __shared__ double s_t[8];
+    const int tid = threadIdx.x;
+    int cidx[4];
+    cidx[0] = col0 + 2 * tid;
+    cidx[1] = cidx[0] + 1;
+    cidx[2] = col0 + 512 + 2 * tid;
+    cidx[3] = cidx[2] + 1;
+    const bool pair0 = cidx[1] < k, pair1 = cidx[3] < k;
+    const bool one0 = cidx[0] < k, one1 = cidx[2] < k;
+    // (a row or a column past k reads a clamped address and is masked: ld is even and the pad past an odd k is allocated)
+    const int c0 = one0 ? cidx[0] : col0, c2 = one1 ? cidx[2] : col0;
+    // The loads of rows 0-3 go out ahead of the t_K sums (their chain of dependent loads runs beside them), those of rows 4-7 behind them:
+    // with all eight in front the kernel needs 148 VGPRs instead of 126 (3 waves per SIMD instead of the 4 its co-residency bound was
+    // measured with), with all eight behind the riders run longer (HISTORY.md §4).  Each half is one group of loads.
+    double2 wa[8], wb[8];
+    const auto load_rows = [&](int a0) {
+#pragma unroll
+        for (int a = a0; a < a0 + 4; ++a) {
+            const int row = row0 + a;
+            const double* wp = v.W + (size_t)(row < k ? row : k - 1) * ld;
+            wa[a] = *reinterpret_cast<const double2*>(wp + c0);
+            wb[a] = *reinterpret_cast<const double2*>(wp + c2);
+        }
+    };
+    load_rows(0);
+    constexpr int SPR = BLK / G;  // slots per round: 64 lanes take two rounds of four
+    const int gl = tid & (G - 1);
+#pragma unroll
+    for (int s0 = 0; s0 < 8; s0 += SPR) {
+        const int ls = s0 + tid / G, slot = row0 + ls;
+        if (ls >= 8 || slot >= k) continue;
+        const int p = v.pos_of_kslot[slot];
+        const int var = v.basic_vars[p];
+        const int end = v.csc_ptr[var + 1];
+        double acc = 0.0;
+        for (int e = v.csc_ptr[var] + gl; e < end; e += G) {
+            const RowInfo ri = v.rowinfo[v.csc_row[e]];
+            const double a = ri.kslot < 0 ? v.alpha_q[ri.pos] : 0.0;
+            const double y = a != 0.0 ? a / ri.diag : 0.0;
+            acc += v.csc_val[e] * y;
+        }
+        acc = group_sum<G>(acc);
+        if (gl == 0) {
+            const double t = v.alpha_q[p] - acc;
+            s_t[ls] = t;
+            if (chunk == 0) v.tK[slot] = t;
+        }
+    }
+    load_rows(4);
+    __syncthreads();
+    double vacc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < 8; ++a) {
+        if (row0 + a >= k) continue;
+        const double t = s_t[a];
+        const double w[4] = {one0 ? wa[a].x : 0.0, pair0 ? wa[a].y : 0.0, one1 ? wb[a].x : 0.0, pair1 ? wb[a].y : 0.0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) vacc[j] += w[j] * t;
+    }
+    double* pv = v.part_v + (size_t)stripe * ld;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (cidx[j] < k) pv[cidx[j]] = vacc[j];
+}
 // n_ratio > 0 (large nucleus, lazy primal iteration; launch_ratio_primal): only the first n_ratio blocks run the ratio test; the
 // blocks behind them form t_K, which needs alpha_q and y_S but not the leaving row — the combine of the blocked F push has left
 // y_S by row (its ys form: the quotient the ratio test would write, use_pse = 2 tells pass 1 not to), so the 2 M-entry pull that
 // made k_btran a 23 us kernel runs in the shadow of the ratio test's two grid-wide hand-offs.  The ratio blocks come first in
 // dispatch order and wait only for each other: the co-residency argument of the in-kernel wait is unchanged.
-__global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_pse, int n_ratio = 0, int tk_lanes = 0, int tk_onfly = 0, int rl_cap = -1, int rk_inside = 0) {
+__global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_pse, int n_ratio = 0, int tk_lanes = 0, int tk_onfly = 0, int rl_cap = -1, int rk_inside = 0,
+                                                            int v_ride = 0) {
     Ctl* c = v.ctl;
     const int nrb = n_ratio > 0 ? n_ratio : (int)gridDim.x;
     // Grid form: the inputs of the thread's PT positions depend on nothing but the block index, so their loads are issued BEFORE the
@@ -1765,6 +1843,12 @@ __global__ void __launch_bounds__(BLK) k_ratio_primal_fused(DevView v, int use_p
     if (c->halt || c->it.status != ITER_PIVOT) return;
     if ((int)blockIdx.x >= nrb) {
         const int tb = (int)blockIdx.x - nrb;
+        if (v_ride > 0) {  // medium nucleus: t_K and the v partials of the pass over W (v_ride: stripes of the capacity-sized tiling)
+            if (tk_lanes <= 4) v_ride_body<4>(v, c, tb, v_ride);
+            else if (tk_lanes <= 16) v_ride_body<16>(v, c, tb, v_ride);
+            else v_ride_body<64>(v, c, tb, v_ride);
+            return;
+        }
         if (tk_onfly) {  // (small nucleus: k_small_basis then carries no t_K blocks and waits for none)
             if (tk_lanes <= 4) tk_ride_body<4, true>(v, c, tb);
             else if (tk_lanes <= 16) tk_ride_body<16, true>(v, c, tb);
@@ -3341,13 +3425,24 @@ __device__ __forceinline__ void fw_store2(double* p, double a, double b) {
 // g_j = V[j].rho_K, h_j = U[j].t_K that k_post_fused adds to the two products.
 // TILED: 1-D grid; the tile blocks stride over the (stripe, chunk) tiles of the CURRENT k, so neither a
 // pass nor an early exit pays for dispatching the cap-sized grid (16 384 blocks at cap 16 384: ~20 us).
-template <int TR, bool WITH_TAU, bool WITH_V, bool DO_UPDATE, bool NT = false, bool LR = false, int RL = 1, bool TILED = false>
+// VT (medium nucleus whose v partials rode in the ratio launch, v_ride_body; untiled eta-only pass): the grid has one block row MORE, in
+// FRONT of the chunk rows (first in dispatch order), whose first blocks_for(cap, 32) blocks are the v tail (v_tail_body) — it reads the
+// partials and scatters v by row, the eta update reads and writes W: the two share nothing, and k_post_fused is not launched.
+template <int TR, int TC>
+__device__ __forceinline__ void v_tail_body(const DevView& v, const Ctl* c, int b, int k, int fold_fused, bool xsh, const double* xb);  // (below)
+template <int TR, bool WITH_TAU, bool WITH_V, bool DO_UPDATE, bool NT = false, bool LR = false, int RL = 1, bool TILED = false, bool VT = false>
 __global__ void __launch_bounds__(BLK) k_fused_w(DevView v) {
+    static_assert(!VT || (TR == 8 && !WITH_TAU && !WITH_V && DO_UPDATE && !LR && !TILED), "the v tail rides with the eta-only pass of 8-row tiles");
     Ctl* c = v.ctl;
     if (c->halt || c->it.status != ITER_PIVOT) return;
     KMARK0(c, 8);
     if (LR && c->fold) return;
     const int k = c->k, ld = v.ld;
+    if (VT && blockIdx.y == 0) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&c->v_rides, 1);
+        v_tail_body<TR, FW_TC>(v, c, (int)blockIdx.x, k, 0, false, nullptr);  // (blocks past k / 32 leave at once)
+        return;
+    }
     const int n_tile_blocks = TILED ? (int)gridDim.x - (LR ? LR_MAX : 0) : 0;
     if (LR && (TILED ? (int)blockIdx.x >= n_tile_blocks : blockIdx.y == gridDim.y - 1)) {
         const int j = TILED ? (int)blockIdx.x - n_tile_blocks : (int)blockIdx.x;
@@ -3375,7 +3470,7 @@ __global__ void __launch_bounds__(BLK) k_fused_w(DevView v) {
     const int ntiles = TILED ? ((k + TR * RL - 1) / (TR * RL)) * nchunks_k : 1;
     for (int tile = TILED ? (int)blockIdx.x : 0; tile < ntiles; tile += TILED ? n_tile_blocks : 1) {
     const int stripe = TILED ? tile / nchunks_k : (int)blockIdx.x;
-    const int chunk = TILED ? tile % nchunks_k : (int)blockIdx.y;
+    const int chunk = TILED ? tile % nchunks_k : (int)blockIdx.y - (VT ? 1 : 0);
     const int row0 = stripe * (TR * RL);
     const int col0 = chunk * FW_TC;
     if (row0 >= k || col0 >= k) return;  // untiled grids are sized by the capacity
@@ -4033,8 +4128,14 @@ __global__ void __launch_bounds__(BLK) k_post_fused(DevView v, int n_push, int t
         return;
     }
     if (!WITH_V) return;
+    v_tail_body<TR, TC>(v, c, (int)blockIdx.x - n_push, k, fold_fused, xsh, xb);
+}
+// The v tail of the pass over W — block b of blocks_for(cap, 32): v_K = the sum of the per-stripe partials in a fixed order, scattered by
+// row (solver.rs:1114).  Of k_post_fused, and of the eta-update launch of the medium nucleus whose v partials rode in the ratio launch
+// (k_fused_w, VT).
+template <int TR, int TC>
+__device__ __forceinline__ void v_tail_body(const DevView& v, const Ctl* c, int b, int k, int fold_fused, bool xsh, const double* xb) {
     // 32 slots x 8 stripe groups per block; LDS combines the 8 partial sums in a fixed order
-    const int b = (int)blockIdx.x - n_push;
     const int lane32 = threadIdx.x & 31, grp = threadIdx.x >> 5;
     const int i = b * 32 + lane32;
     if (b * 32 >= k) return;
@@ -5216,10 +5317,23 @@ bool btran_rides_ratio(const DevView& dv, const Geom& g) {
     if (e && e[0] == '0') return false;
     return g.head_fused && !g.big && !g.fac && !dv.lrJ && g.cap <= 4096 && tk_rides_ratio_small(dv, g);
 }
-void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride, int rk_inside) {
+// ... and the v partials of the pass over W ride there as well (v_ride_body): the BASIS stage is one launch, the v tail beside the eta update
+// (launch_eta_vtail).  The 8-row tiles of the plain pass only.  MLP_V_RIDE=0: k_fused_w<8> with the v partials + k_post_fused.
+bool v_rides_ratio(const DevView& dv, const Geom& g) {
+    const char* e = std::getenv("MLP_V_RIDE");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
+    if (e && e[0] == '0') return false;
+    return btran_rides_ratio(dv, g) && fw_rows(g) == 8;
+}
+void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride, int rk_inside, int v_ride) {
     if (tk_ride) {  // (the caller asked tk_rides_ratio / tk_rides_ratio_small first); 2: small nucleus, y_S on the fly
         const int nb = grid_for(g.m);
         const int lanes = g.lanes <= 4 ? 4 : (g.lanes <= 16 ? 16 : 64);
+        if (v_ride) {  // (the caller asked v_rides_ratio): one rider per tile of k_fused_w<8>'s capacity-sized grid, behind the ratio blocks
+            const int nstripes = (g.cap + 8 - 1) / 8, nchunks = (g.cap + FW_TC - 1) / FW_TC;
+            hipLaunchKernelGGL(k_ratio_primal_fused, dim3(nb + nstripes * nchunks), dim3(BLK), 0, st, dv, use_pse, nb, lanes, 1, ratio_list_cap(dv, g), rk_inside,
+                               nstripes);
+            return;
+        }
         hipLaunchKernelGGL(k_ratio_primal_fused, dim3(nb + blocks_for((long)g.cap * lanes)), dim3(BLK), 0, st, dv, tk_ride == 2 ? use_pse : 2, nb, lanes,
                            tk_ride == 2 ? 1 : 0, ratio_list_cap(dv, g), rk_inside);
         return;
@@ -5450,6 +5564,13 @@ void launch_fused_w(const DevView& dv, const Geom& g, int with_v, hipStream_t st
         else if (with_tau) LAUNCH_T(2, (k_fused_w<16, true, false, true, true, false, 1, true>), dim3(nb), b, 0, st, dv);
         else LAUNCH_T(2, (k_fused_w<16, false, false, true, true, false, 1, true>), dim3(nb), b, 0, st, dv);
     }
+}
+// Medium nucleus whose v partials rode in the ratio launch (v_rides_ratio): the eta-only pass of 8-row tiles with one block row in front of
+// it for the v tail (k_fused_w, VT) — what launch_fused_w + launch_post_fused do in two launches
+void launch_eta_vtail(const DevView& dv, const Geom& g, hipStream_t st) {
+    if (g.cap <= 0) return;
+    const int nstripes = (g.cap + 8 - 1) / 8, nchunks = (g.cap + FW_TC - 1) / FW_TC;  // (nstripes >= blocks_for(cap, 32): the tail fits its row)
+    LAUNCH_T(2, (k_fused_w<8, false, false, true, false, false, 1, false, true>), dim3(nstripes, nchunks + 1), dim3(BLK), 0, st, dv);
 }
 bool rk_rides_post(const DevView& dv, const Geom& g) {
     const char* e = std::getenv("MLP_RK_RIDE");
