@@ -30,7 +30,8 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False, cutoff=None, tighten=False):
+def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False, cutoff=None, tighten=False,
+        propagate=False):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -115,6 +116,16 @@ def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0,
             print("%-12s %14s %14s   %s" % ("variable", "lower", "upper", ""))
             for v, a, b in zip(cv, clo, chi):
                 print("%-12s %14.8g %14.8g   %s" % (names[int(v)], a, b, "fixed" if a == b else ""))
+    if propagate:  # the bounds that the rows imply (no variable is taken as integer), applied to the solution
+        try:
+            sol, count, infeasible = sol.tighten_by_propagation()
+        except B.Infeasible:
+            print("propagation: the tightened model is infeasible")
+            return 1
+        if infeasible:
+            print("propagation: the rows prove the model infeasible, %s" % sol.propagate_info())
+            return 1
+        print("propagation: %d variables tightened, objective %.12g, %s %s" % (count, sol.objective(), sol.propagate_info(), sol.bounds_info()))
     for k in range(gomory_rounds):
         x = sol.values()
         vs, _ = sol.basis_status()
@@ -173,10 +184,12 @@ def main():
                     help="print the bounds the reduced costs imply for an incumbent of objective VALUE (Solution.cutoff_bounds)")
     ap.add_argument("--tighten", action="store_true",
                     help="with --cutoff: apply the listed bounds to the solution (Solution.tighten_by_reduced_cost)")
+    ap.add_argument("--propagate", action="store_true",
+                    help="tighten the bounds by propagation over the rows (Solution.tighten_by_propagation) and print the count and the counters")
     a = ap.parse_args()
     import minilp_amd as B
     return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau, a.gmi_rounds, [nm for nm in a.continuous.split(",") if nm],
-               a.branch_penalties, a.cutoff, a.tighten)
+               a.branch_penalties, a.cutoff, a.tighten, a.propagate)
 
 
 if __name__ == "__main__":

@@ -88,7 +88,7 @@ def stoer_wagner_py(w):
 
 
 class TspSolver:
-    def __init__(self, backend, pts, log=None, batch_cuts=False, branching="fractional", rc_fixing=False):
+    def __init__(self, backend, pts, log=None, batch_cuts=False, branching="fractional", rc_fixing=False, propagate=False):
         self.B = backend
         assert branching in ("fractional", "penalties")
         self.branching = branching  # "penalties": Solution.branch_penalties chooses the variable and prunes sides (needs a back end that has it)
@@ -104,6 +104,9 @@ class TspSolver:
         self.rc_fixing = rc_fixing  # reduced-cost fixing at every node once a tour is known (needs a back end that has it)
         if rc_fixing:
             self.stats.update(rc_calls=0, rc_fixed=0)
+        self.propagate = propagate  # bound propagation after the fixings of every node (needs a back end that has it)
+        if propagate:
+            self.stats.update(prop_calls=0, prop_tightened=0, prop_pruned=0)
         n = self.n
         self.edge_var = -np.ones((n, n), dtype=np.int64)
         p = backend.Problem(backend.MINIMIZE)
@@ -243,6 +246,25 @@ class TspSolver:
                 cur, fixed = cur.fix_by_reduced_cost(best_cost, integer_vars=np.ones(self.n * (self.n - 1) // 2, dtype=bool))
                 self.stats["rc_calls"] += 1
                 self.stats["rc_fixed"] += len(fixed)
+            if self.propagate:  # what the degree rows and the cuts imply once edges are fixed; every edge variable is integer
+                try:
+                    cur, count, infeasible = cur.tighten_by_propagation(integer_vars=np.ones(self.n * (self.n - 1) // 2, dtype=bool))
+                except self.B.Infeasible:
+                    infeasible, count = True, 0
+                self.stats["prop_calls"] += 1
+                self.stats["prop_tightened"] += count
+                if infeasible:
+                    self.stats["prop_pruned"] += 1
+                    continue
+                if count:
+                    self.stats["lp_solves"] += 1
+                    try:
+                        cur = self.add_subtour_constraints(cur)
+                    except self.B.Infeasible:
+                        continue
+                    obj = cur.objective()
+                    if obj > best_cost:
+                        continue
             pick = self.choose_branch(cur)
             if pick is not None:
                 stack.append(dict(start=cur, var=pick[0], pen=pick[1], start_val=0 if cur[pick[0]] < 0.5 else 1, cur=None))
@@ -317,6 +339,8 @@ def main():
                     help="penalties: choose the branching variable by Solution.branch_penalties and skip sides its bounds rule out")
     ap.add_argument("--rc-fixing", action="store_true",
                     help="fix edge variables by their reduced costs (Solution.fix_by_reduced_cost) after every node LP once a tour is known")
+    ap.add_argument("--propagate", action="store_true",
+                    help="tighten the bounds by propagation over the rows (Solution.tighten_by_propagation) after the fixings of every node")
     a = ap.parse_args()
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -324,7 +348,7 @@ def main():
     name, pts = read_tsplib(a.file, a.nodes)
     t0 = time.time()
     s = TspSolver(backend, pts, log=lambda m: print("[%.1fs] %s" % (time.time() - t0, m), flush=True), batch_cuts=a.batch_cuts, branching=a.branching,
-                  rc_fixing=a.rc_fixing)
+                  rc_fixing=a.rc_fixing, propagate=a.propagate)
     cost, tour = s.solve(a.max_bb_nodes)
     print("problem %s (%d cities): tour cost %.10f, %s, %.1fs" % (name, len(pts), cost, s.stats, time.time() - t0))
     print("tour:", " ".join(str(int(t) + 1) for t in tour))  # Tour::to_string (tsp.rs:161-167): 1-based city numbers

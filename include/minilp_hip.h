@@ -53,6 +53,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * mlp_solution_unfix_vars, mlp_fix_info with its own mlp_fix_info_size()) are additive in the same way. */
 /* Still version 5: the bound changes (mlp_solution_set_var_bounds, mlp_solution_tighten_by_reduced_cost, mlp_solution_var_bounds,
  * mlp_bounds_info with its own mlp_bounds_info_size()) are additive in the same way. */
+/* Still version 5: the bound propagation (mlp_solution_propagate_bounds, mlp_solution_tighten_by_propagation, mlp_propagate_info with
+ * its own mlp_propagate_info_size()) is additive in the same way. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -596,7 +598,7 @@ typedef struct mlp_bounds_info {
     uint64_t nonbasic;   /* of them non-basic */
     uint64_t shifted;    /* ... of them whose value moved with its bound */
     uint64_t solves;     /* FTRANs of the shift, 0 or 1 */
-    uint64_t tightened;  /* tighten_by_reduced_cost: entries applied */
+    uint64_t tightened;  /* tighten_by_reduced_cost, tighten_by_propagation: entries applied */
     uint64_t pivots;     /* iterations of the dual re-solve */
     double bytes;        /* algorithmic bytes of the device work (without the re-solve) */
     double device_ms;    /* its time on the device (HIP events around the launches) */
@@ -604,6 +606,61 @@ typedef struct mlp_bounds_info {
 } mlp_bounds_info;
 int mlp_solution_bounds_info(const mlp_solution* s, mlp_bounds_info* out);
 uint64_t mlp_bounds_info_size(void);
+
+/* ---- Bound propagation from row activities (node presolve) --------------------------------------------------------------------------------
+ * mlp_solution_propagate_bounds lists the bounds that the rows of the model imply on its structural variables, given the bounds and
+ *   the fixings it holds now.  The work is done on the device: two streaming passes over A per round.
+ *   THE MODEL is the engine's internal form.  The variables are the columns j of [A | I]: j < num_vars structural, num_vars + r the slack
+ *   of row r; their bounds [l_j, u_j] are the ones the solution holds now (mlp_solution_var_bounds; a slack: [0, inf) for '<=',
+ *   (-inf, 0] for '>=', [0, 0] for '='); a non-basic column flagged MLP_NB_FIXED by mlp_solution_fix_var(s) is [xN_j, xN_j].  Every row
+ *   is the equality sum_j a_rj x_j = rhs_r over ALL its stored entries: its own slack, and the slacks of other rows that a cut row taken
+ *   from the tableau carries.  No sign is turned for Maximize.  Basis, values and reduced costs are not read: the result is a property
+ *   of the model and the fixed flags, bit-identical whatever the basis, and bit-identical from run to run.
+ *   ONE ROUND is a Jacobi sweep: every candidate comes from the bounds at the start of the round.
+ *     per row:   minfin_r = the sum of the finite minimal contributions (a l_j for a > 0, a u_j for a < 0), mininf_r = the number of
+ *                infinite ones; maxfin_r, maxinf_r mirrored (a u_j for a > 0, a l_j for a < 0).  A stored zero contributes nothing.
+ *     per entry (r, j), own = the contribution of j itself:
+ *                rest_min = minfin_r - own   if own is finite and mininf_r == 0,
+ *                           minfin_r         if own is infinite and mininf_r == 1,
+ *                           -inf             otherwise;                              rest_max mirrored (+inf otherwise);
+ *                a > 0:  upper candidate (rhs_r - rest_min) / a,  lower candidate (rhs_r - rest_max) / a;   a < 0: the two swap.
+ *                An infinite candidate imposes nothing.
+ *     per column: u' = the minimum of its upper candidates, l' = the maximum of its lower candidates;
+ *                var_is_int[j] != 0 (structural variables only):  u' = floor(u' + 1e-9),  l' = ceil(l' - 1e-9);
+ *                u' is accepted if u is infinite and u' finite, or if u' < u - 1e-7 max(1, |u|); l' likewise (l' > l + 1e-7 max(1, |l|));
+ *                an accepted l' that exceeds the round's u by at most 1e-9 max(1, |u|) is clamped to u; if it exceeds it by more the
+ *                model is INFEASIBLE.  An accepted u' against the round's l: the same, mirrored.
+ *   The rounds stop after one that accepts nothing, or after max_rounds (1..64; 10 is a good default).  INFEASIBLE stops the call at
+ *   once: *infeasible = 1, *count = 0, status 0.
+ *   THE LIST holds the structural variables whose bounds after the last round differ from the bounds at the start, MLP_NB_FIXED columns
+ *   excluded, in ascending variable number, each entry with BOTH bounds; new_lo == new_hi: the variable can be fixed.  Slack bounds
+ *   tighten too, in the working copy of the call, where they carry information from round to round; they are never listed and never
+ *   written to the solution.  *count and *infeasible are always set; cap < *count is MLP_EINVAL with nothing written (cap = num_vars
+ *   always suffices).  var_is_int == NULL: no variable is integer (num_vars is still checked).
+ *   The call is a read, side-effect free, and works on ANY state of a solution, a budget-limited or paused solve included.
+ *   MLP_EINVAL: NULL handle / count / infeasible, num_vars != mlp_solution_num_vars, max_rounds outside 1..64, a sharded solution.
+ * mlp_solution_tighten_by_propagation runs that read and applies the WHOLE list through the body of mlp_solution_set_var_bounds: one
+ *   classification, at most one FTRAN, at most one dual re-solve; mlp_bounds_info describes the application.  Like set_var_bounds it
+ *   needs a solved model (else MLP_EINVAL).  *tightened = the length of the list.  *infeasible = 1 changes nothing and is status 0: the
+ *   caller prunes.  A re-solve that ends Infeasible (or a list whose bounds cross) is status 1; like every mutator, any non-zero status
+ *   frees the solution and sets *s = NULL.  A pivot budget is lifted; cached duals and ranges are dropped.
+ * mlp_propagate_info: what the last of the two calls on this solution did (zeros before the first).  Only grows at its end;
+ *   mlp_propagate_info_size() is its size as the library was built. */
+int mlp_solution_propagate_bounds(const mlp_solution* s, const uint8_t* var_is_int, uint32_t num_vars, int32_t max_rounds, uint32_t* vars,
+                                  double* new_lo, double* new_hi, uint64_t cap, uint64_t* count, int* infeasible);
+int mlp_solution_tighten_by_propagation(mlp_solution** s, const uint8_t* var_is_int, uint32_t num_vars, int32_t max_rounds,
+                                        uint64_t* tightened, int* infeasible);
+typedef struct mlp_propagate_info {
+    uint64_t requests;      /* columns of [A | I] scanned per round */
+    uint64_t rounds;        /* rounds run (the last one accepted nothing, found the model infeasible, or was round max_rounds) */
+    uint64_t accepted;      /* bound changes accepted over all rounds, slacks included */
+    uint64_t listed;        /* entries of the list */
+    uint64_t listed_fixed;  /* ... of them with new_lo == new_hi */
+    double bytes;           /* algorithmic bytes of the device work (without the application) */
+    double device_ms;       /* its time on the device (HIP events around the launches, the per-round reads of 8 bytes included) */
+} mlp_propagate_info;
+int mlp_solution_propagate_info(const mlp_solution* s, mlp_propagate_info* out);
+uint64_t mlp_propagate_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

@@ -127,6 +127,10 @@ extern "C" {
     pub fn mlp_solution_var_bounds(s: *const mlp_solution, vars: *const u32, n: u64, lo: *mut f64, hi: *mut f64) -> c_int;
     pub fn mlp_solution_bounds_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
     pub fn mlp_bounds_info_size() -> u64;
+    pub fn mlp_solution_propagate_bounds(s: *const mlp_solution, var_is_int: *const u8, num_vars: u32, max_rounds: i32, vars: *mut u32, new_lo: *mut f64, new_hi: *mut f64, cap: u64, count: *mut u64, infeasible: *mut c_int) -> c_int;
+    pub fn mlp_solution_tighten_by_propagation(s: *mut *mut mlp_solution, var_is_int: *const u8, num_vars: u32, max_rounds: i32, tightened: *mut u64, infeasible: *mut c_int) -> c_int;
+    pub fn mlp_solution_propagate_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
+    pub fn mlp_propagate_info_size() -> u64;
     // reading the tableau: rows / columns of B^-1 A and of B^-1, solves with the basis (additive: the ABI version stays 5)
     pub fn mlp_solution_num_rows(s: *const mlp_solution) -> u64;
     pub fn mlp_solution_basis_head(s: *const mlp_solution, head: *mut u64, num_rows: u64) -> c_int;

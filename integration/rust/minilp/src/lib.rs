@@ -442,6 +442,32 @@ impl Solution {
         Some((0..count as usize).map(|t| (Variable(v[t] as usize), lo[t], hi[t])).collect())
     }
 
+    /// Bounds that the rows of the model imply on its variables, given the bounds and fixings it holds now (bound propagation, node
+    /// presolve): `None` if the rounds prove the model infeasible (prune the node), else every variable whose bounds tighten as
+    /// `(variable, lo, hi)` in ascending order; `lo == hi` means the variable can be fixed.  `integer_vars` rounds the bounds of a
+    /// marked variable inwards; at most `max_rounds` (1..=64) Jacobi rounds are run.  Works on any state of a solution (extension:
+    /// no counterpart in the reference; semantics in `minilp_hip.h`).
+    ///
+    /// # Panics
+    ///
+    /// Will panic if the mask has the wrong length or `max_rounds` is out of range.
+    pub fn propagate_bounds(&self, integer_vars: Option<&[bool]>, max_rounds: usize) -> Option<Vec<(Variable, f64, f64)>> {
+        let vm: Option<Vec<u8>> = integer_vars.map(|m| m.iter().map(|&b| b as u8).collect());
+        let (vp, vn) = vm.as_ref().map_or((std::ptr::null(), self.num_vars as u32), |m| (m.as_ptr(), m.len() as u32));
+        let n = self.num_vars;
+        let (mut v, mut lo, mut hi) = (vec![0u32; n], vec![0.0f64; n], vec![0.0f64; n]);
+        let (mut count, mut infeasible): (u64, std::os::raw::c_int) = (0, 0);
+        let st = unsafe {
+            sys::mlp_solution_propagate_bounds(self.raw, vp, vn, max_rounds.min(65) as i32, v.as_mut_ptr(), lo.as_mut_ptr(), hi.as_mut_ptr(),
+                                               n as u64, &mut count, &mut infeasible)
+        };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        if infeasible != 0 {
+            return None;
+        }
+        Some((0..count as usize).map(|t| (Variable(v[t] as usize), lo[t], hi[t])).collect())
+    }
+
     /// Range `(lo, hi)` of the right-hand side of a constraint (by index, in the order the constraints were added) over which the
     /// current basis stays feasible; within it the objective moves by `dual_value * delta` (extension).
     pub fn rhs_range(&self, constraint: usize) -> (f64, f64) {
@@ -647,6 +673,22 @@ impl Solution {
             .consume(|s| unsafe { sys::mlp_solution_tighten_by_reduced_cost(s, cutoff, vp, vn, &mut count, &mut pruned) })
             .expect("tighten_by_reduced_cost moves no value: it cannot make the problem infeasible");
         (sol, count as usize, pruned != 0)
+    }
+
+    /// [`propagate_bounds`](Self::propagate_bounds) with the whole list applied through the body of
+    /// [`set_var_bounds`](Self::set_var_bounds): one dual re-solve at most.  Returns the solution, how many variables were tightened
+    /// and whether the rounds proved the model infeasible (then nothing changes: prune the node).  Needs a solved model (extension).
+    ///
+    /// # Errors
+    ///
+    /// Will return an error if the re-solve with the tightened bounds finds the problem infeasible.
+    pub fn tighten_by_propagation(self, integer_vars: Option<&[bool]>, max_rounds: usize) -> Result<(Self, usize, bool), Error> {
+        let vm: Option<Vec<u8>> = integer_vars.map(|m| m.iter().map(|&b| b as u8).collect());
+        let (vp, vn) = vm.as_ref().map_or((std::ptr::null(), self.num_vars as u32), |m| (m.as_ptr(), m.len() as u32));
+        let (mut count, mut infeasible): (u64, std::os::raw::c_int) = (0, 0);
+        let rounds = max_rounds.min(65) as i32;
+        let sol = self.consume(|s| unsafe { sys::mlp_solution_tighten_by_propagation(s, vp, vn, rounds, &mut count, &mut infeasible) })?;
+        Ok((sol, count as usize, infeasible != 0))
     }
 
     /// Bounds `(lo, hi)` of a variable as the solution holds them now (extension).

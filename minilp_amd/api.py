@@ -91,6 +91,11 @@ class MlpBoundsInfo(C.Structure):  # include/minilp_hip.h: mlp_bounds_info (only
                 ("tightened", C.c_uint64), ("pivots", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
 
 
+class MlpPropagateInfo(C.Structure):  # include/minilp_hip.h: mlp_propagate_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("rounds", C.c_uint64), ("accepted", C.c_uint64), ("listed", C.c_uint64),
+                ("listed_fixed", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -246,6 +251,12 @@ def lib():
     sig("mlp_solution_tighten_by_reduced_cost", i32, C.POINTER(vp), dbl, pu8, u32, pu64, C.POINTER(i32))
     sig("mlp_solution_var_bounds", i32, vp, pu32, u64, pdbl, pdbl)
     sig("mlp_solution_bounds_info", i32, vp, C.POINTER(MlpBoundsInfo))
+    sig("mlp_propagate_info_size", u64)
+    if L.mlp_propagate_info_size() != C.sizeof(MlpPropagateInfo):
+        raise ImportError(f"{_SO}: mlp_propagate_info is {L.mlp_propagate_info_size()} bytes, this binding {C.sizeof(MlpPropagateInfo)}: rebuild it")
+    sig("mlp_solution_propagate_bounds", i32, vp, pu8, u32, C.c_int32, pu32, pdbl, pdbl, u64, pu64, C.POINTER(i32))
+    sig("mlp_solution_tighten_by_propagation", i32, C.POINTER(vp), pu8, u32, C.c_int32, pu64, C.POINTER(i32))
+    sig("mlp_solution_propagate_info", i32, vp, C.POINTER(MlpPropagateInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -818,6 +829,41 @@ class Solution:
         r = MlpBoundsInfo()
         _raise(lib().mlp_solution_bounds_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in MlpBoundsInfo._fields_}
+
+    # ---- bound propagation from row activities (include/minilp_hip.h: mlp_solution_propagate_bounds ...; semantics there)
+    def propagate_bounds(self, integer_vars=None, max_rounds=10):
+        """Bounds that the rows of the model imply on its structural variables, given the bounds and fixings it holds now (node
+        presolve).  Returns (vars, lo, hi, infeasible): the variables whose bounds tighten, ascending, each with both bounds;
+        lo == hi: the variable can be fixed.  infeasible: the rounds prove that the model has no solution (the arrays are empty).
+        integer_vars: a bool mask or a list of indices; the bounds of a marked variable are rounded inwards.  A read that works on any
+        state, a budget-limited solve included: the solution is left as it is."""
+        n = self.num_vars
+        vm = None if integer_vars is None else self._int_mask(integer_vars, n)
+        v, lo, hi = np.zeros(n, dtype=np.uint32), np.zeros(n), np.zeros(n)
+        count, infeasible = C.c_uint64(), C.c_int()
+        _raise(lib().mlp_solution_propagate_bounds(self._h, None if vm is None else _p(vm, C.c_uint8), n if vm is None else len(vm),
+                                                   int(max_rounds), _p(v, C.c_uint32), _p(lo, C.c_double), _p(hi, C.c_double), n,
+                                                   C.byref(count), C.byref(infeasible)))
+        k = int(count.value)
+        return v[:k].copy(), lo[:k].copy(), hi[:k].copy(), bool(infeasible.value)
+
+    def tighten_by_propagation(self, integer_vars=None, max_rounds=10):
+        """propagate_bounds with the whole list applied through set_var_bounds (one dual re-solve at most).  Returns (Solution, count,
+        infeasible); infeasible leaves the solution as it is.  Needs a solved model."""
+        n = self.num_vars
+        vm = None if integer_vars is None else self._int_mask(integer_vars, n)
+        h = self._take()
+        count, infeasible = C.c_uint64(), C.c_int()
+        _raise(lib().mlp_solution_tighten_by_propagation(C.byref(h), None if vm is None else _p(vm, C.c_uint8),
+                                                         n if vm is None else len(vm), int(max_rounds), C.byref(count),
+                                                         C.byref(infeasible)))
+        return Solution(h), int(count.value), bool(infeasible.value)
+
+    def propagate_info(self):
+        """Counters of the last propagate_bounds / tighten_by_propagation call (mlp_propagate_info) as a dict."""
+        r = MlpPropagateInfo()
+        _raise(lib().mlp_solution_propagate_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in MlpPropagateInfo._fields_}
 
     def cut_info(self):
         """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""

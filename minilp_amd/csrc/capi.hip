@@ -26,6 +26,7 @@ struct mlp_solution {
     Engine::BranchInfo branch;    // of the last mlp_solution_branch_penalties call
     Engine::FixInfo fix;          // of the last mlp_solution_cutoff_bounds / mlp_solution_fix_vars / mlp_solution_unfix_vars call
     Engine::BoundsInfo bounds;    // of the last mlp_solution_set_var_bounds / mlp_solution_tighten_by_reduced_cost call
+    Engine::PropagateInfo prop;   // of the last mlp_solution_propagate_bounds / mlp_solution_tighten_by_propagation call
     std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
     std::vector<uint32_t> tab_indices;
     std::vector<double> tab_values;
@@ -806,6 +807,69 @@ int mlp_solution_bounds_info(const mlp_solution* s, mlp_bounds_info* out) {
     });
 }
 uint64_t mlp_bounds_info_size(void) { return (uint64_t)sizeof(mlp_bounds_info); }
+
+// ---- bound propagation from row activities (propagate.inc)
+int mlp_solution_propagate_bounds(const mlp_solution* cs, const uint8_t* var_is_int, uint32_t num_vars, int32_t max_rounds, uint32_t* vars,
+                                  double* new_lo, double* new_hi, uint64_t cap, uint64_t* count, int* infeasible) {
+    return guarded([&] {
+        mlp_solution* s = const_cast<mlp_solution*>(cs);
+        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+        if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "propagate_bounds is not available on a sharded solution");
+        Engine* e = s->eng;
+        if (!count || !infeasible) throw MlpError(MLP_EINVAL, "propagate_bounds: NULL count / infeasible");
+        *count = 0;
+        *infeasible = 0;
+        if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "propagate_bounds: num_vars must be mlp_solution_num_vars");
+        if (max_rounds < 1 || max_rounds > 64) throw MlpError(MLP_EINVAL, "propagate_bounds: max_rounds must lie in 1..64");
+        Engine::PropagateInfo info;
+        std::vector<uint32_t> v;
+        std::vector<double> lo, hi;
+        bool inf = false;
+        e->propagate_bounds(var_is_int, (int)max_rounds, v, lo, hi, inf, info);
+        *infeasible = inf ? 1 : 0;
+        *count = (uint64_t)v.size();
+        if (cap < *count) throw MlpError(MLP_EINVAL, "propagate_bounds: cap is below the count (num_vars always suffices)");
+        if (*count && (!vars || !new_lo || !new_hi)) throw MlpError(MLP_EINVAL, "propagate_bounds: NULL output");
+        if (*count) {
+            std::memcpy(vars, v.data(), sizeof(uint32_t) * v.size());
+            std::memcpy(new_lo, lo.data(), sizeof(double) * v.size());
+            std::memcpy(new_hi, hi.data(), sizeof(double) * v.size());
+        }
+        s->prop = info;
+    });
+}
+int mlp_solution_tighten_by_propagation(mlp_solution** s, const uint8_t* var_is_int, uint32_t num_vars, int32_t max_rounds,
+                                        uint64_t* tightened, int* infeasible) {
+    return consume_on_error(s, guarded([&] {
+        require(s);
+        refuse_if_sharded(*s);
+        Engine* e = (*s)->eng;
+        if (e->transport != "none") throw MlpError(MLP_EINVAL, "tighten_by_propagation is not available on a sharded solution");
+        if (!tightened || !infeasible) throw MlpError(MLP_EINVAL, "tighten_by_propagation: NULL tightened / infeasible");
+        *tightened = 0;
+        *infeasible = 0;
+        if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "tighten_by_propagation: num_vars must be mlp_solution_num_vars");
+        if (max_rounds < 1 || max_rounds > 64) throw MlpError(MLP_EINVAL, "tighten_by_propagation: max_rounds must lie in 1..64");
+        if (!e->solved()) throw MlpError(MLP_EINVAL, "tighten_by_propagation: model not solved");
+        (*s)->bounds = Engine::BoundsInfo();
+        (*s)->prop = Engine::PropagateInfo();
+        e->pivot_budget = -1;
+        stale(*s);
+        bool inf = false;
+        *tightened = e->tighten_by_propagation(var_is_int, (int)max_rounds, inf, (*s)->prop, (*s)->bounds);
+        *infeasible = inf ? 1 : 0;
+    }));
+}
+int mlp_solution_propagate_info(const mlp_solution* s, mlp_propagate_info* out) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / propagate info");
+        std::memset(out, 0, sizeof(*out));
+        const Engine::PropagateInfo& f = s->prop;
+        out->requests = f.requests; out->rounds = f.rounds; out->accepted = f.accepted; out->listed = f.listed;
+        out->listed_fixed = f.listed_fixed; out->bytes = f.bytes; out->device_ms = f.device_ms;
+    });
+}
+uint64_t mlp_propagate_info_size(void) { return (uint64_t)sizeof(mlp_propagate_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

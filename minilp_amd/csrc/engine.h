@@ -265,6 +265,18 @@ public:
     // cutoff_bounds with every entry applied on the device (g as there); the host reads back the count only
     uint64_t tighten_by_reduced_cost(double g, const uint8_t* var_is_int, BoundsInfo& info);
     void var_bounds(const uint32_t* vars, uint64_t n, double* lo, double* hi);  // vars == nullptr: all num_vars of them
+    // Bound propagation from row activities (propagate.inc; include/minilp_hip.h mlp_solution_propagate_bounds,
+    // mlp_solution_tighten_by_propagation).  The read works on any state and reads neither basis nor values: Jacobi
+    // rounds over the model's rows, the bounds and the fixed flags; the list comes back in ascending variable number, empty when the
+    // rounds prove the model infeasible.
+    struct PropagateInfo {
+        uint64_t requests = 0, rounds = 0, accepted = 0, listed = 0, listed_fixed = 0;
+        double bytes = 0, device_ms = 0;
+    };
+    void propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::vector<uint32_t>& vars, std::vector<double>& lo,
+                          std::vector<double>& hi, bool& infeasible, PropagateInfo& info);
+    // the read, then the whole list through set_var_bounds (binfo describes that application); returns the length of the list
+    uint64_t tighten_by_propagation(const uint8_t* var_is_int, int max_rounds, bool& infeasible, PropagateInfo& info, BoundsInfo& binfo);
     // Reading the tableau of the current basis (tableau.inc; include/minilp_hip.h mlp_solution_binv_rows ...).  Columns:
     // j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by CONSTRAINT (0 / ignored for one
     // without a row), vectors by position have length num_rows().  Internal form A x + s = b: no sign turn for Maximize.  Requests are
@@ -324,6 +336,7 @@ private:
     struct ShiftBufs;  // the blocks of the shift that fix_vars and set_var_bounds share
     double shift_basic_values(FixBufs& b, ShiftBufs& w);
     void cutoff_launch(double g, const uint8_t* var_is_int, CutoffRun& r);
+    void cutoff_alloc(const uint8_t* var_is_int, CutoffRun& r);
     std::vector<int> h_cons_row;  // constraint (Problem / Solution::add_constraint order) -> row; -1 for one without terms (no row)
     std::vector<int> h_rptr, h_rcol;
     std::vector<double> h_rval;

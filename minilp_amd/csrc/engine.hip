@@ -4274,6 +4274,14 @@ struct Engine::CutoffRun {
     const int* count() const { return sums.p + nsum; }
 };
 void Engine::cutoff_launch(double g, const uint8_t* var_is_int, CutoffRun& r) {
+    cutoff_alloc(var_is_int, r);
+    r.b.g = g;
+    HIPCHECK(hipEventRecord(r.ev.e[0], st));
+    launch_cutoff_bounds(hview, r.b, r.sums.p, st);
+}
+// the staging, the list and the uploaded marks of one compaction over the structural variables (propagate_bounds compacts its list
+// into the same buffers)
+void Engine::cutoff_alloc(const uint8_t* var_is_int, CutoffRun& r) {
     const int nv = num_vars;
     sync_view();
     r.ntiles = cutoff_tiles(nv);
@@ -4286,9 +4294,7 @@ void Engine::cutoff_launch(double g, const uint8_t* var_is_int, CutoffRun& r) {
     CutoffBufs& b = r.b;
     b.mask = var_is_int ? r.dmask.p : nullptr;
     b.tcnt = r.tcnt.p; b.toff = r.toff.p; b.svar = r.svar.p; b.slo = r.slo.p; b.shi = r.shi.p; b.ovar = r.ovar.p; b.olo = r.olo.p; b.ohi = r.ohi.p;
-    b.nv = nv; b.g = g;
-    HIPCHECK(hipEventRecord(r.ev.e[0], st));
-    launch_cutoff_bounds(hview, b, r.sums.p, st);
+    b.nv = nv; b.g = 0.0;
 }
 // The read: nothing is written but private buffers; the reduced costs are the engine's own d on the device, the host reads back the
 // length of the list and then the list.
@@ -4624,5 +4630,98 @@ uint64_t Engine::tighten_by_reduced_cost(double g, const uint8_t* var_is_int, Bo
     info.device_ms = r.ev.ms();
     info.wall_ms = (now_s() - t0) * 1e3;
     return (uint64_t)total;
+}
+
+// ------------------------------------------------------------------ bound propagation (propagate.inc)
+// The read: nothing is written but private buffers.  Per round the host reads back two integers (bounds accepted, columns found
+// infeasible); at the end the length of the list and the list.
+void Engine::propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::vector<uint32_t>& vars, std::vector<double>& lo,
+                              std::vector<double>& hi, bool& infeasible, PropagateInfo& info) {
+    if (sharded()) throw MlpError(-1, "propagate_bounds is not available on a sharded solution");
+    if (max_rounds < 1 || max_rounds > 64) throw MlpError(-1, "propagate_bounds: max_rounds must lie in 1..64");
+    info = PropagateInfo();
+    infeasible = false;
+    vars.clear(); lo.clear(); hi.clear();
+    const int nv = num_vars, N = N_, m = m_;
+    if (nv <= 0) return;
+    CutoffRun r;
+    cutoff_alloc(var_is_int, r);
+    const Geom g = geom();
+    DevBuf<double> rhs, wlo[2], whi[2];
+    DevBuf<double2> rowfin;
+    DevBuf<int2> rowinf;
+    DevBuf<int> word;
+    rhs.upload(h_rhs, st);
+    rhs.ensure((size_t)m + 1, (size_t)m, st);
+    for (int q = 0; q < 2; ++q) { wlo[q].ensure((size_t)N + 1, 0, st); whi[q].ensure((size_t)N + 1, 0, st); }
+    rowfin.ensure((size_t)m + 1, 0, st); rowinf.ensure((size_t)m + 1, 0, st); word.ensure(2, 0, st);
+    PropBufs b{};
+    b.mask = r.b.mask; b.rhs = rhs.p;
+    for (int q = 0; q < 2; ++q) { b.lo[q] = wlo[q].p; b.hi[q] = whi[q].p; }
+    b.rowfin = rowfin.p; b.rowinf = rowinf.p; b.word = word.p;
+    b.m = m; b.N = N; b.nv = nv;
+    info.requests = (uint64_t)N;
+    HIPCHECK(hipEventRecord(r.ev.e[0], st));
+    launch_prop_setup(hview, b, st);
+    int cur = 0;
+    for (int rnd = 1; rnd <= max_rounds; ++rnd) {
+        launch_prop_round(hview, g, b, cur, st);
+        int w[2] = {0, 0};
+        HIPCHECK(hipMemcpyAsync(w, word.p, sizeof(w), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        info.rounds = (uint64_t)rnd;
+        if (w[0] < 0 || w[1] < 0 || (long)w[0] > 2L * N) throw MlpError(-3, "propagate_bounds: a round returned impossible counts");
+        if (w[1]) {
+            infeasible = true;
+            break;
+        }
+        info.accepted += (uint64_t)w[0];
+        cur ^= 1;
+        if (!w[0]) break;
+    }
+    int total = 0;
+    if (!infeasible) {
+        launch_prop_list(hview, b, r.b, cur, r.sums.p, st);
+        HIPCHECK(hipEventRecord(r.ev.e[1], st));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipMemcpyAsync(&total, r.count(), sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipStreamSynchronize(st));
+        if (total < 0 || total > nv) throw MlpError(-3, "propagate_bounds: the compaction returned an impossible count");
+        vars.resize((size_t)total); lo.resize((size_t)total); hi.resize((size_t)total);
+        if (total) {
+            HIPCHECK(hipMemcpyAsync(vars.data(), r.ovar.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipMemcpyAsync(lo.data(), r.olo.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipMemcpyAsync(hi.data(), r.ohi.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+            HIPCHECK(hipStreamSynchronize(st));
+        }
+    } else {
+        HIPCHECK(hipEventRecord(r.ev.e[1], st));
+        HIPCHECK(hipGetLastError());
+        HIPCHECK(hipStreamSynchronize(st));
+    }
+    info.listed = (uint64_t)total;
+    for (int i = 0; i < total; ++i) info.listed_fixed += lo[i] == hi[i] ? 1 : 0;
+    // algorithmic bytes.  Set-up: bounds, location, flags read (21), working bounds written (16) per column.  A round: the CSR pass reads
+    // 12 bytes per entry and gathers two bounds (16), and writes 24 per row; the CSC pass reads 12 per entry and gathers the row's four
+    // numbers and its right-hand side (32), and reads and writes both bounds of every column (32).  The list: 36 per structural variable,
+    // two counters per tile written and read twice, 80 per entry as in cutoff_bounds.
+    const double nnz = (double)h_rcol.size();
+    info.bytes = 37.0 * N + (double)info.rounds * (72.0 * nnz + 24.0 * m + 32.0 * N + (var_is_int ? 1.0 * nv : 0.0)) +
+                 (infeasible ? 0.0 : 36.0 * nv + 16.0 * (double)r.ntiles + 80.0 * total);
+    info.device_ms = r.ev.ms();
+}
+
+uint64_t Engine::tighten_by_propagation(const uint8_t* var_is_int, int max_rounds, bool& infeasible, PropagateInfo& info, BoundsInfo& binfo) {
+    if (sharded()) throw MlpError(-1, "tighten_by_propagation is not available on a sharded solution");
+    if (!solved()) throw MlpError(-1, "tighten_by_propagation: model not solved (the re-solve is the dual one: it needs a dual-feasible basis)");
+    binfo = BoundsInfo();
+    std::vector<uint32_t> v;
+    std::vector<double> lo, hi;
+    propagate_bounds(var_is_int, max_rounds, v, lo, hi, infeasible, info);
+    if (infeasible || v.empty()) return 0;
+    host_bounds();
+    set_var_bounds(std::vector<int>(v.begin(), v.end()), lo, hi, binfo);
+    binfo.tightened = (uint64_t)v.size();
+    return (uint64_t)v.size();
 }
 }  // namespace mlp

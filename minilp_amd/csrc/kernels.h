@@ -670,6 +670,22 @@ void launch_bounds_classify(const DevView& dv, const BoundBufs& b, hipStream_t s
 void launch_bounds_commit(const DevView& dv, const BoundBufs& b, int shifted, hipStream_t st);  // objective (if shifted), xN, flags, bounds
 // the list of launch_cutoff_bounds written to the bounds; count: its length on the device (sums[ceil(cutoff_tiles(nv) / 4096)])
 void launch_bounds_apply_list(const DevView& dv, const CutoffBufs& c, const int* count, double* var_lo, double* var_hi, hipStream_t st);
+// bound propagation from row activities (propagate.inc): Jacobi rounds of one CSR pass and one CSC pass over [A | I]; the list of the
+// tightened structural variables is compacted into a CutoffBufs (its mask and g unused)
+struct PropBufs {
+    const uint8_t* mask;  // nv: 1 = integer variable; nullptr: no bound is rounded
+    const double* rhs;    // m
+    double* lo[2];        // N each: the working bounds of a round's start and of its end (the roles swap per round)
+    double* hi[2];
+    double2* rowfin;      // m: (minfin, maxfin), the sums of a row's finite minimal / maximal contributions
+    int2* rowinf;         // m: (mininf, maxinf), the counts of its infinite ones
+    int* word;            // 2: bounds accepted in the round, columns found infeasible in it
+    int m, N, nv;         // rows, columns of [A | I], structural variables
+};
+void launch_prop_setup(const DevView& dv, const PropBufs& b, hipStream_t st);                      // lo[0], hi[0]
+void launch_prop_round(const DevView& dv, const Geom& g, const PropBufs& b, int cur, hipStream_t st);  // rowfin, rowinf; lo / hi[cur ^ 1], word
+// the structural variables whose bounds lo / hi[cur] differ from var_lo / var_hi, as launch_cutoff_bounds leaves its list (sums as there)
+void launch_prop_list(const DevView& dv, const PropBufs& b, const CutoffBufs& c, int cur, int* sums, hipStream_t st);
 // Sparse rows out of a dense block, one batch of at most RG_BATCH basic positions (tableau.inc, cuts.inc, gmi.inc).  Phase 1,
 // launch_rows_generate: the rows of B^-1 (b.blk, b.req, the SolveBufs part as for ranging), one pass over A that leaves the dense block
 // dense[N][RG_BATCH] by variable, the scanned offsets off[RG_BATCH * cut_segments(N)] (cnt: same size, sums: the scan's scratch), the row

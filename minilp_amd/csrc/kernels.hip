@@ -5770,6 +5770,7 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
 #include "tableau.inc" // reading the tableau: 16 rows of B^-1 A as sparse rows, 16 solves with dense right-hand sides per pass over W0 (side-effect free)
 #include "fixing.inc"  // reduced-cost bounds from a cutoff (one classifying pass, deterministic compaction; side-effect free) and the kernels of fix_vars / unfix_vars
 #include "bounds.inc"  // new bounds for structural variables: classification, commit, and the device-to-device list of the reduced-cost bounds
+#include "propagate.inc"  // bound propagation from row activities: a CSR pass and a CSC pass per Jacobi round, the list by fixing.inc's compaction (side-effect free)
 
 void launch_gauss_jordan(double* Kd, double* Winv, int k, int ld, int* d_flag, double* d_scratch, hipStream_t st) {
     if (k <= 0) return;
