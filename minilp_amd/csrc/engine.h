@@ -253,7 +253,7 @@ public:
     // served together (one FTRAN, none when nothing moves), the basic ones by one forced dual pivot each, feasibility restored once
     void fix_vars(const std::vector<int>& vars, const std::vector<double>& vals, FixInfo& info);
     uint64_t unfix_vars(const std::vector<int>& vars, FixInfo& info);  // unfix_var's rule per request, ONE optimize(); returns the released count
-    // New bounds for structural variables of a solved model (bounds.inc; include/minilp_hip.h mlp_solution_set_var_bounds,
+    // New bounds for structural variables of a solved model (fixing.inc, bounds.inc; include/minilp_hip.h mlp_solution_set_var_bounds,
     // mlp_solution_tighten_by_reduced_cost).  BoundsInfo describes the last of the two mutators.
     struct BoundsInfo {
         uint64_t requests = 0, basic = 0, nonbasic = 0, shifted = 0, solves = 0, tightened = 0, pivots = 0;
@@ -334,9 +334,22 @@ private:
     void host_bounds();
     struct CutoffRun;  // the private device buffers of one run of launch_cutoff_bounds
     struct ShiftBufs;  // the blocks of the shift that fix_vars and set_var_bounds share
-    double shift_basic_values(FixBufs& b, ShiftBufs& w);
+    double shift_basic_values(BoundBufs& b, ShiftBufs& w);
+    // The body that fix_vars and set_var_bounds share: classify the requests (ascending variable number), shift the basic values if a
+    // request moves, commit, follow with the host mirrors.  before_commit sees the counts while nothing has changed yet and may refuse.
+    struct Moves {
+        int shifted = 0, basic = 0, infinite = 0;  // requests that move, basic requests, requests whose side has an infinite new bound
+        uint64_t solves = 0;
+        double bytes = 0, device_ms = 0;
+    };
+    Moves move_nonbasic(const std::vector<int>& var, const std::vector<double>& lo, const std::vector<double>& hi, bool fix,
+                        const std::function<void(const Moves&)>& before_commit = nullptr);
+    uint64_t release_fixed(const std::vector<int>& vars, FixInfo& info, const char* who);  // the body of unfix_var and unfix_vars
     void cutoff_launch(double g, const uint8_t* var_is_int, CutoffRun& r);
     void cutoff_alloc(const uint8_t* var_is_int, CutoffRun& r);
+    // the length of r's list, checked against the number of variables (the error names `who`); vars != nullptr: the list as well
+    int cutoff_read(const CutoffRun& r, const char* who, std::vector<uint32_t>* vars = nullptr, std::vector<double>* lo = nullptr,
+                    std::vector<double>* hi = nullptr, uint64_t* listed_fixed = nullptr);
     std::vector<int> h_cons_row;  // constraint (Problem / Solution::add_constraint order) -> row; -1 for one without terms (no row)
     std::vector<int> h_rptr, h_rcol;
     std::vector<double> h_rval;

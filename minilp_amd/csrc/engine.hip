@@ -2725,26 +2725,8 @@ int Engine::fix_var_apply(int var, double val) {
 
 bool Engine::unfix_var(int var) {  // solver.rs:418-438
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    if (h_var_loc[var] >= 0) return false;
-    int col = -1 - h_var_loc[var];
-    if (!h_nb_fixed[col]) return false;
-    h_nb_fixed[col] = 0;
-    fetch_values();
-    host_bounds();
-    double cur = h_xN[col];
-    uint8_t f = (uint8_t)((cur == h_lo[var] ? NB_AT_MIN : 0) | (cur == h_hi[var] ? NB_AT_MAX : 0));
-    HIPCHECK(hipMemcpyAsync(d_nbflags.p + col, &f, 1, hipMemcpyHostToDevice, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    dual_feasible = false;
-    double t0 = now_s();
-    budget_exhausted = false;
-    try {
-        optimize();
-    } catch (LpFail&) {
-        throw MlpError(-1, "unfix_var: optimize failed (solver.rs:433 unwrap)");
-    }
-    stats.solve_wall_s += now_s() - t0;
-    return true;
+    FixInfo unreported;   // (the single form reports nothing: what mlp_fix_info shows stays)
+    return release_fixed(std::vector<int>(1, var), unreported, "unfix_var") != 0;
 }
 
 void Engine::add_gomory_cut(int var) {  // solver.rs:440-460
@@ -4310,26 +4292,29 @@ void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint
     cutoff_launch(g, var_is_int, r);
     HIPCHECK(hipEventRecord(r.ev.e[1], st));
     HIPCHECK(hipGetLastError());
-    const long ntiles = r.ntiles;
-    const DevBuf<uint32_t>& ovar = r.ovar;
-    const DevBuf<double>&olo = r.olo, &ohi = r.ohi;
+    const int total = cutoff_read(r, "cutoff_bounds", &vars, &lo, &hi, &info.listed_fixed);
+    info.listed = (uint64_t)total;
+    // algorithmic bytes: per variable its location (4), and for a non-basic one its flags, reduced cost and bounds (25; the value of a
+    // marked column and its mark: 9); per tile two counters written, read twice; per entry 20 bytes written, read, written and read back
+    info.bytes = (var_is_int ? 38.0 : 29.0) * nv + 16.0 * (double)r.ntiles + 80.0 * total;
+    info.device_ms = r.ev.ms();
+}
+int Engine::cutoff_read(const CutoffRun& r, const char* who, std::vector<uint32_t>* vars, std::vector<double>* lo, std::vector<double>* hi,
+                        uint64_t* listed_fixed) {
     int total = 0;
     HIPCHECK(hipMemcpyAsync(&total, r.count(), sizeof(int), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    if (total < 0 || total > nv) throw MlpError(-3, "cutoff_bounds: the compaction returned an impossible count");
-    vars.resize((size_t)total); lo.resize((size_t)total); hi.resize((size_t)total);
+    if (total < 0 || total > r.b.nv) throw MlpError(-3, std::string(who) + ": the compaction returned an impossible count");
+    if (!vars) return total;
+    vars->resize((size_t)total); lo->resize((size_t)total); hi->resize((size_t)total);
     if (total) {
-        HIPCHECK(hipMemcpyAsync(vars.data(), ovar.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(lo.data(), olo.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipMemcpyAsync(hi.data(), ohi.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(vars->data(), r.ovar.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(lo->data(), r.olo.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
+        HIPCHECK(hipMemcpyAsync(hi->data(), r.ohi.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
     }
-    info.listed = (uint64_t)total;
-    for (int i = 0; i < total; ++i) info.listed_fixed += lo[i] == hi[i] ? 1 : 0;
-    // algorithmic bytes: per variable its location (4), and for a non-basic one its flags, reduced cost and bounds (25; the value of a
-    // marked column and its mark: 9); per tile two counters written, read twice; per entry 20 bytes written, read, written and read back
-    info.bytes = (var_is_int ? 38.0 : 29.0) * nv + 16.0 * (double)ntiles + 80.0 * total;
-    info.device_ms = r.ev.ms();
+    for (int i = 0; i < total; ++i) *listed_fixed += (*lo)[i] == (*hi)[i] ? 1 : 0;
+    return total;
 }
 
 // The shift that fix_vars and set_var_bounds share: b.var / b.diff hold the moves of non-basic columns; r = A delta, ONE FTRAN through the
@@ -4338,7 +4323,7 @@ void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint
 struct Engine::ShiftBufs {
     DevBuf<double> delta, X, Y, XK, YK, lrh;
 };
-double Engine::shift_basic_values(FixBufs& b, ShiftBufs& w) {
+double Engine::shift_basic_values(BoundBufs& b, ShiftBufs& w) {
     constexpr int R = RG_BATCH;
     const DevView& dv = hview;
     const Geom g = geom();
@@ -4361,6 +4346,72 @@ double Engine::shift_basic_values(FixBufs& b, ShiftBufs& w) {
            (fac_on_ ? (24.0 + 16.0 * ctx.J) * m : 8.0 * (double)k * k + 16.0 * ctx.J * k + 32.0 * (double)k * R + 20.0 * (double)h_rcol.size());
 }
 
+// The body that fix_vars and set_var_bounds share (fixing.inc): the requests, sorted by variable — a fixing passes its non-basic ones only,
+// as lo == hi == the value asked for — are classified into private buffers and the counts read back; before_commit sees them while
+// nothing has changed yet; then the shift of the basic values if a request moves, the commit, the host mirrors.
+Engine::Moves Engine::move_nonbasic(const std::vector<int>& hvar, const std::vector<double>& hlo, const std::vector<double>& hhi, bool fix,
+                                    const std::function<void(const Moves&)>& before_commit) {
+    const size_t n = hvar.size();
+    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    DevBuf<int> dvar, dcnt;
+    DevBuf<double> dlo, dhi, dtarget, ddiff;
+    DevBuf<uint8_t> dflags;
+    dvar.upload(hvar, st); dlo.upload(hlo, st); dhi.upload(hhi, st);
+    dtarget.ensure(n, 0, st); ddiff.ensure(n, 0, st); dflags.ensure(n, 0, st); dcnt.ensure(3, 0, st);
+    BoundBufs b{};
+    b.var = dvar.p; b.lo = dlo.p; b.hi = dhi.p; b.target = dtarget.p; b.diff = ddiff.p; b.flags = dflags.p; b.cnt = dcnt.p;
+    b.var_lo = d_lo.p; b.var_hi = d_hi.p; b.n = (long)n;
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
+    launch_move_classify(hview, b, fix ? 1 : 0, st);
+    int cnt[3] = {0, 0, 0};
+    HIPCHECK(hipMemcpyAsync(cnt, dcnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    Moves mv;
+    mv.shifted = cnt[0]; mv.basic = cnt[1]; mv.infinite = cnt[2];
+    // classification, per request: variable, location, bounds, flags and value read (33; new bounds read the reduced cost as well: 41);
+    // target, diff and flags written (17).  (Of a fixing's 50, a classification of its own could spare the 4 of the location, the second
+    // bound and the 9 of target and flags: that is the price of the one kernel.)
+    mv.bytes = (fix ? 50.0 : 58.0) * (double)n;
+    if (before_commit) before_commit(mv);
+    // from here on the state changes: the shift (r = A delta, ONE FTRAN through the dense right-hand-side path, x_B -= B^-1 r), the commit
+    ShiftBufs w;
+    if (mv.shifted && m_ > 0) {
+        mv.bytes += shift_basic_values(b, w);
+        mv.solves = 1;
+    }
+    launch_move_commit(hview, b, fix ? 1 : 0, mv.shifted ? 1 : 0, st);
+    HIPCHECK(hipEventRecord(ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    mv.device_ms = ev.ms();
+    mv.bytes += (fix ? 18.0 : 41.0) * (double)n;  // commit: variable, location, diff, flags read and the flags written; new bounds: the bounds as well
+    for (size_t i = 0; i < n; ++i) {
+        if (fix) {
+            h_nb_fixed[-1 - h_var_loc[hvar[i]]] = 1;
+        } else {
+            h_lo[hvar[i]] = hlo[i];
+            h_hi[hvar[i]] = hhi[i];
+        }
+    }
+    if (mv.shifted) values_dirty = true;
+    return mv;
+}
+
+// What fix_vars, unfix_vars and set_var_bounds report about their own run: the pivots and the wall time of the call.
+struct CallTimer {
+    Stats& stats;
+    const double t0 = now_s();
+    const uint64_t it0;
+    explicit CallTimer(Stats& s) : stats(s), it0(s.iterations) {}
+    void finish(uint64_t& pivots, double& wall_ms) {
+        pivots = stats.iterations - it0;
+        stats.solve_wall_s += now_s() - t0;
+        wall_ms = (now_s() - t0) * 1e3;
+    }
+};
+
 // The batched forms.  Checks first, nothing is changed before they pass.
 void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& vals, FixInfo& info) {
     if (sharded()) throw MlpError(-1, "fix_vars is not available on a sharded solution");
@@ -4377,8 +4428,7 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
     for (size_t i = 0; i < vars.size(); ++i)
         if (!(vals[i] >= h_lo[vars[i]] && vals[i] <= h_hi[vars[i]])) throw LpFail{1};
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    const double t0 = now_s();
-    const uint64_t it0 = stats.iterations;
+    CallTimer timer(stats);
     ensure_beta();
     // step 1: the requests non-basic at the basis the call finds, in ascending variable number
     std::vector<std::pair<int, double>> nb;
@@ -4391,43 +4441,18 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
     info.nonbasic = nb.size();
     bool moved = !basic.empty();
     if (!nb.empty()) {
-        const size_t n = nb.size();
-        std::vector<int> hcol(n), hvar(n);
-        std::vector<double> hval(n);
-        for (size_t i = 0; i < n; ++i) {
+        std::vector<int> hvar(nb.size());
+        std::vector<double> hval(nb.size());
+        for (size_t i = 0; i < nb.size(); ++i) {
             hvar[i] = nb[i].first;
-            hcol[i] = -1 - h_var_loc[nb[i].first];
             hval[i] = nb[i].second;
         }
-        pull_ctl();  // (k_ and the count of pending terms as the device holds them)
-        sync_view();
-        DevBuf<int> dcol, dvar, dcnt;
-        DevBuf<double> dval, ddiff;
-        dcol.upload(hcol, st); dvar.upload(hvar, st); dval.upload(hval, st);
-        ddiff.ensure(n, 0, st); dcnt.ensure(1, 0, st);
-        FixBufs b{};
-        b.col = dcol.p; b.var = dvar.p; b.val = dval.p; b.diff = ddiff.p; b.nshift = dcnt.p; b.n = (long)n;
-        EventPair ev;
-        HIPCHECK(hipEventRecord(ev.e[0], st));
-        launch_fix_diff(hview, b, st);
-        int shifted = 0;
-        HIPCHECK(hipMemcpyAsync(&shifted, dcnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        info.shifted = (uint64_t)shifted;
-        info.bytes = 36.0 * (double)n;
-        ShiftBufs w;
-        if (shifted && m_ > 0) {
-            info.bytes += shift_basic_values(b, w);
-            info.solves = 1;
-            moved = true;
-        }
-        launch_fix_commit(hview, b, shifted ? 1 : 0, st);
-        HIPCHECK(hipEventRecord(ev.e[1], st));
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipStreamSynchronize(st));
-        info.device_ms = ev.ms();
-        for (size_t i = 0; i < n; ++i) h_nb_fixed[hcol[i]] = 1;
-        if (shifted) values_dirty = true;
+        const Moves mv = move_nonbasic(hvar, hval, hval, true);
+        info.shifted = (uint64_t)mv.shifted;
+        info.solves = mv.solves;
+        info.bytes = mv.bytes;
+        info.device_ms = mv.device_ms;
+        moved = moved || mv.solves;
     }
     // step 2: the basic requests in list order, one forced dual pivot each (the columns fixed above cannot enter)
     for (size_t i : basic) {
@@ -4440,35 +4465,36 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
         budget_exhausted = false;
         restore_feasibility();
     }
-    info.pivots = stats.iterations - it0;
-    stats.solve_wall_s += now_s() - t0;
-    info.wall_ms = (now_s() - t0) * 1e3;
+    timer.finish(info.pivots, info.wall_ms);
 }
 
 uint64_t Engine::unfix_vars(const std::vector<int>& vars, FixInfo& info) {
     if (sharded()) throw MlpError(-1, "unfix_vars is not available on a sharded solution");
-    info = FixInfo();
-    info.requests = vars.size();
     for (int j : vars)
         if (j < 0 || j >= num_vars) throw MlpError(-1, "unfix_vars: variable out of range");
-    std::vector<int> hcol, hvar;  // unfix_var's rule: a basic or not-fixed variable is skipped
+    return release_fixed(vars, info, "unfix_vars");
+}
+// unfix_var's rule (solver.rs:418-438) per request: a basic or not-fixed variable is skipped; the flags of a released column come from
+// its value against its bounds, on the device; ONE optimize().  Returns the released count.
+uint64_t Engine::release_fixed(const std::vector<int>& vars, FixInfo& info, const char* who) {
+    info = FixInfo();
+    info.requests = vars.size();
+    std::vector<int> hvar;
     for (int j : vars) {
         if (h_var_loc[j] >= 0) continue;
         const int col = -1 - h_var_loc[j];
         if (!h_nb_fixed[col]) continue;
         h_nb_fixed[col] = 0;
-        hcol.push_back(col);
         hvar.push_back(j);
     }
-    if (hcol.empty()) return 0;
+    if (hvar.empty()) return 0;
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    const double t0 = now_s();
-    const uint64_t it0 = stats.iterations;
+    CallTimer timer(stats);
     sync_view();
-    DevBuf<int> dcol, dvar;
-    dcol.upload(hcol, st); dvar.upload(hvar, st);
-    FixBufs b{};
-    b.col = dcol.p; b.var = dvar.p; b.n = (long)hcol.size();
+    DevBuf<int> dvar;
+    dvar.upload(hvar, st);
+    BoundBufs b{};
+    b.var = dvar.p; b.n = (long)hvar.size();
     EventPair ev;
     HIPCHECK(hipEventRecord(ev.e[0], st));
     launch_fix_release(hview, b, st);
@@ -4476,21 +4502,19 @@ uint64_t Engine::unfix_vars(const std::vector<int>& vars, FixInfo& info) {
     HIPCHECK(hipGetLastError());
     HIPCHECK(hipStreamSynchronize(st));
     info.device_ms = ev.ms();
-    info.bytes = 33.0 * (double)hcol.size();
-    info.unfixed = hcol.size();
+    info.bytes = 33.0 * (double)hvar.size();
+    info.unfixed = hvar.size();
     dual_feasible = false;
     budget_exhausted = false;
     try {
         optimize();
     } catch (LpFail&) {
-        throw MlpError(-1, "unfix_vars: optimize failed (solver.rs:433 unwrap)");
+        throw MlpError(-1, std::string(who) + ": optimize failed (solver.rs:433 unwrap)");
     }
-    info.pivots = stats.iterations - it0;
-    stats.solve_wall_s += now_s() - t0;
-    info.wall_ms = (now_s() - t0) * 1e3;
+    timer.finish(info.pivots, info.wall_ms);
     return info.unfixed;
 }
-// ------------------------------------------------------------------ bounds (bounds.inc)
+// ------------------------------------------------------------------ bounds (fixing.inc, bounds.inc)
 void Engine::host_bounds() {
     if (!bounds_mirror_stale_) return;
     HIPCHECK(hipMemcpyAsync(h_lo.data(), d_lo.p, sizeof(double) * (size_t)num_vars, hipMemcpyDeviceToHost, st));
@@ -4538,8 +4562,7 @@ void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<doub
     }
     for (size_t i = 0; i < n; ++i)
         if (lo[i] > hi[i]) throw LpFail{1};
-    const double t0 = now_s();
-    const uint64_t it0 = stats.iterations;
+    CallTimer timer(stats);
     host_bounds();
     std::vector<int> hvar(n);
     std::vector<double> hlo(n), hhi(n);
@@ -4548,62 +4571,27 @@ void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<doub
         hlo[i] = lo[ord[i]];
         hhi[i] = hi[ord[i]];
     }
-    // step 1: the classification
-    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
-    sync_view();
-    DevBuf<int> dvar, dcnt;
-    DevBuf<double> dlo, dhi, dtarget, ddiff;
-    DevBuf<uint8_t> dflags;
-    dvar.upload(hvar, st); dlo.upload(hlo, st); dhi.upload(hhi, st);
-    dtarget.ensure(n, 0, st); ddiff.ensure(n, 0, st); dflags.ensure(n, 0, st); dcnt.ensure(3, 0, st);
-    BoundBufs b{};
-    b.var = dvar.p; b.lo = dlo.p; b.hi = dhi.p; b.target = dtarget.p; b.diff = ddiff.p; b.flags = dflags.p; b.cnt = dcnt.p;
-    b.var_lo = d_lo.p; b.var_hi = d_hi.p; b.n = (long)n;
-    EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
-    launch_bounds_classify(hview, b, st);
-    int cnt[3] = {0, 0, 0};
-    HIPCHECK(hipMemcpyAsync(cnt, dcnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    if (cnt[2])
-        throw MlpError(-1, "set_var_bounds: " + std::to_string(cnt[2]) + " request(s) make infinite the bound a non-basic column sits at; the "
-                           "column would have to change sides, which the dual re-solve cannot serve");
-    const int shifted = cnt[0];
-    info.shifted = (uint64_t)shifted;
-    info.basic = (uint64_t)cnt[1];
+    // steps 1 and 2: the classification, then the shift and the commit
+    const Moves mv = move_nonbasic(hvar, hlo, hhi, false, [&](const Moves& c) {
+        if (c.infinite)
+            throw MlpError(-1, "set_var_bounds: " + std::to_string(c.infinite) + " request(s) make infinite the bound a non-basic column sits at; the "
+                               "column would have to change sides, which the dual re-solve cannot serve");
+        cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
+    });
+    info.shifted = (uint64_t)mv.shifted;
+    info.basic = (uint64_t)mv.basic;
     info.nonbasic = n - info.basic;
-    info.bytes = 58.0 * (double)n;  // per request: variable, location, bounds, flags, value, reduced cost read; target, diff, flags written
-    // from here on the state changes
-    cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    // step 2: the shift (r = A delta, ONE FTRAN through the dense right-hand-side path, x_B -= B^-1 r) and the commit
-    ShiftBufs w;
-    if (shifted && m_ > 0) {
-        FixBufs fb{};
-        fb.var = dvar.p; fb.diff = ddiff.p; fb.n = (long)n;
-        info.bytes += shift_basic_values(fb, w);
-        info.solves = 1;
-    }
-    launch_bounds_commit(hview, b, shifted ? 1 : 0, st);
-    HIPCHECK(hipEventRecord(ev.e[1], st));
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipStreamSynchronize(st));
-    info.device_ms = ev.ms();
-    info.bytes += 41.0 * (double)n;
-    for (size_t i = 0; i < n; ++i) {
-        h_lo[hvar[i]] = hlo[i];
-        h_hi[hvar[i]] = hhi[i];
-    }
-    if (shifted) values_dirty = true;
+    info.solves = mv.solves;
+    info.bytes = mv.bytes;
+    info.device_ms = mv.device_ms;
     // step 3: ONE dual re-solve after a shift, or when a basic value now violates its bounds
     budget_exhausted = false;
-    if (shifted || (cnt[1] && !basic_values_feasible())) {
+    if (mv.shifted || (mv.basic && !basic_values_feasible())) {
         ensure_beta();  // (only in front of a re-solve: a call that moves nothing leaves every bit of the state)
         primal_feasible = false;
         restore_feasibility();
     }
-    info.pivots = stats.iterations - it0;
-    stats.solve_wall_s += now_s() - t0;
-    info.wall_ms = (now_s() - t0) * 1e3;
+    timer.finish(info.pivots, info.wall_ms);
 }
 
 uint64_t Engine::tighten_by_reduced_cost(double g, const uint8_t* var_is_int, BoundsInfo& info) {
@@ -4618,10 +4606,7 @@ uint64_t Engine::tighten_by_reduced_cost(double g, const uint8_t* var_is_int, Bo
     launch_bounds_apply_list(hview, r.b, r.count(), d_lo.p, d_hi.p, st);
     HIPCHECK(hipEventRecord(r.ev.e[1], st));
     HIPCHECK(hipGetLastError());
-    int total = 0;
-    HIPCHECK(hipMemcpyAsync(&total, r.count(), sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHECK(hipStreamSynchronize(st));
-    if (total < 0 || total > nv) throw MlpError(-3, "tighten_by_reduced_cost: the compaction returned an impossible count");
+    const int total = cutoff_read(r, "tighten_by_reduced_cost");
     if (total) bounds_mirror_stale_ = true;
     cold_start_ = false;
     info.requests = info.nonbasic = info.tightened = (uint64_t)total;
@@ -4684,23 +4669,13 @@ void Engine::propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::ve
         launch_prop_list(hview, b, r.b, cur, r.sums.p, st);
         HIPCHECK(hipEventRecord(r.ev.e[1], st));
         HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpyAsync(&total, r.count(), sizeof(int), hipMemcpyDeviceToHost, st));
-        HIPCHECK(hipStreamSynchronize(st));
-        if (total < 0 || total > nv) throw MlpError(-3, "propagate_bounds: the compaction returned an impossible count");
-        vars.resize((size_t)total); lo.resize((size_t)total); hi.resize((size_t)total);
-        if (total) {
-            HIPCHECK(hipMemcpyAsync(vars.data(), r.ovar.p, sizeof(uint32_t) * total, hipMemcpyDeviceToHost, st));
-            HIPCHECK(hipMemcpyAsync(lo.data(), r.olo.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
-            HIPCHECK(hipMemcpyAsync(hi.data(), r.ohi.p, sizeof(double) * total, hipMemcpyDeviceToHost, st));
-            HIPCHECK(hipStreamSynchronize(st));
-        }
+        total = cutoff_read(r, "propagate_bounds", &vars, &lo, &hi, &info.listed_fixed);
     } else {
         HIPCHECK(hipEventRecord(r.ev.e[1], st));
         HIPCHECK(hipGetLastError());
         HIPCHECK(hipStreamSynchronize(st));
     }
     info.listed = (uint64_t)total;
-    for (int i = 0; i < total; ++i) info.listed_fixed += lo[i] == hi[i] ? 1 : 0;
     // algorithmic bytes.  Set-up: bounds, location, flags read (21), working bounds written (16) per column.  A round: the CSR pass reads
     // 12 bytes per entry and gathers two bounds (16), and writes 24 per row; the CSC pass reads 12 per entry and gathers the row's four
     // numbers and its right-hand side (32), and reads and writes both bounds of every column (32).  The list: 36 per structural variable,

@@ -1,5 +1,5 @@
-// fixing.inc — reduced-cost bounds from a cutoff and the batched fixing of variables (include/minilp_hip.h: mlp_solution_cutoff_bounds,
-// mlp_solution_fix_vars, mlp_solution_unfix_vars; DESIGN.md §7.7).
+// fixing.inc — reduced-cost bounds from a cutoff, the batched fixing of variables and new bounds for them (include/minilp_hip.h:
+// mlp_solution_cutoff_bounds, mlp_solution_fix_vars, mlp_solution_unfix_vars, mlp_solution_set_var_bounds; DESIGN.md §7.7, §7.8).
 //
 // The read (side-effect free like ranging.inc: only the private buffers of CutoffBufs are written):
 //   k_cb_classify is ONE pass over the structural variables in tiles of BLK: location, flags, reduced cost, bounds (and, for a marked
@@ -11,17 +11,26 @@
 // Tiles ascend, places inside a tile ascend: the list is in ascending variable number whatever the grid, and bit-identical from run to
 // run.  No atomics.  Both kernels stride over the tiles with a tile index in long arithmetic: no number of variables is left out.
 //
-// The mutator (the non-basic requests of fix_vars, all served together):
-//   k_fx_diff     diff_i = val_i - xN[col_i] per request and the count of the non-zero ones (an integer count: its order is immaterial);
+// The mutators (the non-basic requests of fix_vars and every request of set_var_bounds, DESIGN.md §7.8, all served together; the host
+// sorts them by variable):
+//   k_mv_classify ONE grid-stride pass over the requests.  It writes private buffers only.  New bounds (fix = 0): a BASIC column gets no
+//                 target; a NON-BASIC column keeps its side — at lower: lo', at upper: hi', both flags (lo == hi, not fixed): lower if
+//                 d_j >= 0, else upper, no flag: clamp(xN, lo', hi') — and the new flags come from the target against lo' / hi'; a column
+//                 fixed by fix_var(s) keeps value and flags.  A fixing (fix = 1, lo == hi == the value asked for): the target is that
+//                 value whatever the flags, the flags NB_AT_MIN | NB_AT_MAX | NB_FIXED.  Either way diff = target - xN.  Three integer
+//                 counts (their order is immaterial): requests that shift, basic requests, and requests whose side has an infinite new
+//                 bound (set_var_bounds then refuses);
 //   k_fx_scatter  delta[var_i] = diff_i into a dense, zeroed delta[N] (the variables of a call are distinct: no two writes meet);
 //   k_fx_rhs      r = A delta as a pull per CSR row in storage order — the sum of a row does not depend on the order of the list —
 //                 into column 0 of the interleaved right-hand-side block of tableau.inc; launch_tab_solve then runs ONE FTRAN through
 //                 the dense right-hand-side path of every representation of B^-1;
 //   k_fx_apply    x_B -= B^-1 r;
-//   k_fx_commit   one workgroup: obj += sum diff_i d_i over the requests in ascending variable number (the host sorts them; thread t sums
-//                 the requests t, t + BLK, ... and the partial sums meet in a fixed tree), then xN = val where it moved and the flags
-//                 NB_AT_MIN | NB_AT_MAX | NB_FIXED.
+//   k_mv_commit   one workgroup: obj += sum diff_i d_i over the requests in ascending variable number (thread t sums the requests t,
+//                 t + BLK, ... and the partial sums meet in a fixed tree), then xN where it moved and the flags of the non-basic
+//                 requests; new bounds are written for every request, by variable (var_lo / var_hi) and, for a basic one, by position
+//                 (loB / hiB: the copies the pivots carry along); a fixing writes no bound;
 //   k_fx_release  unfix_vars: the flags of a released column rebuilt from its value against the bounds.
+// No float atomics; a request index is a long; no LDS beyond the reduction tree.
 
 constexpr int CB_MAX_BLOCKS = 1024;  // workgroups of the two passes of the read (they stride over the tiles beyond that)
 
@@ -101,16 +110,45 @@ void launch_cutoff_bounds(const DevView& dv, const CutoffBufs& b, int* sums, hip
     hipLaunchKernelGGL(k_cb_gather, dim3(nb), dim3(BLK), 0, st, b);
 }
 
-// ------------------------------------------------------------------- fix_vars / unfix_vars
-__global__ void __launch_bounds__(BLK) k_fx_diff(DevView v, FixBufs b) {
+// ------------------------------------------------------------------- fix_vars / set_var_bounds / unfix_vars
+__global__ void __launch_bounds__(BLK) k_mv_classify(DevView v, BoundBufs b, int fix) {
     const long step = (long)gridDim.x * BLK;
     for (long i = (long)blockIdx.x * BLK + threadIdx.x; i < b.n; i += step) {
-        const double diff = b.val[i] - v.xN[b.col[i]];
+        const int loc = v.var_loc[b.var[i]];
+        double diff = 0.0, target = 0.0;
+        uint8_t f = 0;
+        if (loc >= 0) {
+            atomicAdd(b.cnt + 1, 1);
+        } else {
+            const int col = -1 - loc;
+            const double x = v.xN[col], lo = b.lo[i], hi = b.hi[i];
+            f = v.nbflags[col];
+            target = x;
+            if (fix || !(f & NB_FIXED)) {
+                if (fix) {
+                    target = lo;  // (lo == hi: the value asked for; an already fixed column is moved)
+                } else {
+                    const bool at_min = (f & NB_AT_MIN) != 0, at_max = (f & NB_AT_MAX) != 0;
+                    const int side = at_min && at_max ? (v.d[col] >= 0.0 ? 1 : 2) : (at_min ? 1 : (at_max ? 2 : 0));
+                    if (side == 1) target = lo;
+                    else if (side == 2) target = hi;
+                    else target = fmin(fmax(x, lo), hi);
+                    if (isinf(target)) {  // the bound on the column's side is infinite: the dual path cannot serve the request
+                        atomicAdd(b.cnt + 2, 1);
+                        target = x;
+                    }
+                }
+                diff = target - x;
+                f = fix ? (uint8_t)(NB_AT_MIN | NB_AT_MAX | NB_FIXED) : (uint8_t)((target == lo ? NB_AT_MIN : 0) | (target == hi ? NB_AT_MAX : 0));
+                if (diff != 0.0) atomicAdd(b.cnt, 1);
+            }
+        }
+        b.target[i] = target;
         b.diff[i] = diff;
-        if (diff != 0.0) atomicAdd(b.nshift, 1);
+        b.flags[i] = f;
     }
 }
-__global__ void __launch_bounds__(BLK) k_fx_scatter(FixBufs b) {
+__global__ void __launch_bounds__(BLK) k_fx_scatter(BoundBufs b) {
     const long step = (long)gridDim.x * BLK;
     for (long i = (long)blockIdx.x * BLK + threadIdx.x; i < b.n; i += step) {
         const double diff = b.diff[i];
@@ -118,7 +156,7 @@ __global__ void __launch_bounds__(BLK) k_fx_scatter(FixBufs b) {
     }
 }
 template <int R>
-__global__ void __launch_bounds__(BLK) k_fx_rhs(DevView v, FixBufs b) {
+__global__ void __launch_bounds__(BLK) k_fx_rhs(DevView v, BoundBufs b) {
     const long step = (long)gridDim.x * BLK;
     for (long row = (long)blockIdx.x * BLK + threadIdx.x; row < v.m; row += step) {
         const int end = v.csr_ptr[row + 1];
@@ -128,20 +166,20 @@ __global__ void __launch_bounds__(BLK) k_fx_rhs(DevView v, FixBufs b) {
     }
 }
 template <int R>
-__global__ void __launch_bounds__(BLK) k_fx_apply(DevView v, FixBufs b) {
+__global__ void __launch_bounds__(BLK) k_fx_apply(DevView v, BoundBufs b) {
     const long step = (long)gridDim.x * BLK;
     for (long p = (long)blockIdx.x * BLK + threadIdx.x; p < v.m; p += step) {
         const double y = b.Y[(size_t)p * R];
         if (y != 0.0) v.xB[p] -= y;
     }
 }
-__global__ void __launch_bounds__(BLK) k_fx_commit(DevView v, FixBufs b, int shifted) {
+__global__ void __launch_bounds__(BLK) k_mv_commit(DevView v, BoundBufs b, int fix, int shifted) {
     __shared__ double sh[BLK];
     if (shifted) {
         double s = 0.0;
         for (long i = threadIdx.x; i < b.n; i += BLK) {
             const double diff = b.diff[i];
-            if (diff != 0.0) s += diff * v.d[b.col[i]];
+            if (diff != 0.0) s += diff * v.d[-1 - v.var_loc[b.var[i]]];
         }
         sh[threadIdx.x] = s;
         __syncthreads();
@@ -152,37 +190,49 @@ __global__ void __launch_bounds__(BLK) k_fx_commit(DevView v, FixBufs b, int shi
         if (threadIdx.x == 0) v.ctl->it.obj += sh[0];
     }
     for (long i = threadIdx.x; i < b.n; i += BLK) {
-        const int col = b.col[i];
-        if (b.diff[i] != 0.0) v.xN[col] = b.val[i];
-        v.nbflags[col] = NB_AT_MIN | NB_AT_MAX | NB_FIXED;
+        const int var = b.var[i], loc = v.var_loc[var];
+        if (!fix) {
+            const double lo = b.lo[i], hi = b.hi[i];
+            b.var_lo[var] = lo;
+            b.var_hi[var] = hi;
+            if (loc >= 0) {
+                v.loB[loc] = lo;
+                v.hiB[loc] = hi;
+            }
+        }
+        if (loc < 0) {
+            const int col = -1 - loc;
+            if (b.diff[i] != 0.0) v.xN[col] = b.target[i];
+            v.nbflags[col] = b.flags[i];
+        }
     }
 }
-__global__ void __launch_bounds__(BLK) k_fx_release(DevView v, FixBufs b) {
+__global__ void __launch_bounds__(BLK) k_fx_release(DevView v, BoundBufs b) {
     const long step = (long)gridDim.x * BLK;
     for (long i = (long)blockIdx.x * BLK + threadIdx.x; i < b.n; i += step) {
-        const int col = b.col[i], var = b.var[i];
+        const int var = b.var[i], col = -1 - v.var_loc[var];  // (the host lists non-basic columns only)
         const double cur = v.xN[col];
         v.nbflags[col] = (uint8_t)((cur == v.var_lo[var] ? NB_AT_MIN : 0) | (cur == v.var_hi[var] ? NB_AT_MAX : 0));
     }
 }
 
-void launch_fix_diff(const DevView& dv, const FixBufs& b, hipStream_t st) {
-    (void)hipMemsetAsync(b.nshift, 0, sizeof(int), st);
-    hipLaunchKernelGGL(k_fx_diff, dim3(tab_grid(b.n)), dim3(BLK), 0, st, dv, b);
+void launch_move_classify(const DevView& dv, const BoundBufs& b, int fix, hipStream_t st) {
+    (void)hipMemsetAsync(b.cnt, 0, 3 * sizeof(int), st);
+    hipLaunchKernelGGL(k_mv_classify, dim3(tab_grid(b.n)), dim3(BLK), 0, st, dv, b, fix);
 }
-void launch_fix_rhs(const DevView& dv, const FixBufs& b, int N, hipStream_t st) {
+void launch_move_commit(const DevView& dv, const BoundBufs& b, int fix, int shifted, hipStream_t st) {
+    hipLaunchKernelGGL(k_mv_commit, dim3(1), dim3(BLK), 0, st, dv, b, fix, shifted);
+}
+void launch_fix_rhs(const DevView& dv, const BoundBufs& b, int N, hipStream_t st) {
     constexpr int R = RG_BATCH;
     (void)hipMemsetAsync(b.delta, 0, sizeof(double) * (size_t)N, st);
     (void)hipMemsetAsync(b.X, 0, sizeof(double) * (size_t)dv.m * R, st);
     hipLaunchKernelGGL(k_fx_scatter, dim3(tab_grid(b.n)), dim3(BLK), 0, st, b);
     hipLaunchKernelGGL(k_fx_rhs<R>, dim3(tab_grid(dv.m)), dim3(BLK), 0, st, dv, b);
 }
-void launch_fix_apply(const DevView& dv, const FixBufs& b, hipStream_t st) {
+void launch_fix_apply(const DevView& dv, const BoundBufs& b, hipStream_t st) {
     hipLaunchKernelGGL(k_fx_apply<RG_BATCH>, dim3(tab_grid(dv.m)), dim3(BLK), 0, st, dv, b);
 }
-void launch_fix_commit(const DevView& dv, const FixBufs& b, int shifted, hipStream_t st) {
-    hipLaunchKernelGGL(k_fx_commit, dim3(1), dim3(BLK), 0, st, dv, b, shifted);
-}
-void launch_fix_release(const DevView& dv, const FixBufs& b, hipStream_t st) {
+void launch_fix_release(const DevView& dv, const BoundBufs& b, hipStream_t st) {
     hipLaunchKernelGGL(k_fx_release, dim3(tab_grid(b.n)), dim3(BLK), 0, st, dv, b);
 }

@@ -635,39 +635,30 @@ struct CutoffBufs {
 long cutoff_tiles(int nv);
 // sums: the scan's scratch, cutoff_tiles(nv) / 4096 + 2 ints; sums[ceil(cutoff_tiles(nv) / 4096)] = length of the list
 void launch_cutoff_bounds(const DevView& dv, const CutoffBufs& b, int* sums, hipStream_t st);
-// the non-basic requests of fix_vars, served together, and the released columns of unfix_vars (fixing.inc)
-struct FixBufs {
-    const int* col;     // n: non-basic position of a request (the requests in ascending variable number)
-    const int* var;     // n: its variable
-    const double* val;  // n: the value asked for
-    double* diff;       // n: val - xN
-    int* nshift;        // 1: requests with diff != 0
-    double* delta;      // N: diff by variable, 0 elsewhere
-    double* X;          // [m][RG_BATCH]: column 0 = A delta by row (the block of TabBufs)
-    const double* Y;    // [m][RG_BATCH]: column 0 = B^-1 A delta by position
-    long n;
-};
-void launch_fix_diff(const DevView& dv, const FixBufs& b, hipStream_t st);            // diff, nshift
-void launch_fix_rhs(const DevView& dv, const FixBufs& b, int N, hipStream_t st);      // delta, X (before launch_tab_solve)
-void launch_fix_apply(const DevView& dv, const FixBufs& b, hipStream_t st);           // x_B -= Y (after it)
-void launch_fix_commit(const DevView& dv, const FixBufs& b, int shifted, hipStream_t st);  // objective (if shifted), xN, flags
-void launch_fix_release(const DevView& dv, const FixBufs& b, hipStream_t st);         // flags from the value against the bounds
-// new bounds for structural variables (bounds.inc): the requests in ascending variable number; the shift itself runs through
-// launch_fix_rhs / launch_tab_solve / launch_fix_apply with a FixBufs on (var, diff)
+// the requests of fix_vars and set_var_bounds, served together, and the released columns of unfix_vars (fixing.inc): the requests in
+// ascending variable number.  A fixing passes non-basic requests only, each as lo == hi == the value asked for
 struct BoundBufs {
     const int* var;     // n: variable of a request
     const double* lo;   // n: its new bounds
     const double* hi;
     double* target;     // n: value of a non-basic request after the call
-    double* diff;       // n: target - xN (0: basic, fixed by fix_var, or already there)
+    double* diff;       // n: target - xN (0: basic, fixed by fix_var when the call sets bounds, or already there)
     uint8_t* flags;     // n: flags of a non-basic request after the call
     int* cnt;           // 3: requests with diff != 0, basic requests, requests whose side has an infinite new bound
     double* var_lo;     // N: the bounds by variable (DevView holds them read-only)
     double* var_hi;
+    double* delta;      // N: diff by variable, 0 elsewhere
+    double* X;          // [m][RG_BATCH]: column 0 = A delta by row (the block of TabBufs)
+    const double* Y;    // [m][RG_BATCH]: column 0 = B^-1 A delta by position
     long n;
 };
-void launch_bounds_classify(const DevView& dv, const BoundBufs& b, hipStream_t st);             // target, diff, flags, cnt
-void launch_bounds_commit(const DevView& dv, const BoundBufs& b, int shifted, hipStream_t st);  // objective (if shifted), xN, flags, bounds
+// fix = 1: a fixing (the target is the value asked for whatever the flags, the flags NB_AT_MIN | NB_AT_MAX | NB_FIXED, no bound is
+// written); fix = 0: new bounds (the column keeps its side; the bounds are written in all four copies)
+void launch_move_classify(const DevView& dv, const BoundBufs& b, int fix, hipStream_t st);             // target, diff, flags, cnt
+void launch_move_commit(const DevView& dv, const BoundBufs& b, int fix, int shifted, hipStream_t st);  // objective (if shifted), xN, flags, bounds
+void launch_fix_rhs(const DevView& dv, const BoundBufs& b, int N, hipStream_t st);                     // delta, X (before launch_tab_solve)
+void launch_fix_apply(const DevView& dv, const BoundBufs& b, hipStream_t st);                          // x_B -= Y (after it)
+void launch_fix_release(const DevView& dv, const BoundBufs& b, hipStream_t st);                        // var, n: flags from the value against the bounds
 // the list of launch_cutoff_bounds written to the bounds; count: its length on the device (sums[ceil(cutoff_tiles(nv) / 4096)])
 void launch_bounds_apply_list(const DevView& dv, const CutoffBufs& c, const int* count, double* var_lo, double* var_hi, hipStream_t st);
 // bound propagation from row activities (propagate.inc): Jacobi rounds of one CSR pass and one CSC pass over [A | I]; the list of the
