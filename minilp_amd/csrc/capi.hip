@@ -169,7 +169,7 @@ int mlp_problem_solve_ex(const mlp_problem* p, mlp_solution** out, int64_t budge
     *out = nullptr;
     mlp_solution* s = new mlp_solution();
     int st = guarded([&] {
-        s->eng = new Engine();
+        s->eng = new Engine(Settings::from_env());
         s->eng->pivot_budget = budget;
         s->eng->trace = flags & 1u;
         s->eng->profile = flags & 2u;
@@ -187,7 +187,7 @@ int mlp_problem_solve_from_basis(const mlp_problem* p, const void* blob, uint64_
     *out = nullptr;
     mlp_solution* s = new mlp_solution();
     int st = guarded([&] {
-        s->eng = new Engine();
+        s->eng = new Engine(Settings::from_env());
         s->eng->pivot_budget = budget;
         s->eng->trace = flags & 1u;
         s->eng->profile = flags & 2u;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "settings.h"
 
 namespace mlp {
 
@@ -147,7 +148,7 @@ struct Stats {
     uint64_t kase[5] = {0, 0, 0, 0, 0};  // partition-change cases: nuc->nuc, grow, shrink, col swap, same-row
 };
 
-// What ONE iteration launches, decided once (Engine::plan_iteration) for a (phase, DevView, Geom, environment) and read by every stage
+// What ONE iteration launches, decided once (Engine::plan_iteration) for a (phase, DevView, Geom) and read by every stage
 // (Engine::launch_stage).  Plain values; a plan is never compared and never part of a graph's key (get_graph compares Geom).
 enum class IterForm : int { Plain, PrimalHead, SmallBasis, MediumRide, LargeRide, ShardedPull, Factor };  // each one's rule: plan_iteration
 enum class FtranEntry : int { Fused, GatherLrh, PrepGather };  // head inside the gather kernel | delayed-update mode: the same | head launch + gather
@@ -171,7 +172,7 @@ struct IterPlan {
 
 class Engine {
 public:
-    Engine();
+    explicit Engine(const Settings& settings);  // Settings::from_env() for a new Solution, the parent's cfg for a clone
     ~Engine();
     Engine(const Engine&) = delete;
 
@@ -308,6 +309,7 @@ public:
     static void rccl_unique_id(void* out128);
     bool sharded() const { return shard_world > 1; }
 
+    const Settings cfg;  // every MLP_* knob, as the environment stood when the Solution was created (settings.h)
     int num_vars = 0;
     int direction = 0;
     int64_t pivot_budget = -1;
@@ -362,25 +364,17 @@ private:
     double amax_ = 0.0;                       // max |A_ij| (incl. the slack identity): scale bound of the deterministic blocked push
     bool force_det_push_ = false;             // set around recalc_basic_vals: the blocked push in its deterministic form
     bool pb_det_default = false;              // unsharded solves: deterministic blocked push by default (set from the measured A/B)
-    bool ratio_two = false;                  // MLP_RATIO_TWO_KERNELS, or latched by an ITER_STALL: two launches for the two Harris passes
-    long long ratio_spin_limit = 20000000LL; // MLP_RATIO_SPIN_LIMIT: polls before a fused ratio test gives up (0: the first launch stalls; tests)
+    bool ratio_two;                          // cfg.ratio_two, or latched by an ITER_STALL: two launches for the two Harris passes
     bool ranks_share_device = false;
-    // sparse tableau row (k_row_touch / k_row_pull) while the nucleus is small
-    int str_kmax = 230;                      // MLP_STR_K: largest nucleus the sparse form is used for (0: never)
-    int sb_kmax = 160;                       // MLP_SMALL_BASIS_K: largest nucleus (at the end of a full record ring) k_small_basis is used for; measured
-                                             // crossover with the three launches at k ~ 110-120 (tools/small_basis_curve.py)
-    bool sb_now = false;                     // ... decided per batch like str_now (the geometry is baked into the graphs)
-    // small-nucleus primal head (primal_head.inc): FTRAN + Harris test + BTRAN + inverse update + touched columns in ONE workgroup, while the
-    // nucleus stays within ph_kmax slots for the whole batch (the batch is cut short for that); MLP_PRIMAL_HEAD_K overrides the bound (0: off)
-    int ph_kmax = -1;                        // -1: primal_head_kmax(longest column)
+    // the forms of the small-nucleus iteration, decided per batch (the geometry is baked into the graphs): sparse tableau row, k_small_basis,
+    // k_primal_head (primal_head.inc: the batch is cut short so that the nucleus stays within the head's slots)
+    bool sb_now = false;
     bool ph_now = false;
     bool str_now = false, str_clean = false; // geometry of the batch being run; alpha_r / helper are zero outside touched entries
     DevBuf<int> d_ar_list;   // non-basic positions with alpha_r != 0 (dual iteration, CSC-pull tableau row): the dual Harris test walks the list
     DevBuf<int> d_str_list;
     // hypersparse single-workgroup iteration (hyper.inc)
-    int hyper_mode = -1;                     // MLP_HYPER: 1 on wherever the kernel applies, 0 off, -1 auto (<= 16 non-zeros per row on average)
-    long hyper_heavy = 0;                    // MLP_HYPER_HEAVY: eta-update entries one workgroup takes on (0: the kernel's default)
-    int hyper_backoff_max = 8;   // after bail-outs in a row the multi-kernel path keeps going for up to 2 << this pivots (swept 2..8 on config 3)
+    static constexpr int hyper_backoff_max = 8;   // after bail-outs in a row the multi-kernel path keeps going for up to 2 << this pivots (swept 2..8 on config 3)
     uint64_t hyper_off_until = 0;            // lifetime pivot count until which the multi-kernel path runs (after bail-outs)
     int hyper_bail_streak = 0;
     DevBuf<int> d_hy_stamp;                  // n + m epoch stamps (alpha_r list / singleton part of the alpha_q list) + the kernel's derived maps
@@ -389,14 +383,11 @@ private:
     bool hyper_capable(int phase) const;
     // ---- compact factor of the basis (csrc/factor.inc, HISTORY.md §2.6): B^-1 = (peeled triangular factor of the
     // basis at the last refactorisation)^-1 + at most fac_J_ additive rank-1 terms, instead of the explicit nucleus inverse
-    int fac_mode = -1;                       // MLP_FACTOR: 1 from the start (falls back to the explicit inverse when the peel leaves a bump),
-                                             // 0 never, -1 auto: tried when the nucleus would need more than fac_auto_cap_ slots
     bool fac_on_ = false;
-    int fac_J_ = 64;                         // rank-1 terms the factor has room for (MLP_FACTOR_J: room = period = that value)
-    int fac_period_ = 48;                    // pivots between refactorisations: 48, or 64 while a refactorisation is expensive (many levels, a bump)
-    bool fac_period_auto_ = true;
+    bool fac_leaving_ = false;               // inside fac_leave: its re-inversion must not switch straight back
+    int fac_J_;                              // rank-1 terms the factor has room for: cfg.fac_J, at most the solve's grid (fac_alloc)
+    int fac_period_;                         // pivots between refactorisations: cfg.fac_period; in auto 48, or 64 while a refactorisation is expensive (fac_refactor)
     int fac_nlev_ = 0;
-    int fac_auto_cap_ = 8192;                // MLP_FACTOR_FROM
     uint64_t fac_tried_at_ = 0;              // lifetime pivot count of the last attempt that found a bump
     bool fac_tried_ = false;
     DevBuf<int> d_fac_pos_of_var, d_fac_var_of_pos, d_fac_prow, d_fac_items, d_fac_lptr, d_fac_meta, d_fac_tmp, d_fac_counters;
@@ -412,15 +403,11 @@ private:
     DevBuf<double> d_fac_WbT;               // transpose of the bump inverse
     DevBuf<FacTailRec> d_fac_tprog;  // the tail of the solves as records: FTRAN | BTRAN, FAC_TAIL_CAP each
     DevBuf<int> d_fac_lev3;   // 3 m: level of a position | level of a row's pivot position | reach of a position
-    bool fac_skip_ = true;    // every solve walks only the levels its right-hand side can reach
+    static constexpr bool fac_skip_ = true;    // every solve walks only the levels its right-hand side can reach
     DevBuf<double> d_fac_Wb;   // allocated with the first bump
-    bool fac_pair_ = true;                   // the two solves of a stage share one walk over the levels
+    static constexpr bool fac_pair_ = true;  // the two solves of a stage share one walk over the levels
     int fac_bump_ = 0;
-    int fac_bump_max_ = FAC_BMAX;            // MLP_FACTOR_BUMP: largest bump the compact factor carries through its DENSE inverse
-    // sparse factor of the bump (factor_sb.inc): bumps of fac_sb_from_ .. fac_sb_max_ columns are eliminated sparsely (LU with fill in
-    // rounds of independent pivots); one whose rows outgrow their slots falls back to the dense inverse (b <= fac_bump_max_)
-    int fac_sb_max_ = FAC_SB_MAX;            // MLP_FACTOR_SB: 0 = never
-    int fac_sb_from_ = 48;                   // MLP_FACTOR_SB_FROM: smaller bumps keep the dense inverse (one wave-sized product per solve)
+    // sparse factor of the bump (factor_sb.inc)
     int fac_sb_fail_b_ = 0, fac_sb_fail_skip_ = 0;  // size of the last bump that failed the sparse elimination / refactorisations left before it is tried again
     bool fac_sb_on_ = false;                 // the current factor carries its bump sparsely
     DevBuf<int> d_fac_sb_int;                // integer scratch + outputs of the factorisation (FacSbWork)
@@ -429,17 +416,16 @@ private:
     FacSbWork fac_sb_work(int m) const;
     void fac_alloc();
     void fac_fill_view(DevView& v) const;
-    bool fac_refactor(int bump_limit = -1);  // the peel + level lists from the current basis; false when it leaves a bump beyond the limit (-1: MLP_FACTOR_BUMP)
+    bool fac_refactor(int bump_limit = -1);  // the peel + level lists from the current basis; false when it leaves a bump beyond the limit (-1: cfg.fac_bump_max)
     bool fac_enter(int bump_limit = -1);     // switch to the compact factor (false: the basis does not peel; nothing changed)
     void fac_make_room(int need);
     void fac_leave();                        // back to the explicit nucleus inverse (re-inversion from A)
     void ensure_hyper();         // sharded solve with another rank on this GPU (or unknown): same
     // Lazy dual steepest edge: the primal loop never reads beta, so its iterations skip tau = B^-1 rho (solver.rs:1157)
     // and the beta recurrence; beta is rebuilt exactly from the basis inverse (k_exact_beta) when something next needs it
-    bool lazy_dse = true;                    // MLP_LAZY_DSE=0: maintain beta in every pivot like the reference
     bool beta_stale = false;
     bool batch_lazy = false;                 // the iterations being recorded skip the beta recurrence
-    bool lazy_now(int phase) const { return lazy_dse && enable_dse && phase == 0 && !stepping && !fac_on_ && max_row_nnz_ <= HEAD_LIST_CAP; }
+    bool lazy_now(int phase) const { return cfg.lazy_dse && enable_dse && phase == 0 && !stepping && !fac_on_ && max_row_nnz_ <= HEAD_LIST_CAP; }
     void ensure_beta();
     std::vector<int> h_colnnz, h_single_row;
     std::vector<double> h_single_val;
@@ -479,20 +465,16 @@ private:
     DevBuf<double> d_pk_val;
     DevBuf<unsigned char> d_pk_valid;
     DevBuf<unsigned char> d_fmark;   // det_pull: row marks of the FTRAN pull (zero outside an FTRAN)
-    bool use_pack = true;           // MLP_SWEEP_PACKED=0: the sweep always takes the indirect path through the full copy
+    bool use_pack;                  // cfg.use_pack, until a packed copy has not fitted: then the indirect path through the full copy for good
     bool pack_built = false;
     size_t band_total_ = 0;         // entries of the band-major copy (incl. pad entries)
-    bool use_order = true;          // banded sweep in the locality order (positions sorted by the variable they hold)
+    static constexpr bool use_order = true;  // banded sweep in the locality order (positions sorted by the variable they hold)
     uint64_t order_built_at = 0;    // lifetime pivot count at the last rebuild
     uint64_t lifetime_pivots = 0;   // (stats can be reset by the caller)
-    uint64_t order_every = 2048;
     bool order_valid = false;
-    uint64_t order_from = 4096;     // pivots after which the order is switched on
-    bool order_force = false;       // (loaded bases: from the start)
+    bool order_force = false;       // the order from the first pivot instead of after cfg.order_from (loaded bases)
     void refresh_nb_order(bool force);
-    int det_mode = -1;              // MLP_DETERMINISTIC: 1 force the pulled F products, 0 never, -1 auto (<= 2^21 non-zeros)
-    int banded_mode = -1;           // MLP_BANDED: 1 force on, 0 off, -1 auto (m >= 4 bands and >= 2^22 non-zeros)
-    bool use_banded() const;
+    bool use_banded() const;        // cfg.banded_mode; auto: m >= 4 bands and >= 2^22 non-zeros (cfg.det_mode auto: <= 2^21 non-zeros)
   public:
     bool banded_active() const { return use_banded(); }
     bool factor_active() const { return fac_on_; }
@@ -504,10 +486,9 @@ private:
     DevBuf<int> d_fpk_cnt, d_fpk_var;
     DevBuf<double> d_fpk_val, d_fpk_x, d_fpk_part;
     DevBuf<unsigned char> d_fpk_in;
-    bool fpull_on_ = true;       // MLP_FPULL=0: the blocked push + k_ratio_primal_fused (A/B, tests)
     bool fpk_valid_ = false;
     uint64_t fpk_built_at_ = 0, fpk_builds_ = 0;
-    int fpk_every_ = 1024;
+    static constexpr int fpk_every_ = 1024;
     bool fpk_wanted() const;
     void fpk_rebuild();
     DevBuf<int> d_colblk;        // blocked F push (large nucleus): row-block offsets per column
@@ -515,25 +496,22 @@ private:
     bool colblk_dirty = true;
     void ensure_colblk();
     DevBuf<double> d_sdiag_of_pos, d_W, d_U, d_V, d_Ut;
-    int ld_pad = 16;    // MLP_LDPAD: extra doubles per row of a large W (row pitch = cap + pad): breaks the power-of-two stride
-    int pad_for(int cap) const { return (cap >= 8192 || force_big_tiles) ? ld_pad : 0; }
+    int pad_for(int cap) const { return (cap >= 8192 || cfg.force_big_tiles) ? cfg.ld_pad : 0; }  // row pitch of a large W = cap + pad: breaks the power-of-two stride
     int ld() const { return cap_ + pad_for(cap_); }
-    int lr_force = -1;  // MLP_LOWRANK: force the delayed-update period (0 = off); default: 32 from cap 8192
+    // delayed-update period: cfg.lr_force, or 32 from capacity 8192 on; 0 on the compact factor (Ctl.nlow counts ITS rank-1 terms)
+    int lr_period() const { return fac_on_ ? 0 : (cfg.lr_force >= 0 ? cfg.lr_force : (cap_ >= 8192 ? 32 : 0)); }
     DevBuf<double> d_work;  // alpha_q | tau | rv (2m) | hS  — one memset per batch
     DevBuf<double> d_alpha_r, d_helper;
     DevBuf<int2> d_nb_rng;
-    int sw_balanced = 1;  // MLP_STREAM_BALANCED=0: fixed 128-row strips in the streaming pass (A/B runs); N > 1: that many blocks
     int rt_device = 0;
     void acquire_runtime();  // streams, events, pinned Ctl mirror: recycled across Solutions
     void release_runtime();
-    bool force_big_tiles = false;  // MLP_BIGTILE: use the large-nucleus tiling of the fused W pass at any size (tests)
     int shard_rank = 0, shard_world = 1;
     // Round 5: DEFERRED sharding.  While the nucleus is small (the sparse-tableau-row regime, a few hundred pivots from the slack basis)
     // a pivot is 40-60 us of latency-bound launches: two or three per-pivot exchanges over xGMI can only slow it down (measured,
     // oversubscribed: 3 665 against 19 095 pivots/s).  Until the tableau row becomes a pass over A the ranks therefore run as
     // bit-identical REPLICAS — the deterministic unsharded iteration on every rank, no exchange — and the column-block sharding goes
-    // live at the first batch that leaves that regime (never back).  MLP_SHARD_DEFER=0: sharded from the first pivot (protocol tests).
-    bool shard_defer_ = true;
+    // live at the first batch that leaves that regime (never back).  cfg.shard_defer off: sharded from the first pivot (protocol tests).
     bool shard_live_ = false;
     bool shard_is_live() const { return shard_world > 1 && shard_live_; }
     MailRec* d_mail = nullptr;
@@ -543,7 +521,6 @@ private:
     void* peer_box[MAX_WORLD] = {};        // ... and the peers' boxes as mapped through HIP IPC
     int mail_fanout = 1;
     size_t xb_cap_ = 0;                    // doubles per vector slot of the exchange buffer (>= the largest possible nucleus)
-    bool no_wshard = false;                // MLP_NO_WSHARD: keep the streaming pass replicated on every rank
     void release_mailboxes();
     // pump transport (MLP_TRANSPORT=rccl | pump): the kernels post into / poll this rank's own device box; while a batch is in flight
     // the host moves the records between the ranks on a second stream: stage -> all-gather -> deliver (kernels.hip: k_mail_stage)
@@ -566,7 +543,6 @@ private:
     std::string transport = "none";        // human-readable name of the exchange transport
   private:
     size_t mail_bytes = 0;
-    double refresh_tol = 1e-7;  // re-invert W when the two-way pivot check disagrees by more than this
     DevBuf<double> d_aK, d_rK, d_tK, d_tauK, d_vK, d_klist_a, d_blist_a, d_part_tau, d_part_v;
     DevBuf<int> d_klist_s, d_blist_s;
     DevBuf<double> d_red_key, d_red_key2;
@@ -584,16 +560,13 @@ private:
     bool values_dirty = true;
 
     // --- iteration graphs: [phase][pse]
-    bool use_graph = true;
-    int batch = 32;  // (round 4: 16 -> 32: one host round trip per 32 replayed iterations; the driver's 20-pivot window is then ONE batch)
-    long final_refresh_pivots = 50000;  // MLP_FINAL_REFRESH: re-examine optimality on recomputed reduced costs after this many pivots (0 = never)
+    // (cfg.batch, round 4: 16 -> 32: one host round trip per 32 replayed iterations; the driver's 20-pivot window is then ONE batch)
     uint64_t iters_since_recalc = 0, iters_since_polish = 0;
     bool basic_values_feasible();
     bool reduced_costs_feasible();
     bool cold_start_ = true;  // the solve started from the slack basis / a loaded basis (try_new, load_basis); add_constraint, fix_var ... clear it:
                               // warm-start re-solves are short and keep the lazy capture policy
-    int graph_iters = 10;  // (round 5: 8 -> 10: the driver's 20-pivot window is two graphs) MLP_GRAPH_ITERS: iterations per graph once a geometry has run for a while (1 = off)
-    // graph slots: [0] one iteration per graph, [1] graph_iters iterations per graph (long runs)
+    // graph slots: [0] one iteration per graph, [1] cfg.graph_iters iterations per graph (long runs; round 5: 8 -> 10: the driver's 20-pivot window is two graphs)
     hipGraphExec_t gexec[2][2][2] = {};
     hipGraph_t ggraph[2][2][2] = {};
     Geom ggeom[2][2][2];

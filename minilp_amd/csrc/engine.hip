@@ -64,62 +64,16 @@ void ProblemData::add_constraint(const uint32_t* vars, const double* coeffs, uin
 }
 
 // ------------------------------------------------------------------ Engine basics
-Engine::Engine() {
+static_assert(Settings::kRing == RING && Settings::kLrMax == LR_MAX && Settings::kFacBmax == FAC_BMAX && Settings::kFacSbMax == FAC_SB_MAX &&
+                  Settings::kRlCap == RL_CAP, "settings.h clamps to the kernels' capacities");
+Engine::Engine(const Settings& settings)
+    : cfg(settings), ratio_two(settings.ratio_two), fac_J_(settings.fac_J), fac_period_(settings.fac_period), use_pack(settings.use_pack) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         throw MlpError(-4, "no HIP device visible: the simplex hot path has no CPU fallback");
     acquire_runtime();
     std::memset(h_ctl, 0, sizeof(Ctl));
     std::memset(&hview, 0, sizeof(hview));
-    const char* ng = std::getenv("MLP_NO_GRAPH");
-    use_graph = !(ng && ng[0] == '1');
-    const char* rt = std::getenv("MLP_REFRESH_TOL");
-    if (rt) refresh_tol = std::atof(rt);
-    const char* lr = std::getenv("MLP_LOWRANK");
-    if (lr) lr_force = std::max(0, std::min(LR_MAX, std::atoi(lr)));
-    const char* lp = std::getenv("MLP_LDPAD");
-    if (lp) ld_pad = std::max(0, std::min(4096, std::atoi(lp))) & ~1;
-    const char* bt = std::getenv("MLP_BIGTILE");
-    force_big_tiles = bt && std::atoi(bt) != 0;
-    const char* dm = std::getenv("MLP_DETERMINISTIC");
-    if (dm) det_mode = std::atoi(dm) != 0 ? 1 : 0;
-    const char* bd = std::getenv("MLP_BANDED");
-    if (bd) banded_mode = std::atoi(bd) != 0 ? 1 : 0;
-    const char* fr = std::getenv("MLP_FINAL_REFRESH");
-    if (fr) final_refresh_pivots = std::atol(fr);
-    if (const char* sp = std::getenv("MLP_SWEEP_PACKED")) use_pack = sp[0] != '0';
-    if (const char* of = std::getenv("MLP_ORDER_FROM")) order_from = (uint64_t)std::atoll(of);    // (tests: locality order from pivot 0,
-    if (const char* oe = std::getenv("MLP_ORDER_EVERY")) order_every = (uint64_t)std::atoll(oe);  //  rebuilt every few pivots)
-    const char* lz = std::getenv("MLP_LAZY_DSE");
-    lazy_dse = !(lz && lz[0] == '0');
-    ratio_two = std::getenv("MLP_RATIO_TWO_KERNELS") != nullptr;
-    if (const char* hy = std::getenv("MLP_HYPER")) hyper_mode = std::atoi(hy) > 0 ? 1 : 0;  // 1: whenever the kernel applies, 0: never
-    if (const char* phk = std::getenv("MLP_PRIMAL_HEAD_K")) ph_kmax = std::max(0, std::atoi(phk));
-    if (const char* sbk = std::getenv("MLP_SMALL_BASIS_K")) sb_kmax = std::max(0, std::min(256, std::atoi(sbk)));
-    if (const char* sk = std::getenv("MLP_STR_K")) str_kmax = std::atoi(sk);  // sparse tableau row up to this nucleus size (0: never)
-    if (const char* hh = std::getenv("MLP_HYPER_HEAVY")) hyper_heavy = std::atol(hh);        // work bound per iteration (tests force bail-outs)
-    if (const char* rs = std::getenv("MLP_RATIO_SPIN_LIMIT")) ratio_spin_limit = std::atoll(rs);
-    if (const char* sb = std::getenv("MLP_STREAM_BALANCED")) sw_balanced = std::atoi(sb);
-    if (const char* fm = std::getenv("MLP_FACTOR")) fac_mode = std::atoi(fm) > 0 ? 1 : 0;
-    if (const char* fj = std::getenv("MLP_FACTOR_J")) {  // a fixed period; default: 48, and 64 while a refactorisation is expensive (fac_refactor)
-        fac_J_ = fac_period_ = std::max(1, std::min(64, std::atoi(fj)));
-        fac_period_auto_ = false;
-    }
-    if (const char* ff = std::getenv("MLP_FACTOR_FROM")) fac_auto_cap_ = std::max(256, std::atoi(ff));
-    if (const char* fb = std::getenv("MLP_FACTOR_BUMP")) {  // (lowering the bump limit lowers it for both carriers of the bump)
-        const int want = std::atoi(fb);
-        fac_bump_max_ = std::max(0, std::min(FAC_BMAX, want));
-        if (want < FAC_BMAX) fac_sb_max_ = std::min(fac_sb_max_, fac_bump_max_);  // (a value at or above the dense carrier's capacity leaves the sparse carrier's limit alone)
-    }
-    if (const char* fb = std::getenv("MLP_FACTOR_SB")) fac_sb_max_ = std::max(0, std::min(FAC_SB_MAX, std::atoi(fb)));
-    if (const char* fb = std::getenv("MLP_FACTOR_SB_FROM")) fac_sb_from_ = std::max(1, std::atoi(fb));
-    if (const char* fp = std::getenv("MLP_FPULL")) fpull_on_ = fp[0] != '0';
-    const char* nws = std::getenv("MLP_NO_WSHARD");
-    no_wshard = nws && std::atoi(nws) != 0;
-    const char* bs = std::getenv("MLP_BATCH");
-    if (bs) batch = std::max(1, std::min(RING, std::atoi(bs)));
-    const char* gi = std::getenv("MLP_GRAPH_ITERS");
-    if (gi) graph_iters = std::max(1, std::min(32, std::atoi(gi)));
 }
 // ------------------------------------------------------------------ per-Solution runtime objects
 // Two streams, six events and the pinned Ctl mirror cost 4-5 ms to create and 3 ms to destroy; the
@@ -310,25 +264,29 @@ void Engine::drop_graphs() {
 
 static constexpr size_t kMailBoxBytesPerRank = sizeof(MailRec) * 2 * MAIL_KINDS;
 Geom Engine::geom() const {
-    Geom g;
+    Geom g{};  // (compared with memcmp: get_graph)
     g.m = m_;
     g.n = num_vars;
     g.cap = cap_;
     double avg = num_vars > 0 ? (double)(h_rcol.size() - (size_t)m_) / (double)num_vars : 1.0;  // structural columns
     g.lanes = avg >= 40.0 ? 64 : (avg >= 6.0 ? 16 : 4);
     g.sweep_one = avg < 3.0 ? 1 : 0;  // (the 400 000-column transport solve 15.63 s against 15.82-15.95 with four lanes per two-entry column)
-    g.big = (cap_ > 4096 || force_big_tiles) ? 1 : 0;
-    const int lr = lr_force >= 0 ? lr_force : (cap_ >= 8192 ? 32 : 0);  // as in sync_view
-    g.head_fused = (!fac_on_ && lr == 0 && max_col_nnz_ <= HEAD_LIST_CAP && max_row_nnz_ <= HEAD_LIST_CAP) ? 1 : 0;
+    g.big = (cap_ > 4096 || cfg.force_big_tiles) ? 1 : 0;
+    g.head_fused = (!fac_on_ && lr_period() == 0 && max_col_nnz_ <= HEAD_LIST_CAP && max_row_nnz_ <= HEAD_LIST_CAP) ? 1 : 0;
     g.fac = fac_on_ ? 1 : 0;
     // in-kernel wait between the two Harris passes: never while the ranks of a sharded solve share a device (their grids
     // compete for the same CUs), never again after a wait has timed out once
     g.ratio_two = (ratio_two || (shard_world > 1 && ranks_share_device)) ? 1 : 0;
-    g.ratio_list = ratio_spin_limit > 0 ? 1 : 0;  // (a spin limit of 0 is the test hook that makes the in-kernel wait give up: the wait then has to run)
+    g.ratio_list = cfg.ratio_spin_limit > 0 ? 1 : 0;  // (a spin limit of 0 is the test hook that makes the in-kernel wait give up: the wait then has to run)
     g.str = (str_now && !stepping && !fac_on_) ? 1 : 0;
     g.sb = (g.str && sb_now) ? 1 : 0;
     g.ph = (g.str && ph_now) ? 1 : 0;
     g.fp = hview.fpk_on ? 1 : 0;
+    g.forms = (cfg.ratio_one ? FORM_RATIO_ONE : 0u) | (cfg.tk_ride ? FORM_TK_RIDE : 0u) | (cfg.ratio_list ? FORM_RATIO_LIST : 0u) |
+              (cfg.btran_ride ? FORM_BTRAN_RIDE : 0u) | (cfg.v_ride ? FORM_V_RIDE : 0u) | (cfg.small_basis ? FORM_SMALL_BASIS : 0u) |
+              (cfg.primal_head ? FORM_PRIMAL_HEAD : 0u) | (cfg.rk_ride ? FORM_RK_RIDE : 0u) | (cfg.pull_inside ? FORM_PULL_INSIDE : 0u) |
+              (cfg.head_apply ? FORM_HEAD_APPLY : 0u);
+    g.rl_cap = cfg.ratio_list_cap;
     return g;
 }
 
@@ -336,8 +294,8 @@ Geom Engine::geom() const {
 // [b * BAND_ROWS, (b + 1) * BAND_ROWS) with 16-bit local row indices.  Columns hold ascending rows, so the
 // entries of (column, band) are a contiguous run of the plain CSC.
 bool Engine::use_banded() const {
-    if (banded_mode == 0) return false;
-    if (banded_mode == 1) return true;
+    if (cfg.banded_mode == 0) return false;
+    if (cfg.banded_mode == 1) return true;
     return m_ >= 4 * BAND_ROWS && h_rcol.size() >= ((size_t)1 << 22);
 }
 void Engine::ensure_banded() {
@@ -364,7 +322,7 @@ void Engine::ensure_banded() {
 }
 
 void Engine::refresh_nb_order(bool force) {
-    if (!force && (!order_valid || lifetime_pivots - order_built_at < order_every)) return;
+    if (!force && (!order_valid || lifetime_pivots - order_built_at < cfg.order_every)) return;
     std::vector<int> ord;
     ord.reserve((size_t)num_vars);
     for (int var = 0; var < N_; ++var)  // ascending variables = storage order of the band-major copy
@@ -423,10 +381,9 @@ void Engine::ensure_colblk() {
 
 // Pulled F product (fpull.inc): wanted wherever the blocked push in its float-atomic form serves the unsharded delayed-update mode
 bool Engine::fpk_wanted() const {
-    const int lr = fac_on_ ? 0 : (lr_force >= 0 ? lr_force : (cap_ >= 8192 ? 32 : 0));
     // (sharded solves too: the pull is replicated on every rank like the rest of the FTRAN, and — a fixed summation order — it keeps the ranks
     // bit-identical replicas without the fixed-point limbs of the deterministic push)
-    return fpull_on_ && !fac_on_ && !stepping && lr > 0 && enable_pse && d_rowinfo.p != nullptr;
+    return cfg.fpull && !fac_on_ && !stepping && lr_period() > 0 && enable_pse && d_rowinfo.p != nullptr;
 }
 // (Re)build the row-major packed copy of the nucleus columns from the CSR of A and the device's CURRENT maps, on the device, in one
 // pass (~30 us on config 4: 10^7 entries read once); alpha_K by variable starts from zero.  Called between batches: at the first batch
@@ -480,14 +437,13 @@ DevView* Engine::sync_view() {
     // hence independent of the order in which they land), so a sharded solve no longer needs the pull for a nucleus beyond a
     // few hundred columns: it takes the blocked push from capacity 512 on (below that the marked pull touches few rows and
     // is cheaper than the push's fixed cost).  MLP_PB_DET=1 / 0 forces the deterministic form on / off for unsharded solves.
-    static const int pb_det_env = std::getenv("MLP_PB_DET") ? std::atoi(std::getenv("MLP_PB_DET")) : -1;
     int hbits = 1;
     while (hbits < 31 && (1 << hbits) <= max_row_nnz_) hbits += 1;  // terms one accumulator can receive: < 2^hbits
     const bool det_fits = hbits <= 20;
-    const bool pb_det = det_fits && (shard_det || force_det_push_ || pb_det_env == 1 || (pb_det_env < 0 && pb_det_default));
+    const bool pb_det = det_fits && (shard_det || force_det_push_ || cfg.pb_det == 1 || (cfg.pb_det < 0 && pb_det_default));
     // (small models take the pull sharded or not — MLP_DETERMINISTIC auto — so that their sharded and unsharded runs stay bit-identical)
-    const bool pb_size = cap_ > 4096 || force_big_tiles ||
-                         (shard_det && pb_det && cap_ >= 512 && det_mode != 1 && h_rcol.size() > ((size_t)1 << 21));
+    const bool pb_size = cap_ > 4096 || cfg.force_big_tiles ||
+                         (shard_det && pb_det && cap_ >= 512 && cfg.det_mode != 1 && h_rcol.size() > ((size_t)1 << 21));
     v.pb_on = (pb_size && (!shard_det || pb_det)) ? 1 : 0;
     v.pb_det = (v.pb_on && pb_det) ? 1 : 0;
     v.pb_hbits = hbits;
@@ -505,7 +461,7 @@ DevView* Engine::sync_view() {
         v.fpk_x = fp ? d_fpk_x.p : nullptr; v.fpk_part = d_fpk_part.p;
         v.fpk_on = fp ? 1 : 0; v.pad5 = 0;
     }
-    v.det_pull = (!v.pb_on && (det_mode == 1 || shard_det || force_det_push_ || (det_mode < 0 && h_rcol.size() <= ((size_t)1 << 21)))) ? 1 : 0;
+    v.det_pull = (!v.pb_on && (cfg.det_mode == 1 || shard_det || force_det_push_ || (cfg.det_mode < 0 && h_rcol.size() <= ((size_t)1 << 21)))) ? 1 : 0;
     if (v.det_pull) {  // (a pooled block is not zero: cleared whenever the allocation changes; the pull clears what it consumes)
         const unsigned char* before = d_fmark.p;
         d_fmark.ensure((size_t)m_ + 64, 0, st);
@@ -523,7 +479,7 @@ DevView* Engine::sync_view() {
     v.nbands = (m_ + BAND_ROWS - 1) / BAND_ROWS;
     // (while the non-basic positions still hold their original variables the plain position order IS the locality
     // order and the indirection only costs: 96.9 vs 95.1 us per pivot in the benchmark window)
-    if (v.banded && use_order && shard_world == 1 && (lifetime_pivots >= order_from || order_force)) {
+    if (v.banded && use_order && shard_world == 1 && (lifetime_pivots >= cfg.order_from || order_force)) {
         if (!order_valid || (use_pack && !pack_built)) refresh_nb_order(true);
         v.nb_order = d_nb_order.p;
     } else {
@@ -538,7 +494,7 @@ DevView* Engine::sync_view() {
     // (16 up to cap 16 384 in round 1: 304 vs 296 us per pivot at k = 10 000).  A period of 64 was measured in round 3 at
     // k = 20 500: the fused fold REPLACES that pivot's streaming pass, so its net cost is (1 338 - 479) / 32 = 27 us per pivot
     // and a period of 64 could save 13 of them at best; the 64-term kernel (occupancy 2) took 3.2 ms: 716 vs 695 us per pivot
-    v.lrJ = fac_on_ ? 0 : (lr_force >= 0 ? lr_force : (cap_ >= 8192 ? 32 : 0));  // (compact factor: Ctl.nlow counts ITS rank-1 terms)
+    v.lrJ = lr_period();
     v.alpha_q = d_work.p;
     v.tau = d_work.p + (size_t)m_;
     v.rv = reinterpret_cast<double2*>(d_work.p + 2 * (size_t)m_);
@@ -572,15 +528,15 @@ DevView* Engine::sync_view() {
     {   // exchange buffers of the row-sharded streaming pass (peer transport, large-nucleus delayed-update mode only)
         const size_t mb = kMailBoxBytesPerRank * (size_t)std::max(shard_world, 1);
         v.wshard = (live && mail_fanout > 1 && own_box && v.lrJ > 0 && geom().big &&
-                    !no_wshard && (size_t)cap_ <= xb_cap_) ? 1 : 0;
+                    !cfg.no_wshard && (size_t)cap_ <= xb_cap_) ? 1 : 0;
         v.xbuf = own_box ? reinterpret_cast<double*>(static_cast<uint8_t*>(own_box) + mb) : nullptr;
         for (int r = 0; r < MAX_WORLD; ++r)
             v.xbuf_peer[r] = peer_box[r] ? reinterpret_cast<double*>(static_cast<uint8_t*>(peer_box[r]) + mb) : nullptr;
         v.xb_cap = (int)xb_cap_; v.pad3 = 0;
     }
     v.sw_nbal = 0; v.sw_pad = 0;
-    if (sw_balanced && v.lrJ > 0 && geom().big)
-        v.sw_nbal = sw_balanced > 1 ? sw_balanced : stream_coresident_blocks();
+    if (cfg.sw_balanced && v.lrJ > 0 && geom().big)
+        v.sw_nbal = cfg.sw_balanced > 1 ? cfg.sw_balanced : stream_coresident_blocks();
     v.nb_lo = live ? (int)((long)num_vars * shard_rank / shard_world) : 0;
     v.nb_hi = live ? (int)((long)num_vars * (shard_rank + 1) / shard_world) : num_vars;
     if (std::memcmp(&old, &hview, sizeof(DevView)) != 0) {
@@ -652,11 +608,11 @@ void Engine::ensure_nucleus_cap(int need) {
     if (need > m_) need = m_;  // the nucleus can never exceed the number of rows
     if (need <= cap_) return;
     // Selection of the second representation by the MEASURED shape of the basis: before the explicit inverse
-    // grows past fac_auto_cap_ slots (8 k^2 bytes, O(k^2) traffic per pivot), peel the current basis; if the peel consumes
+    // grows past cfg.fac_auto_cap slots (8 k^2 bytes, O(k^2) traffic per pivot), peel the current basis; if the peel consumes
     // every column (no bump: the LU of this basis has no fill) the solve continues on the compact factor.  A basis that does
     // not peel (config 4: a random sparse nucleus fills to dense) keeps the explicit inverse; the attempt is repeated only
     // after the nucleus has doubled again.
-    if (fac_mode < 0 && need > fac_auto_cap_ && fac_allowed_under_sharding() && !stepping && d_ctl.p && k_ > 0 &&
+    if (cfg.fac_mode < 0 && !fac_leaving_ && need > cfg.fac_auto_cap && fac_allowed_under_sharding() && !stepping && d_ctl.p && k_ > 0 &&
         (!fac_tried_ || cap_ >= 2 * (int)fac_tried_at_)) {
         fac_tried_ = true;
         fac_tried_at_ = (uint64_t)std::max(cap_, 1);
@@ -958,10 +914,7 @@ void Engine::golive_check() {
     uint64_t ob = 0;
     std::memcpy(&ob, &obj, sizeof(ob));
     uint64_t fp[4] = {(uint64_t)lifetime_pivots, (uint64_t)(int64_t)k_, h, ob};
-    {   // test hook: MLP_TEST_GOLIVE_SKEW=<rank> makes that rank publish a perturbed fingerprint (tests/test_dist_gpu.py)
-        const char* sk = std::getenv("MLP_TEST_GOLIVE_SKEW");
-        if (sk && std::atoi(sk) == shard_rank) fp[2] ^= 1ull;
-    }
+    if (cfg.golive_skew == shard_rank) fp[2] ^= 1ull;  // test hook: that rank publishes a perturbed fingerprint (tests/test_dist_gpu.py)
     Rendezvous* mine = rv + shard_rank;
     const uint64_t seq = ++golive_seq_;
     for (int j = 0; j < 4; ++j) mine->fp[j] = fp[j];
@@ -1031,8 +984,7 @@ void Engine::pump_until_idle() {
         bool all = false;
         pump_round(q == hipSuccess, &all);
         if (all) break;
-        static const bool dbg = std::getenv("MLP_PUMP_DEBUG") != nullptr;
-        if (dbg && now_s() - t0 > next_report) {
+        if (cfg.pump_debug && now_s() - t0 > next_report) {
             next_report += 1.0;
             std::fprintf(stderr, "[mlp pump] rank %d seq %llu: %.1f s, %llu rounds so far, local stream %s, words", shard_rank, pump_seq_, now_s() - t0,
                          (unsigned long long)pump_rounds_, q == hipSuccess ? "idle" : "busy");
@@ -1086,7 +1038,7 @@ void Engine::enable_sharding(int rank, int world, const char* shm_name, const ch
     const bool had_factor = fac_on_;
     release_mailboxes();
     std::string tname = transport_name ? transport_name : "";
-    if (tname.empty() && std::getenv("MLP_TRANSPORT")) tname = std::getenv("MLP_TRANSPORT");
+    if (tname.empty()) tname = cfg.transport;
     const int pump = tname == "rccl" ? 1 : (tname == "pump" ? 2 : 0);
     if (!tname.empty() && !pump && tname != "peer" && tname != "host")
         throw MlpError(-1, "enable_sharding: unknown transport '" + tname + "' (peer, host, rccl, pump)");
@@ -1237,9 +1189,7 @@ void Engine::enable_sharding(int rank, int world, const char* shm_name, const ch
     // device side by side, or their grid barriers wait for workgroups that cannot start (factor.inc: fac_solve_set_sharers)
     if (world > 1 && ranks_share_device && fac_allowed_under_sharding()) fac_solve_set_sharers(world);
     {   // deferred sharding (engine.h): replicas until the tableau row becomes a pass over A; MLP_SHARD_DEFER=0 shards from the first pivot
-        const char* sd = std::getenv("MLP_SHARD_DEFER");
-        shard_defer_ = !(sd && sd[0] == '0');
-        shard_live_ = !(shard_defer_ && world > 1 && !pump_backend_);
+        shard_live_ = !(cfg.shard_defer && world > 1 && !pump_backend_);
         view_dirty = true;
     }
 }
@@ -1387,8 +1337,8 @@ void Engine::try_new(const ProblemData& pd) {
     h_ctl->it.obj = cur_obj;
     h_ctl->it.status = ITER_NONE;
     h_ctl->up.kase = -1;
-    h_ctl->ratio_spin_limit = ratio_spin_limit;
-    h_ctl->kprof_on = std::getenv("MLP_KPROF") ? std::atoi(std::getenv("MLP_KPROF")) : 0;  // 1: kernel timeline marks; 2..5: per-rank quantity in the records (diagnostics)
+    h_ctl->ratio_spin_limit = cfg.ratio_spin_limit;
+    h_ctl->kprof_on = cfg.kprof;  // 1: kernel timeline marks; 2..5: per-rank quantity in the records (diagnostics)
     HIPCHECK(hipMemcpyAsync(d_ctl.p, h_ctl, sizeof(Ctl), hipMemcpyHostToDevice, st));
     ensure_nucleus_cap(256);
     push_maps();
@@ -1396,7 +1346,7 @@ void Engine::try_new(const ProblemData& pd) {
     launch_init_nb_rng(hview, geom(), st);
     HIPCHECK(hipStreamSynchronize(st));
     values_dirty = true;
-    if (fac_mode == 1 && m_ > 0) (void)fac_enter();  // MLP_FACTOR=1: the compact factor from the slack basis on (one level)
+    if (cfg.fac_mode == 1 && m_ > 0) (void)fac_enter();  // MLP_FACTOR=1: the compact factor from the slack basis on (one level)
 }
 
 // ------------------------------------------------------------------ values / objective
@@ -1433,7 +1383,7 @@ double Engine::cur_obj_val() {
 //   dual  : BTRAN -> ROW -> RATIO (+ FTRAN head) -> FTRAN (+ plan) -> BASIS -> APPLY
 static const int kStageOrder[2][6] = {{STAGE_FTRAN, STAGE_RATIO, STAGE_BTRAN, STAGE_BASIS, STAGE_ROW, STAGE_APPLY},
                                       {STAGE_BTRAN, STAGE_ROW, STAGE_RATIO, STAGE_FTRAN, STAGE_BASIS, STAGE_APPLY}};
-// The launches of one iteration, decided ONCE for the current view, geometry and environment: the only place where the launch predicates
+// The launches of one iteration, decided ONCE for the current view and geometry: the only place where the launch predicates
 // of kernels.h are combined.  The stages below read the plan; nothing they launch reports back.
 IterPlan Engine::plan_iteration(int phase) const {
     const DevView& dv = hview;
@@ -1449,10 +1399,8 @@ IterPlan Engine::plan_iteration(int phase) const {
         // A dual iteration without primal steepest edge, run whole (not stepped): the three single-purpose launches around the solves —
         // the leaving row's scalars, the plan after the FTRAN, the new rank-1 term — ride inside the solves (16.8 us of 170 per pivot on the
         // 200 000-row transport instance, profiles/r05c_transport_first60k_kernel_stats.csv); bit-identical (MLP_FACTOR_FUSE=0: A/B, tests)
-        static const bool fuse_env = !(std::getenv("MLP_FACTOR_FUSE") && std::getenv("MLP_FACTOR_FUSE")[0] == '0');
-        static const bool rho_part_env = !(std::getenv("MLP_FACTOR_RHO_PART") && std::getenv("MLP_FACTOR_RHO_PART")[0] == '0');
-        pl.fac_pair = fac_pair_ ? 1 : 0, pl.fac_rho_part = rho_part_env ? 1 : 0;
-        pl.fac_fused = (fuse_env && phase == 1 && !pse && pl.dse && fac_pair_ && !stepping) ? 1 : 0;
+        pl.fac_pair = fac_pair_ ? 1 : 0, pl.fac_rho_part = cfg.fac_rho_part ? 1 : 0;
+        pl.fac_fused = (cfg.fac_fuse && phase == 1 && !pse && pl.dse && fac_pair_ && !stepping) ? 1 : 0;
         return pl;
     }
     const bool lazy = lazy_now(phase);                       // primal iteration: no tau, no beta update (ensure_beta() later)
@@ -1627,15 +1575,11 @@ void Engine::launch_stage(const IterPlan& pl, int stage, bool with_events) {
         throw MlpError(-1, "unknown stage");
     }
 }
-static bool use_graph_env() {
-    const char* ng = std::getenv("MLP_NO_GRAPH");
-    return !(ng && ng[0] == '1');
-}
 void Engine::record_iteration(const IterPlan& pl, bool with_events) {
     if (with_events) HIPCHECK(hipEventRecord(ev[8], st));
     // MLP_DEBUG_SYNC=1 with MLP_NO_GRAPH=1 (eager launches): synchronise after every stage and name it — a device fault is then
     // reported at the stage it belongs to
-    static const bool debug_sync = std::getenv("MLP_DEBUG_SYNC") != nullptr && !use_graph_env();
+    const bool debug_sync = cfg.debug_sync && !cfg.use_graph;
     for (int i = 0; i < 6; ++i) {
         launch_stage(pl, kStageOrder[pl.phase][i], with_events);
         if (debug_sync) {
@@ -1775,7 +1719,7 @@ hipGraphExec_t Engine::get_graph(int phase, int multi) {
     HIPCHECK(hipStreamSynchronize(st2));
     HIPCHECK(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     try {
-        const int iters = multi ? graph_iters : 1;
+        const int iters = multi ? cfg.graph_iters : 1;
         const IterPlan pl = plan_iteration(phase);  // one plan per capture
         for (int i = 0; i < iters; ++i) record_iteration(pl, false);
     } catch (...) {
@@ -1832,10 +1776,10 @@ int Engine::process_records() {
     }
     return result;
 }
-// drift monitor: the pivot element from FTRAN and from the tableau row must agree; re-invert when they disagree by more than refresh_tol
+// drift monitor: the pivot element from FTRAN and from the tableau row must agree; re-invert when they disagree by more than cfg.refresh_tol
 void Engine::watch_drift(bool pivoted) {
     if (h_ctl->max_pivot_err > stats.max_pivot_err) stats.max_pivot_err = h_ctl->max_pivot_err;
-    if (pivoted && !(h_ctl->max_pivot_err <= refresh_tol) && (k_ > 0 || fac_on_)) rebuild_inverse();
+    if (pivoted && !(h_ctl->max_pivot_err <= cfg.refresh_tol) && (k_ > 0 || fac_on_)) rebuild_inverse();
 }
 
 int Engine::run_loop(int phase) {
@@ -1851,15 +1795,15 @@ int Engine::run_loop(int phase) {
         }
         // profile mode: every 8th batch is ONE eager iteration bracketed by HIP events on the
         // launch stream (sweep and fused pass), the others are graph replays as usual
-        const bool long_run = use_graph && graph_iters > 1 && graph_batches_in_geom >= 8;
+        const bool long_run = cfg.use_graph && cfg.graph_iters > 1 && graph_batches_in_geom >= 8;
         const bool sample = profile && (sample_every == 1 || batches_run % (long_run ? 4 : 8) == 0);
         batches_run += 1;
         // Capturing a graph costs milliseconds and is invalidated by every add_constraint (m changes),
         // so short warm-start re-solves run eagerly; the graph is captured once the same geometry has
         // survived a few iterations.
-        if (!hview.nb_order && use_order && lifetime_pivots >= order_from) view_dirty = true;  // time to switch the order on
+        if (!hview.nb_order && use_order && lifetime_pivots >= cfg.order_from) view_dirty = true;  // time to switch the order on
         sync_view();
-        if (hview.nb_order) refresh_nb_order(false);  // every `order_every` pivots (same buffer: captured graphs stay valid)
+        if (hview.nb_order) refresh_nb_order(false);  // every `cfg.order_every` pivots (same buffer: captured graphs stay valid)
         if (hview.nb_order && use_pack && pack_built != (hview.pk_ptr != nullptr)) {  // the packed copy came or went
             view_dirty = true;
             sync_view();
@@ -1885,7 +1829,7 @@ int Engine::run_loop(int phase) {
             sync_view();
             launch_reset_ring(hview, st);
             launch_clear_work(hview, st);
-            launch_hyper_dual(hview, enable_dse ? 1 : 0, B, hyper_heavy, st);
+            launch_hyper_dual(hview, enable_dse ? 1 : 0, B, cfg.hyper_heavy, cfg.hyper_prof ? 1 : 0, st);
             str_clean = false;  // (the kernel writes alpha_r on its touched columns without zeroing them)
             pull_ctl();
             const uint64_t before = stats.iterations;
@@ -1919,7 +1863,7 @@ int Engine::run_loop(int phase) {
         // kernel) in between leaves them dirty.
         {
             // (sharded solves too: a rank lists and pulls the touched columns of its own block of non-basic positions)
-            const bool want = str_kmax > 0 && !stepping && !fac_on_ && k_ + RING + 1 <= str_kmax && max_row_nnz_ <= 4096;
+            const bool want = cfg.str_kmax > 0 && !stepping && !fac_on_ && k_ + RING + 1 <= cfg.str_kmax && max_row_nnz_ <= 4096;
             if (want != str_now) {
                 str_now = want;
                 view_dirty = true;
@@ -1927,11 +1871,11 @@ int Engine::run_loop(int phase) {
             // (one workgroup walks all of W in k_small_basis: it pays while the nucleus is small — per pivot of config 4 from the
             // slack basis 55-57 us against 60-62 up to k = 72, 67.0 against 68.8 at k = 104, 78.9 against 77.9 at k = 120, 105
             // against 98 at k = 135 (tools/small_basis_curve.py) — so the form is chosen per batch by the size the nucleus can reach)
-            sb_now = want && k_ + RING + 1 <= sb_kmax;
-            if (shard_world > 1 && !shard_live_ && !(shard_defer_ && want && !pump_backend_)) {
+            sb_now = want && k_ + RING + 1 <= cfg.sb_kmax;
+            if (shard_world > 1 && !shard_live_ && !(cfg.shard_defer && want && !pump_backend_)) {
                 // the column-block sharding goes live (every rank takes this decision at the same pivot: k_ is replicated) — after the
                 // ranks have shown each other that they ARE the same replica (golive_check throws on every rank otherwise)
-                if (shard_defer_) golive_check();
+                if (cfg.shard_defer) golive_check();
                 shard_live_ = true;
                 view_dirty = true;
             }
@@ -1955,7 +1899,7 @@ int Engine::run_loop(int phase) {
         const bool brief = hyper_gap > 0 && hyper_gap <= 4;
         // (pump transports launch eagerly: measured on the test box, a replayed graph keeps the pump's second stream from making
         // progress until the graph has drained — its kernels then wait for records that cannot arrive)
-        const bool graph_now = use_graph && !pump_backend_ && !sample && !brief && (have_graph || eager_iters_in_geom >= 4);
+        const bool graph_now = cfg.use_graph && !pump_backend_ && !sample && !brief && (have_graph || eager_iters_in_geom >= 4);
         if (!have_graph && !brief) eager_iters_in_geom += 1;
         // long runs move on to graphs of several iterations and batches of a full record ring: one
         // launch and one host round trip cover more pivots (6 990 -> 7 300 pivots/s on config 4); short
@@ -1965,12 +1909,12 @@ int Engine::run_loop(int phase) {
         // kernels per pivot, 43 us per pivot on the clock), between two kernels of one graph ~1.4)
         // (second session of round 5: the compact factor too — a batch between two refactorisations is 32 or 64 pivots, three to six graphs
         // of ten iterations instead of one graph launch, and ~8 us of idle device, per pivot)
-        const bool multi = graph_now && (long_run || cold_start_) && graph_iters > 1;
-        int B = graph_now ? (multi ? RING : batch) : 1;
+        const bool multi = graph_now && (long_run || cold_start_) && cfg.graph_iters > 1;
+        int B = graph_now ? (multi ? RING : cfg.batch) : 1;
         if (pivot_budget > 0 && (int64_t)B > pivot_budget) B = (int)pivot_budget;
         if (hyper_gap > 0 && B > hyper_gap) B = hyper_gap;
         {   // small-nucleus primal head: the batch must end before the nucleus can outgrow the kernel's slots
-            const int kmax = std::min(ph_kmax >= 0 ? ph_kmax : primal_head_kmax(std::max(max_col_nnz_, 1)), primal_head_kmax(std::max(max_col_nnz_, 1)));
+            const int kmax = std::min(cfg.ph_kmax >= 0 ? cfg.ph_kmax : primal_head_kmax(std::max(max_col_nnz_, 1)), primal_head_kmax(std::max(max_col_nnz_, 1)));
             bool ph = str_now && phase == 0 && enable_pse && batch_lazy && shard_world == 1 && !stepping && !fac_on_ && kmax > 0 &&
                       max_row_nnz_ <= HEAD_LIST_CAP && !hview.pb_on && !hview.det_pull && hview.rowinfo != nullptr;
             if (ph) {
@@ -2006,11 +1950,11 @@ int Engine::run_loop(int phase) {
         if (phase == 0) launch_price_primal(dv, geom(), enable_pse ? 1 : 0, st);  // opens the first iteration
         else launch_price_dual(dv, geom(), enable_dse ? 1 : 0, st);
         if (graph_now) {
-            const int nfull = multi ? B / graph_iters : 0;  // whole multi-iteration graphs first, the remainder of the batch as one-iteration graphs
+            const int nfull = multi ? B / cfg.graph_iters : 0;  // whole multi-iteration graphs first, the remainder of the batch as one-iteration graphs
             hipGraphExec_t gm = (multi && (nfull > 0 || cold_start_)) ? get_graph(phase, 1) : nullptr;  // (cold solve: captured ahead of its first use)
-            hipGraphExec_t g1 = (B - nfull * graph_iters > 0 || !gm) ? get_graph(phase, 0) : nullptr;
+            hipGraphExec_t g1 = (B - nfull * cfg.graph_iters > 0 || !gm) ? get_graph(phase, 0) : nullptr;
             for (int i = 0; i < nfull; ++i) HIPCHECK(hipGraphLaunch(gm, st));
-            for (int i = nfull * graph_iters; i < B; ++i) HIPCHECK(hipGraphLaunch(g1, st));
+            for (int i = nfull * cfg.graph_iters; i < B; ++i) HIPCHECK(hipGraphLaunch(g1, st));
             graph_batches_in_geom += 1;
         } else {
             if (sample)
@@ -2106,13 +2050,13 @@ void Engine::ensure_beta() {
 // row / column short enough for the in-kernel stage heads.  auto: models with few non-zeros per row (the regime where the
 // multi-kernel iteration loses to reach-restricted CPU work); MLP_HYPER=1 / 0 force it on (where it applies) / off.
 bool Engine::hyper_capable(int phase) const {
-    if (hyper_mode == 0 || phase != 1 || enable_pse || shard_world != 1 || stepping || fac_on_) return false;
-    if ((lr_force >= 0 ? lr_force : (cap_ >= 8192 ? 32 : 0)) != 0 || use_banded()) return false;
+    if (cfg.hyper_mode == 0 || phase != 1 || enable_pse || shard_world != 1 || stepping || fac_on_) return false;
+    if (lr_period() != 0 || use_banded()) return false;
     if (cap_ > 4096) return false;  // (the kernel's dense passes over the nucleus slots hold HY_KU = 8 elements per thread: 4 096 slots)
     // the launch reserves capacity for k_ + RING + 1 slots first (ensure_nucleus_cap): that must not double a 4 096-slot W
     if (std::min(k_ + RING + 1, std::max(m_, 1)) > 4096) return false;
     if (max_col_nnz_ > HEAD_LIST_CAP || max_row_nnz_ > HEAD_LIST_CAP) return false;
-    if (hyper_mode == 1) return true;
+    if (cfg.hyper_mode == 1) return true;
     // few non-zeros per row OR per column (the TSP relaxations of config 5: 129 per degree row, 2 + cuts per column)
     return m_ > 0 && (double)h_rcol.size() <= 16.0 * (double)std::max(m_, num_vars);
 }
@@ -2232,7 +2176,7 @@ bool Engine::fac_refactor(int bump_limit) {
     HIPCHECK(hipStreamSynchronize(st));
     if (m_ <= 0) return false;
     const bool explicit_limit = bump_limit >= 0;
-    if (bump_limit < 0) bump_limit = fac_bump_max_;
+    if (bump_limit < 0) bump_limit = cfg.fac_bump_max;
     fac_alloc();
     sync_view();
     DevView t = hview;  // (also used to probe while the explicit inverse is still the representation in use)
@@ -2315,8 +2259,8 @@ bool Engine::fac_refactor(int bump_limit) {
         fac_sb_fail_skip_ -= 1;
         stats.fac_sb_skipped += 1;
     }
-    const bool sb_try = b > 0 && b >= fac_sb_from_ && b <= fac_sb_max_ && !sb_blocked;
-    if (b > (explicit_limit ? bump_limit : std::max(bump_limit, fac_sb_max_))) return false;
+    const bool sb_try = b > 0 && b >= cfg.fac_sb_from && b <= cfg.fac_sb_max && !sb_blocked;
+    if (b > (explicit_limit ? bump_limit : std::max(bump_limit, cfg.fac_sb_max))) return false;
     bool sb_now = false;
     if (b > 0 || fac_bump_ > 0) {
         std::vector<int> hlev(mm), hrow(mm), bslot(mm, -1), bpos, brow;
@@ -2455,7 +2399,7 @@ bool Engine::fac_refactor(int bump_limit) {
     // Measured: the transport family (20 levels, no bump) 28.4 s with 32 terms, 31.5 s with 64; the config-3 family at 100 000 rows
     // (120-140 levels, bump 1 300-2 200) 25.0 s with 32, 22.9 s with 64.
     // (48, not 32, since the solves got cheaper in round 6: the 200 000-row transport solve 16.81 / 16.11 / 15.88 / 15.90 s at 24 / 32 / 48 / 64)
-    if (fac_period_auto_) fac_period_ = std::min(fac_J_, (nlev >= 64 || b >= 64) ? 64 : 48);
+    if (cfg.fac_period_auto) fac_period_ = std::min(fac_J_, (nlev >= 64 || b >= 64) ? 64 : 48);
     stats.fac_refactors += 1;
     stats.fac_levels = (uint64_t)nlev;
     stats.reinversions += 1;
@@ -2490,8 +2434,7 @@ bool Engine::fac_enter(int bump_limit) {
     return true;
 }
 bool Engine::fac_allowed_under_sharding() const {
-    static const bool forced = std::getenv("MLP_FACTOR_SHARED_DEVICE") && std::getenv("MLP_FACTOR_SHARED_DEVICE")[0] == '1';
-    return shard_world <= 1 || !ranks_share_device || forced;
+    return shard_world <= 1 || !ranks_share_device || cfg.fac_shared_device;
 }
 void Engine::fac_leave() {
     if (!fac_on_) return;
@@ -2499,16 +2442,15 @@ void Engine::fac_leave() {
     fac_on_ = false;
     view_dirty = true;
     stats.fac_switches += 1;
-    const int keep_mode = fac_mode;
     const bool keep_tried = fac_tried_;
-    fac_mode = 0;  // (the re-inversion below must not switch straight back)
+    fac_leaving_ = true;  // (the re-inversion below must not switch straight back)
     try {
         rebuild_inverse();  // classify singleton / nucleus columns, invert the nucleus from A (may end in MLP_ENOMEM on the models this mode exists for)
     } catch (...) {
-        fac_mode = keep_mode;
+        fac_leaving_ = false;
         throw;
     }
-    fac_mode = keep_mode;
+    fac_leaving_ = false;
     fac_tried_ = keep_tried;
     HIPCHECK(hipMemsetAsync(&d_ctl.p->nlow, 0, 2 * sizeof(int), st));
     HIPCHECK(hipStreamSynchronize(st));
@@ -2527,8 +2469,8 @@ void Engine::initial_solve() {
     // (solver.rs:1049-1055).  Recompute x_B = B^-1 (b - N x_N) from the basis; if a bound is then violated
     // by more than the tolerance, the dual loop repairs it (the reduced costs were just recomputed and are
     // dual feasible) and the primal loop confirms optimality.  Bounded; short runs never get here.
-    for (int round = 0; round < 3 && !budget_exhausted && final_refresh_pivots > 0 &&
-                        iters_since_polish >= (uint64_t)final_refresh_pivots; ++round) {
+    for (int round = 0; round < 3 && !budget_exhausted && cfg.final_refresh_pivots > 0 &&
+                        iters_since_polish >= (uint64_t)cfg.final_refresh_pivots; ++round) {
         iters_since_polish = 0;
         if (k_ > 0 || fac_on_) rebuild_inverse();  // fresh K^-1 from A first: the polish is only as accurate as the inverse it uses
         recalc_basic_vals();
@@ -2584,7 +2526,7 @@ void Engine::optimize() {
         // 1e-8 the optimality test works with, so "no eligible column" is re-examined once on reduced costs
         // and an objective recomputed from the basis (solver.rs:1199-1231); the loop resumes if a column
         // turns out to be eligible after all.  Short runs (every parity test) never get here.
-        if (final_refresh_pivots <= 0 || iters_since_recalc < (uint64_t)final_refresh_pivots) break;
+        if (cfg.final_refresh_pivots <= 0 || iters_since_recalc < (uint64_t)cfg.final_refresh_pivots) break;
         recalc_obj_coeffs();
         stats.final_refreshes += 1;
     }
@@ -3198,7 +3140,7 @@ void Engine::rebuild_inverse() {
         fac_on_ = false;  // the basis no longer peels: fall through to the explicit inverse
         view_dirty = true;
         stats.fac_switches += 1;
-    } else if (fac_mode == 1 && fac_allowed_under_sharding() && !stepping) {
+    } else if (cfg.fac_mode == 1 && !fac_leaving_ && fac_allowed_under_sharding() && !stepping) {
         if (fac_enter(32)) return;  // (automatic selection: only a basis that peels almost completely — a bump that grows would flip back)
     }
     HIPCHECK(hipMemsetAsync(&d_ctl.p->nlow, 0, 2 * sizeof(int), st));  // a fresh inverse has no pending terms
@@ -3250,8 +3192,7 @@ void Engine::rebuild_inverse() {
         flag.ensure(2, 0, st);
         HIPCHECK(hipMemsetAsync(flag.p, 0, 2 * sizeof(int), st));
         int hflag = 0;
-        static const bool force_gj = std::getenv("MLP_REINVERT_GJ") != nullptr;  // (debugging: the unblocked Gauss-Jordan at any size)
-        if (k >= 384 && !force_gj) {
+        if (k >= 384 && !cfg.reinvert_gj) {  // (cfg.reinvert_gj, debugging: the unblocked Gauss-Jordan at any size)
             // Large nucleus: blocked in-place Gauss-Jordan with partial pivoting (inverse.inc) — K is assembled row-major
             // straight into W and inverted there; the rank-32 update of a block step is the fold kernel of the delayed-update
             // mode.  (Rounds 1-3 called rocSOLVER's dgetrf + dgetri here: the product links no vendor library any more.)
@@ -3269,7 +3210,7 @@ void Engine::rebuild_inverse() {
             HIPCHECK(hipMemcpyAsync(&hflag, flag.p, sizeof(int), hipMemcpyDeviceToHost, st));
             HIPCHECK(hipStreamSynchronize(st));
         }
-        if (k < 384 || force_gj) {
+        if (k < 384 || cfg.reinvert_gj) {
             // Small nucleus: unblocked Gauss-Jordan with partial pivoting
             DevBuf<double> Kd, scratch;
             Kd.ensure((size_t)k * ld(), 0, st);
@@ -3534,7 +3475,7 @@ void Engine::load_basis(const uint8_t* blob, size_t len) {
 Engine* Engine::clone() {
     flush_lowrank();
     pull_maps();
-    std::unique_ptr<Engine> owner(new Engine());  // a throw below (hipMalloc failure, ...) must not leak the half-built clone
+    std::unique_ptr<Engine> owner(new Engine(cfg));  // a throw below (hipMalloc failure, ...) must not leak the half-built clone
     Engine* e = owner.get();
     e->num_vars = num_vars; e->direction = direction;
     e->m_ = m_; e->N_ = N_;
@@ -3543,8 +3484,8 @@ Engine* Engine::clone() {
     e->h_cons_row = h_cons_row;
     e->h_rptr = h_rptr; e->h_rcol = h_rcol; e->h_rval = h_rval;
     e->h_colnnz = h_colnnz; e->h_single_row = h_single_row; e->h_single_val = h_single_val;
-    e->max_col_nnz_ = max_col_nnz_; e->max_row_nnz_ = max_row_nnz_; e->amax_ = amax_; e->fpull_on_ = fpull_on_;
-    e->sw_balanced = sw_balanced; e->str_kmax = str_kmax; e->sb_kmax = sb_kmax; e->ph_kmax = ph_kmax; e->hyper_mode = hyper_mode; e->hyper_heavy = hyper_heavy; e->hyper_backoff_max = hyper_backoff_max; e->ratio_two = ratio_two; e->ratio_spin_limit = ratio_spin_limit; e->ranks_share_device = false; e->lazy_dse = lazy_dse; e->beta_stale = beta_stale; e->use_order = use_order; e->use_pack = use_pack; e->order_force = order_force; e->lifetime_pivots = lifetime_pivots;
+    e->max_col_nnz_ = max_col_nnz_; e->max_row_nnz_ = max_row_nnz_; e->amax_ = amax_;
+    e->ratio_two = ratio_two; e->ranks_share_device = false; e->beta_stale = beta_stale; e->use_pack = use_pack; e->order_force = order_force; e->lifetime_pivots = lifetime_pivots;
     e->h_basic_vars = h_basic_vars; e->h_nb_vars = h_nb_vars; e->h_var_loc = h_var_loc;
     e->h_kslot_of_pos = h_kslot_of_pos; e->h_srow_of_pos = h_srow_of_pos; e->h_kslot_of_row = h_kslot_of_row;
     e->h_pos_of_srow = h_pos_of_srow; e->h_sdiag_of_pos = h_sdiag_of_pos; e->h_nb_fixed = h_nb_fixed;
@@ -3554,10 +3495,8 @@ Engine* Engine::clone() {
     e->resume_in_optimize = resume_in_optimize;
     e->nnz_nonbasic = nnz_nonbasic;
     e->trace = trace; e->profile = profile;
-    e->banded_mode = banded_mode; e->det_mode = det_mode;
-    e->final_refresh_pivots = final_refresh_pivots; e->iters_since_recalc = iters_since_recalc;
+    e->iters_since_recalc = iters_since_recalc;
     e->iters_since_polish = iters_since_polish;
-    e->ld_pad = ld_pad; e->lr_force = lr_force; e->force_big_tiles = force_big_tiles;
     hipStream_t s2 = e->st;
     {   // the matrix is copied device to device (the host keeps no CSC)
         const size_t nz = h_rcol.size();
@@ -3596,7 +3535,7 @@ Engine* Engine::clone() {
     HIPCHECK(hipStreamSynchronize(s2));
     std::memcpy(e->h_ctl, h_ctl, sizeof(Ctl));
     e->values_dirty = true;
-    e->fac_mode = fac_mode; e->fac_J_ = fac_J_; e->fac_period_ = fac_period_; e->fac_period_auto_ = fac_period_auto_; e->fac_auto_cap_ = fac_auto_cap_; e->fac_bump_max_ = fac_bump_max_; e->fac_sb_max_ = fac_sb_max_; e->fac_sb_from_ = fac_sb_from_; e->fac_pair_ = fac_pair_; e->fac_skip_ = fac_skip_;
+    e->fac_J_ = fac_J_; e->fac_period_ = fac_period_;
     e->cold_start_ = false;  // a clone continues a solve (branch-and-bound: clone + fix_var): warm-start policy, no eager capture of the long graph
     if (fac_on_ && !e->fac_enter())  // (a fresh peel of the same basis: the same operator, no pending terms)
         throw MlpError(-3, "clone: the basis of a solution on the compact factor must peel");

@@ -426,7 +426,12 @@ constexpr int PB_ROWS = 4096;   // rows per LDS block of the blocked F push (32 
 constexpr int PB_CHUNKS = 48;   // capacity of the partial-sum buffer of the blocked F push (column chunks = slot ranges)
 constexpr int PB_CHUNKS_DEFAULT = 24;  // chunks used
 
-struct Geom {
+// Forms of an iteration that a Solution's settings can switch off (Geom.forms; settings.h names the knob of each)
+enum : unsigned {
+    FORM_RATIO_ONE = 1u << 0, FORM_TK_RIDE = 1u << 1, FORM_RATIO_LIST = 1u << 2, FORM_BTRAN_RIDE = 1u << 3, FORM_V_RIDE = 1u << 4,
+    FORM_SMALL_BASIS = 1u << 5, FORM_PRIMAL_HEAD = 1u << 6, FORM_RK_RIDE = 1u << 7, FORM_PULL_INSIDE = 1u << 8, FORM_HEAD_APPLY = 1u << 9
+};
+struct Geom {  // plain ints without padding: compared with memcmp (Engine::get_graph), value-initialised by Engine::geom
     int m, n, cap;
     int lanes;  // lanes per CSC column in the pull kernels (4, 16 or 64; from the average column length)
     int sweep_one;  // average column below 3 entries: the CSC-pull tableau row takes ONE lane per column (a quarter of the workgroups; sums in storage order)
@@ -439,6 +444,8 @@ struct Geom {
     int ratio_two;      // the two Harris passes as two launches (no in-kernel wait): MLP_RATIO_TWO_KERNELS, ranks sharing a device, after an ITER_STALL
     int ratio_list;     // the grid form of the primal Harris test may run as ONE grid pass (list form): off when the spin limit of the in-kernel wait is <= 0
     int fp;             // large nucleus, lazy primal iteration: the F product of the FTRAN is PULLED inside the ratio test's launch (fpull.inc)
+    unsigned forms;     // FORM_* bits: the forms the settings allow (the launch predicates test them)
+    int rl_cap;         // list form of the primal Harris test: entries a block may list (0: every decision re-scans; tests), at most RL_CAP
 };
 // Large tiles in the delayed-update mode: the pass over the nucleus inverse is k_stream_w's strip tiling (its partials lie by strip)
 static inline bool strip_tiled(const DevView& dv, const Geom& g) { return dv.lrJ && g.big; }
@@ -497,7 +504,7 @@ void launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t
 bool rk_rides_post(const DevView& dv, const Geom& g);  // (strip-tiled tail of the large-nucleus pass: the form that carries the rho_K blocks)
 void launch_exact_beta(const DevView& dv, hipStream_t st);  // beta_p = ||e_p^T B^-1||^2 for every basic position (lazy dual steepest edge)
 // hypersparse iteration (hyper.inc): up to max_iters dual iterations (no primal steepest edge) in ONE launch of one workgroup
-void launch_hyper_dual(const DevView& dv, int use_dse, int max_iters, long heavy, hipStream_t st);  // heavy <= 0: default work bound
+void launch_hyper_dual(const DevView& dv, int use_dse, int max_iters, long heavy, int prof_on, hipStream_t st);  // heavy <= 0: default work bound; prof_on: per-stage wall-clock marks
 void launch_mail_handshake(const DevView& dv, int* out, hipStream_t st);  // transport self-test at enable_sharding
 // pump transport: stage this rank's records / deliver the peers' records (between them: an all-gather of the staging blocks)
 constexpr int MAIL_PUMP_RECS = MAIL_KINDS * 2 + 1;  // 64-byte records per rank in the staging buffer (the last one: the host's batch word)

@@ -5173,8 +5173,7 @@ __global__ void __launch_bounds__(BLK) k_row_pull(DevView v, int n_pull) {
         else { STMT32; }                        \
     } while (0)
 
-void launch_hyper_dual(const DevView& dv, int use_dse, int max_iters, long heavy, hipStream_t st) {
-    const int prof_on = std::getenv("MLP_HYPER_PROF") != nullptr ? 1 : 0;  // per-stage wall-clock marks (each costs a timer read)
+void launch_hyper_dual(const DevView& dv, int use_dse, int max_iters, long heavy, int prof_on, hipStream_t st) {  // prof_on: each mark costs a timer read
     static bool attr_set = false;
     if (!attr_set) {  // 136 KB of LDS lists (more than the default 64 KB per workgroup)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_hyper_dual), hipFuncAttributeMaxDynamicSharedMemorySize, (int)HY_LDS_BYTES);
@@ -5248,16 +5247,13 @@ static int coresident_half(const void* fn, int slot) {
     }
     return cache[slot][dev];
 }
-static bool ratio_one_enabled() {  // MLP_RATIO_ONE=0: the grid forms at any size (tests of their in-kernel wait on small instances)
-    const char* e = std::getenv("MLP_RATIO_ONE");  // (read per launch: tests switch it inside one process)
-    return !(e && e[0] == '0');
-}
+// FORM_RATIO_ONE off: the grid forms at any size (tests of their in-kernel wait on small instances)
+static bool ratio_one_enabled(const Geom& g) { return (g.forms & FORM_RATIO_ONE) != 0; }
 // t_K rides in the ratio launch (k_ratio_primal_fused, n_ratio > 0): the one-launch grid form of the test is the one that runs, ...
 static bool tk_ride_grid_runs(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_TK_RIDE");
-    if (e && e[0] == '0') return false;
+    if (!(g.forms & FORM_TK_RIDE)) return false;
     if (dv.world > 1 || g.ratio_two || g.cap <= 0) return false;
-    if (g.m <= 16384 && ratio_one_enabled()) return false;
+    if (g.m <= 16384 && ratio_one_enabled(g)) return false;
     const int nb = grid_for(g.m);
     const int max_coresident = coresident_half(reinterpret_cast<const void*>(k_ratio_primal_fused), 0);
     return nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m;
@@ -5290,7 +5286,7 @@ void launch_fpull_ratio(const DevView& dv, const Geom& g, hipStream_t st, hipEve
 // The form of the primal Harris test without a t_K ride: 0 one block (small model), 1 the fused grid (both passes in one launch, PT = 4
 // positions per thread in registers), 2 pass 1 and pass 2 as two launches whose loops stride (also what state("ratio_primal_form") reports).
 int ratio_primal_form(const DevView& dv, const Geom& g) {
-    if (dv.world <= 1 && g.m <= 16384 && ratio_one_enabled()) return 0;
+    if (dv.world <= 1 && g.m <= 16384 && ratio_one_enabled(g)) return 0;
     const int nb = grid_for(g.m);
     // The fused kernel's blocks wait inside the launch for its last-arriving block, which is only safe while the
     // WHOLE grid is co-resident: bound the grid by what this device (or partition: CPX mode, CU mask) can hold at
@@ -5301,28 +5297,22 @@ int ratio_primal_form(const DevView& dv, const Geom& g) {
     return (nb <= max_coresident && (long)nb * BLK * 4 >= (long)g.m) ? 1 : 2;
 }
 // The list form of the grid test (k_ratio_primal_fused, rl_cap >= 0: one grid pass, no in-kernel wait): entries a block may list, or -1 for
-// the publish-wait form — MLP_RATIO_LIST=0, or a spin limit of 0 or less (Geom.ratio_list = 0: the hook with which a test makes the
-// in-kernel wait give up, so the wait is what has to run).  MLP_RATIO_LIST_CAP (default RL_CAP, 0: every decision re-scans) is for tests.
+// the publish-wait form — FORM_RATIO_LIST off, or a spin limit of 0 or less (Geom.ratio_list = 0: the hook with which a test makes the
+// in-kernel wait give up, so the wait is what has to run).  Geom.rl_cap (default RL_CAP, 0: every decision re-scans) is for tests.
 int ratio_list_cap(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_RATIO_LIST");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
-    if ((e && e[0] == '0') || !g.ratio_list || !dv.rl_cnt || grid_for(g.m) > RL_BLOCKS) return -1;
-    const char* cp = std::getenv("MLP_RATIO_LIST_CAP");
-    return cp ? std::max(0, std::min(RL_CAP, std::atoi(cp))) : RL_CAP;
+    if (!(g.forms & FORM_RATIO_LIST) || !g.ratio_list || !dv.rl_cnt || grid_for(g.m) > RL_BLOCKS) return -1;
+    return g.rl_cap;
 }
 // Medium nucleus, lazy primal iteration: no BTRAN launch — t_K rides behind the ratio blocks (y_S on the fly, as for the small nucleus) and
 // the final block of the test forms rho_K (ratio_primal_finish, rk_inside).  Eager update of the inverse only (no pending terms), tiles of the
-// plain fused pass (capacity <= 4 096), heads inside their kernels.  MLP_BTRAN_RIDE=0: k_btran.
+// plain fused pass (capacity <= 4 096), heads inside their kernels.  FORM_BTRAN_RIDE off: k_btran.
 bool btran_rides_ratio(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_BTRAN_RIDE");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
-    if (e && e[0] == '0') return false;
-    return g.head_fused && !g.big && !g.fac && !dv.lrJ && g.cap <= 4096 && tk_rides_ratio_small(dv, g);
+    return (g.forms & FORM_BTRAN_RIDE) && g.head_fused && !g.big && !g.fac && !dv.lrJ && g.cap <= 4096 && tk_rides_ratio_small(dv, g);
 }
 // ... and the v partials of the pass over W ride there as well (v_ride_body): the BASIS stage is one launch, the v tail beside the eta update
-// (launch_eta_vtail).  The 8-row tiles of the plain pass only.  MLP_V_RIDE=0: k_fused_w<8> with the v partials + k_post_fused.
+// (launch_eta_vtail).  The 8-row tiles of the plain pass only.  FORM_V_RIDE off: k_fused_w<8> with the v partials + k_post_fused.
 bool v_rides_ratio(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_V_RIDE");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
-    if (e && e[0] == '0') return false;
-    return btran_rides_ratio(dv, g) && fw_rows(g) == 8;
+    return (g.forms & FORM_V_RIDE) && btran_rides_ratio(dv, g) && fw_rows(g) == 8;
 }
 void launch_ratio_primal(const DevView& dv, const Geom& g, int use_pse, hipStream_t st, int tk_ride, int rk_inside, int v_ride) {
     if (tk_ride) {  // (the caller asked tk_rides_ratio / tk_rides_ratio_small first); 2: small nucleus, y_S on the fly
@@ -5436,9 +5426,7 @@ void launch_row_sparse(const DevView& dv, const Geom& g, int mode, int with_stru
 #undef ROWPULL
 }
 bool small_basis_supported(const DevView& dv, const Geom& g) {
-    const char* sb = std::getenv("MLP_SMALL_BASIS");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
-    const bool off = sb && sb[0] == '0';
-    return !off && g.sb && g.cap > 0 && g.cap <= SB_CAP && !g.big && !dv.lrJ && g.str && !g.ratio_two && !g.fac && dv.world <= 1;
+    return (g.forms & FORM_SMALL_BASIS) && g.sb && g.cap > 0 && g.cap <= SB_CAP && !g.big && !dv.lrJ && g.str && !g.ratio_two && !g.fac && dv.world <= 1;
 }
 void launch_small_basis(const DevView& dv, const Geom& g, hipStream_t st, int tk_inside) {
     const int n_touch = blocks_for((long)(g.cap + 1) * 64);
@@ -5451,9 +5439,7 @@ void launch_small_basis(const DevView& dv, const Geom& g, hipStream_t st, int tk
 #undef SMALLB
 }
 bool primal_head_supported(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_PRIMAL_HEAD");  // (read per call, i.e. per captured graph: tests toggle it inside one process)
-    const bool off = e && e[0] == '0';
-    return !off && g.ph && g.str && g.cap > 0 && !g.big && !g.fac && !dv.lrJ && dv.world <= 1 && !dv.pb_on && !dv.det_pull && dv.rowinfo &&
+    return (g.forms & FORM_PRIMAL_HEAD) && g.ph && g.str && g.cap > 0 && !g.big && !g.fac && !dv.lrJ && dv.world <= 1 && !dv.pb_on && !dv.det_pull && dv.rowinfo &&
            dv.hy_stamp_p && dv.str_list;
 }
 int primal_head_kmax(int longest_column) {
@@ -5467,7 +5453,7 @@ void launch_init_nb_rng(const DevView& dv, const Geom& g, hipStream_t st) {
     hipLaunchKernelGGL(k_init_nb_rng, dim3(blocks_for(g.n)), dim3(BLK), 0, st, dv);
 }
 void launch_ratio_dual(const DevView& dv, const Geom& g, hipStream_t st, int list_ok) {
-    if (dv.world <= 1 && g.n <= RATIO_ONE_MAX && ratio_one_enabled()) {  // small model: one block, no grid-wide reduction
+    if (dv.world <= 1 && g.n <= RATIO_ONE_MAX && ratio_one_enabled(g)) {  // small model: one block, no grid-wide reduction
         hipLaunchKernelGGL(k_ratio_dual_one, dim3(1), dim3(BLK), 0, st, dv, list_ok);
         return;
     }
@@ -5573,9 +5559,7 @@ void launch_eta_vtail(const DevView& dv, const Geom& g, hipStream_t st) {
     LAUNCH_T(2, (k_fused_w<8, false, false, true, false, false, 1, false, true>), dim3(nstripes, nchunks + 1), dim3(BLK), 0, st, dv);
 }
 bool rk_rides_post(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_RK_RIDE");
-    if (e && e[0] == '0') return false;
-    return strip_tiled(dv, g) && !dv.wshard && dv.world <= 1;
+    return (g.forms & FORM_RK_RIDE) && strip_tiled(dv, g) && !dv.wshard && dv.world <= 1;
 }
 void launch_post_fused(const DevView& dv, const Geom& g, int with_v, hipStream_t st, int classic, int skip_push, int with_tau, int touch, int rk_ride) {
     // touch: also build the touched-column list of the sparse tableau row in this launch (extra blocks) where
@@ -5622,15 +5606,12 @@ void launch_structure_update(const DevView& dv, const Geom& g, hipStream_t st) {
     hipLaunchKernelGGL(k_struct_update, dim3(blocks_for(g.cap)), dim3(BLK), 0, st, dv);
 }
 bool update_pulls_inside(const DevView& dv, const Geom& g) {
-    const char* e = std::getenv("MLP_PULL_INSIDE");  // (tests: the three forms of the small-nucleus iteration must agree, tests/test_primal_head.py)
-    if (e && e[0] == '0') return false;
+    if (!(g.forms & FORM_PULL_INSIDE)) return false;  // (tests: the three forms of the small-nucleus iteration must agree, tests/test_primal_head.py)
     const int t = g.m > g.n ? g.m : g.n;
     return primal_head_supported(dv, g) && blocks_for(t, BLK * 4) <= 2048 && dv.hy_stamp_n != nullptr;  // at most four positions per thread
 }
 bool head_applies(const DevView& dv, const Geom& g) {  // ... and the head applies the basic side and position q itself (the update kernel: non-basic side only)
-    const char* e = std::getenv("MLP_HEAD_APPLY");
-    if (e && e[0] == '0') return false;
-    return update_pulls_inside(dv, g) && dv.nb_order == nullptr && dv.pk_valid == nullptr;
+    return (g.forms & FORM_HEAD_APPLY) && update_pulls_inside(dv, g) && dv.nb_order == nullptr && dv.pk_valid == nullptr;
 }
 void launch_update_pivot(const DevView& dv, const Geom& g, int phase, int use_dse, int use_pse, hipStream_t st, int inline_comb,
                          int with_struct, int pull_inside) {

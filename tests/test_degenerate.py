@@ -68,7 +68,7 @@ PATHS = {
 }
 BUMP_ONLY = ("factor-sparse-bump", "factor-dense-bump")       # on the families whose bases have cycles: cover and two_matching
 KNOBS = sorted({k for env in PATHS.values() for k in env})
-# (MLP_FACTOR_FUSE, MLP_FACTOR_RHO_PART and MLP_PB_DET are read once per process: never varied here)
+# (MLP_FACTOR_FUSE, MLP_FACTOR_RHO_PART and MLP_PB_DET are read once per Solution like every knob; they are not varied here)
 
 # largest measured engine / oracle pivot ratio per family (module docstring)
 RATIO = {"assignment": 1.0, "unit_transport": 1.0, "unit_cover": 1.0, "two_matching": 1.0}

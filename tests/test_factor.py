@@ -350,7 +350,7 @@ def test_a_dense_bump_is_carried_by_the_dense_tail_of_the_elimination(monkeypatc
 def test_fused_launches_and_left_behind_partial_sums_change_no_bit(knob):
     """The dual iteration on the compact factor with its three single-purpose launches riding inside the solves (U_j stored unscaled with
     its factor beside it) and with the BTRAN leaving the partial sums of V_j . rho for the FTRAN of tau — against the forms they replace
-    (knob = 0, read once per process: each form runs in a process of its own): the same pivots, and x, the objective and the dual
+    (knob = 0, read when the Solution is created: each form runs in a process of its own here): the same pivots, and x, the objective and the dual
     steepest-edge weights BIT for bit.  Transport instance (several levels, 32 pending terms) and config 3 (a bump as a sparse LU)."""
     import subprocess, sys, os, json
     code = r'''

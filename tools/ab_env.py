@@ -4,7 +4,7 @@
     python tools/ab_env.py late "MLP_PB_DET=0" "MLP_PB_DET=1" [--reps 2] [--pivots 512]
 
 window: early (pivots 5..25 x 200 fresh solves is too noisy: uses pivots 200..2200 from the slack basis), mid (k = 9 999) or
-late (k = 20 493).  Each configuration runs in its own process (the knobs are read once per process), alternating, REPS times;
+late (k = 20 493).  Each configuration runs in its own process (the knobs are read when a Solution is created), alternating, REPS times;
 prints us per pivot of the graph-replayed run and the objective reached (so that a change of the pivot path is visible)."""
 import os
 import subprocess
