@@ -100,6 +100,10 @@ class MlpPropagateInfo(C.Structure):  # include/minilp_hip.h: mlp_propagate_info
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
 ABI_VERSION = 5  # include/minilp_hip.h: MLP_ABI_VERSION
+# (size function of the library, the class here): lib() refuses a library whose struct differs in size
+_STRUCT_SIZES = (("mlp_certificate_size", MlpCertificate), ("mlp_ranging_info_size", MlpRangingInfo), ("mlp_cut_info_size", MlpCutInfo),
+                 ("mlp_tableau_info_size", MlpTableauInfo), ("mlp_gmi_info_size", MlpGmiInfo), ("mlp_branch_info_size", MlpBranchInfo),
+                 ("mlp_fix_info_size", MlpFixInfo), ("mlp_bounds_info_size", MlpBoundsInfo), ("mlp_propagate_info_size", MlpPropagateInfo))
 
 
 class MlpIterInfo(C.Structure):  # include/minilp_hip.h: mlp_iter_info
@@ -140,9 +144,10 @@ def lib():
     if L.mlp_abi_version() != ABI_VERSION or L.mlp_stats_size() != C.sizeof(MlpStats):
         raise ImportError(f"{_SO} was built from another version of include/minilp_hip.h (ABI {L.mlp_abi_version()}, mlp_stats "
                           f"{L.mlp_stats_size()} bytes; this binding: ABI {ABI_VERSION}, {C.sizeof(MlpStats)} bytes): rebuild it")
-    sig("mlp_certificate_size", u64)
-    if L.mlp_certificate_size() != C.sizeof(MlpCertificate):
-        raise ImportError(f"{_SO}: mlp_certificate is {L.mlp_certificate_size()} bytes, this binding {C.sizeof(MlpCertificate)}: rebuild it")
+    for size_fn, struct in _STRUCT_SIZES:
+        sig(size_fn, u64)
+        if getattr(L, size_fn)() != C.sizeof(struct):
+            raise ImportError(f"{_SO}: {size_fn[:-5]} is {getattr(L, size_fn)()} bytes, this binding {C.sizeof(struct)}: rebuild it")
     sig("mlp_last_error", C.c_char_p)
     sig("mlp_device_count", i32)
     sig("mlp_set_device", i32, i32)
@@ -200,22 +205,13 @@ def lib():
     sig("mlp_solution_reduced_costs", i32, vp, pdbl, u32)
     sig("mlp_solution_reduced_cost", i32, vp, u32, pdbl)
     sig("mlp_solution_certificate", i32, vp, C.POINTER(MlpCertificate))
-    sig("mlp_ranging_info_size", u64)
-    if L.mlp_ranging_info_size() != C.sizeof(MlpRangingInfo):
-        raise ImportError(f"{_SO}: mlp_ranging_info is {L.mlp_ranging_info_size()} bytes, this binding {C.sizeof(MlpRangingInfo)}: rebuild it")
     sig("mlp_solution_basis_status", i32, vp, C.POINTER(C.c_int32), u32, C.POINTER(C.c_int32), u64)
     sig("mlp_solution_cost_ranging", i32, vp, pu32, u64, pdbl, pdbl)
     sig("mlp_solution_rhs_ranging", i32, vp, C.POINTER(C.c_uint64), u64, pdbl, pdbl)
     sig("mlp_solution_ranging_info", i32, vp, C.POINTER(MlpRangingInfo))
-    sig("mlp_cut_info_size", u64)
-    if L.mlp_cut_info_size() != C.sizeof(MlpCutInfo):
-        raise ImportError(f"{_SO}: mlp_cut_info is {L.mlp_cut_info_size()} bytes, this binding {C.sizeof(MlpCutInfo)}: rebuild it")
     sig("mlp_solution_add_constraints_csr", i32, C.POINTER(vp), u64, C.POINTER(C.c_uint64), pu32, pdbl, C.POINTER(C.c_int32), pdbl)
     sig("mlp_solution_add_gomory_cuts", i32, C.POINTER(vp), pu32, u64)
     sig("mlp_solution_cut_info", i32, vp, C.POINTER(MlpCutInfo))
-    sig("mlp_tableau_info_size", u64)
-    if L.mlp_tableau_info_size() != C.sizeof(MlpTableauInfo):
-        raise ImportError(f"{_SO}: mlp_tableau_info is {L.mlp_tableau_info_size()} bytes, this binding {C.sizeof(MlpTableauInfo)}: rebuild it")
     pu64 = C.POINTER(C.c_uint64)
     sig("mlp_solution_num_rows", u64, vp)
     sig("mlp_solution_basis_head", i32, vp, pu64, u64)
@@ -225,35 +221,20 @@ def lib():
     sig("mlp_solution_tableau_cols", i32, vp, pu64, u64, pdbl, u64)
     sig("mlp_solution_basis_solve", i32, vp, i32, pdbl, u64, u64, pdbl, u64)
     sig("mlp_solution_tableau_info", i32, vp, C.POINTER(MlpTableauInfo))
-    sig("mlp_gmi_info_size", u64)
-    if L.mlp_gmi_info_size() != C.sizeof(MlpGmiInfo):
-        raise ImportError(f"{_SO}: mlp_gmi_info is {L.mlp_gmi_info_size()} bytes, this binding {C.sizeof(MlpGmiInfo)}: rebuild it")
     pu8 = C.POINTER(C.c_uint8)
     sig("mlp_solution_add_gmi_cuts", i32, C.POINTER(vp), pu32, u64, pu8, u32, pu8, u64, dbl, C.POINTER(C.c_int32))
     sig("mlp_solution_gmi_info", i32, vp, C.POINTER(MlpGmiInfo))
-    sig("mlp_branch_info_size", u64)
-    if L.mlp_branch_info_size() != C.sizeof(MlpBranchInfo):
-        raise ImportError(f"{_SO}: mlp_branch_info is {L.mlp_branch_info_size()} bytes, this binding {C.sizeof(MlpBranchInfo)}: rebuild it")
     sig("mlp_solution_branch_penalties", i32, vp, pu32, u64, pu8, u32, pu8, u64, pdbl, pdbl, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
         pdbl, C.POINTER(C.c_int32))
     sig("mlp_solution_branch_info", i32, vp, C.POINTER(MlpBranchInfo))
-    sig("mlp_fix_info_size", u64)
-    if L.mlp_fix_info_size() != C.sizeof(MlpFixInfo):
-        raise ImportError(f"{_SO}: mlp_fix_info is {L.mlp_fix_info_size()} bytes, this binding {C.sizeof(MlpFixInfo)}: rebuild it")
     sig("mlp_solution_cutoff_bounds", i32, vp, dbl, pu8, u32, pu32, pdbl, pdbl, u64, pu64, C.POINTER(i32))
     sig("mlp_solution_fix_vars", i32, C.POINTER(vp), pu32, pdbl, u64)
     sig("mlp_solution_unfix_vars", i32, C.POINTER(vp), pu32, u64, pu64)
     sig("mlp_solution_fix_info", i32, vp, C.POINTER(MlpFixInfo))
-    sig("mlp_bounds_info_size", u64)
-    if L.mlp_bounds_info_size() != C.sizeof(MlpBoundsInfo):
-        raise ImportError(f"{_SO}: mlp_bounds_info is {L.mlp_bounds_info_size()} bytes, this binding {C.sizeof(MlpBoundsInfo)}: rebuild it")
     sig("mlp_solution_set_var_bounds", i32, C.POINTER(vp), pu32, pdbl, pdbl, u64)
     sig("mlp_solution_tighten_by_reduced_cost", i32, C.POINTER(vp), dbl, pu8, u32, pu64, C.POINTER(i32))
     sig("mlp_solution_var_bounds", i32, vp, pu32, u64, pdbl, pdbl)
     sig("mlp_solution_bounds_info", i32, vp, C.POINTER(MlpBoundsInfo))
-    sig("mlp_propagate_info_size", u64)
-    if L.mlp_propagate_info_size() != C.sizeof(MlpPropagateInfo):
-        raise ImportError(f"{_SO}: mlp_propagate_info is {L.mlp_propagate_info_size()} bytes, this binding {C.sizeof(MlpPropagateInfo)}: rebuild it")
     sig("mlp_solution_propagate_bounds", i32, vp, pu8, u32, C.c_int32, pu32, pdbl, pdbl, u64, pu64, C.POINTER(i32))
     sig("mlp_solution_tighten_by_propagation", i32, C.POINTER(vp), pu8, u32, C.c_int32, pu64, C.POINTER(i32))
     sig("mlp_solution_propagate_info", i32, vp, C.POINTER(MlpPropagateInfo))
@@ -466,6 +447,12 @@ class Solution:
     def __iter__(self):  # lib.rs:350 iter()
         return iter(enumerate(self.values()))
 
+    def _report(self, fn, struct):
+        """The struct a read fills in, as a dict."""
+        r = struct()
+        _raise(fn(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in struct._fields_}
+
     # ---- dual values, reduced costs, KKT certificate (include/minilp_hip.h: mlp_solution_dual_values ...; user's objective sense)
     @property
     def num_constraints(self):
@@ -496,9 +483,7 @@ class Solution:
 
     def certificate(self):
         """KKT certificate of the current point (mlp_certificate) as a dict."""
-        c = MlpCertificate()
-        _raise(lib().mlp_solution_certificate(self._h, C.byref(c)))
-        return {n: getattr(c, n) for n, _ in MlpCertificate._fields_}
+        return self._report(lib().mlp_solution_certificate, MlpCertificate)
 
     # ---- basis status, cost / rhs ranging (include/minilp_hip.h: mlp_solution_basis_status ...; definitions there)
     def basis_status(self):
@@ -531,9 +516,7 @@ class Solution:
 
     def ranging_info(self):
         """Counters of the last cost_ranging / rhs_ranging call (mlp_ranging_info) as a dict."""
-        r = MlpRangingInfo()
-        _raise(lib().mlp_solution_ranging_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpRangingInfo._fields_}
+        return self._report(lib().mlp_solution_ranging_info, MlpRangingInfo)
 
     # ---- reading the tableau (include/minilp_hip.h: mlp_solution_binv_rows ...; numbering and definitions there): columns are
     #      j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by constraint; internal
@@ -606,9 +589,7 @@ class Solution:
 
     def tableau_info(self):
         """Counters of the last tableau call (mlp_tableau_info) as a dict."""
-        r = MlpTableauInfo()
-        _raise(lib().mlp_solution_tableau_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpTableauInfo._fields_}
+        return self._report(lib().mlp_solution_tableau_info, MlpTableauInfo)
 
     def add_constraint(self, expr, cmp_op, rhs):
         idx, val = _terms(expr)
@@ -661,10 +642,7 @@ class Solution:
 
     def add_gomory_cuts(self, vars):
         """One round of Gomory cuts, one per listed basic variable, all from the current basis; feasibility restored once."""
-        v = np.ascontiguousarray(list(vars), dtype=np.int64)
-        if len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF):
-            raise InternalError(-1, "add_gomory_cuts: variable out of range")
-        v = v.astype(np.uint32)
+        v = self._var_list(vars, "add_gomory_cuts")
         h = self._take()
         _raise(lib().mlp_solution_add_gomory_cuts(C.byref(h), _p(v, C.c_uint32), len(v)))
         return Solution(h)
@@ -682,29 +660,28 @@ class Solution:
         m[idx] = 1
         return m
 
+    @staticmethod
+    def _mask_args(mask, n_without=0):
+        """(pointer, length) of an optional uint8 mask; None: a NULL pointer and n_without."""
+        return (None, n_without) if mask is None else (_p(mask, C.c_uint8), len(mask))
+
     def add_gmi_cuts(self, vars, integer_vars, integer_constraints=None, away=0.01):
         """One round of Gomory mixed-integer cuts (mlp_solution_add_gmi_cuts; semantics in the header), one per listed basic integer
         variable, all from the current basis; feasibility restored once.  integer_vars / integer_constraints: a bool mask or a list of
         indices (constraints: the slacks that are integer; None: all slacks continuous).  Returns (Solution, status): status[i] is 0
         emitted, 1 skipped (fraction within away), 2 skipped (free non-basic column in the row)."""
-        v = np.ascontiguousarray(list(vars), dtype=np.int64)
-        if len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF):
-            raise InternalError(-1, "add_gmi_cuts: variable out of range")
-        v = v.astype(np.uint32)
+        v = self._var_list(vars, "add_gmi_cuts")
         vm = self._int_mask(integer_vars, self.num_vars)
         cm = None if integer_constraints is None else self._int_mask(integer_constraints, self.num_constraints)
         status = np.zeros(len(v), dtype=np.int32)
         h = self._take()
-        _raise(lib().mlp_solution_add_gmi_cuts(C.byref(h), _p(v, C.c_uint32), len(v), _p(vm, C.c_uint8), len(vm),
-                                               None if cm is None else _p(cm, C.c_uint8), 0 if cm is None else len(cm), float(away),
+        _raise(lib().mlp_solution_add_gmi_cuts(C.byref(h), _p(v, C.c_uint32), len(v), _p(vm, C.c_uint8), len(vm), *self._mask_args(cm), float(away),
                                                _p(status, C.c_int32)))
         return Solution(h), status
 
     def gmi_info(self):
         """Counters of the last add_gmi_cuts call (mlp_gmi_info) as a dict."""
-        r = MlpGmiInfo()
-        _raise(lib().mlp_solution_gmi_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpGmiInfo._fields_}
+        return self._report(lib().mlp_solution_gmi_info, MlpGmiInfo)
 
     # ---- branching penalties (include/minilp_hip.h: mlp_solution_branch_penalties; definitions there)
     def branch_penalties(self, vars, integer_vars=None, integer_constraints=None):
@@ -713,10 +690,7 @@ class Solution:
         up_col (the column that would enter; -1: none), frac, status (0 basic and fractional, 1 non-basic or integral: zeros).
         integer_vars / integer_constraints: a bool mask or a list of indices, as for add_gmi_cuts; they switch Tomlin's strengthening on
         (the numbers then bound the integer descendants of the branch, not the child LP).  A read: the solution is left as it is."""
-        v = np.ascontiguousarray(list(vars), dtype=np.int64).reshape(-1)
-        if len(v) and (v.min() < 0 or v.max() > 0xFFFFFFFF):
-            raise InternalError(-1, "branch_penalties: variable out of range")
-        v = v.astype(np.uint32)
+        v = self._var_list(vars, "branch_penalties")
         if integer_vars is None and integer_constraints is not None:
             raise InternalError(-1, "branch_penalties: integer_constraints needs integer_vars")
         vm = None if integer_vars is None else self._int_mask(integer_vars, self.num_vars)
@@ -724,18 +698,15 @@ class Solution:
         n = len(v)
         out = dict(down=np.zeros(n), up=np.zeros(n), down_col=np.zeros(n, dtype=np.int64), up_col=np.zeros(n, dtype=np.int64),
                    frac=np.zeros(n), status=np.zeros(n, dtype=np.int32))
-        _raise(lib().mlp_solution_branch_penalties(self._h, _p(v, C.c_uint32), n, None if vm is None else _p(vm, C.c_uint8),
-                                                   0 if vm is None else len(vm), None if cm is None else _p(cm, C.c_uint8),
-                                                   0 if cm is None else len(cm), _p(out["down"], C.c_double), _p(out["up"], C.c_double),
+        _raise(lib().mlp_solution_branch_penalties(self._h, _p(v, C.c_uint32), n, *self._mask_args(vm), *self._mask_args(cm),
+                                                   _p(out["down"], C.c_double), _p(out["up"], C.c_double),
                                                    _p(out["down_col"], C.c_int64), _p(out["up_col"], C.c_int64),
                                                    _p(out["frac"], C.c_double), _p(out["status"], C.c_int32)))
         return out
 
     def branch_info(self):
         """Counters of the last branch_penalties call (mlp_branch_info) as a dict."""
-        r = MlpBranchInfo()
-        _raise(lib().mlp_solution_branch_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpBranchInfo._fields_}
+        return self._report(lib().mlp_solution_branch_info, MlpBranchInfo)
 
     # ---- reduced-cost bounds from a cutoff, batched fixing (include/minilp_hip.h: mlp_solution_cutoff_bounds ...; semantics there)
     def cutoff_bounds(self, cutoff, integer_vars=None):
@@ -747,8 +718,7 @@ class Solution:
         vm = None if integer_vars is None else self._int_mask(integer_vars, n)
         v, lo, hi = np.zeros(n, dtype=np.uint32), np.zeros(n), np.zeros(n)
         count, pruned = C.c_uint64(), C.c_int()
-        _raise(lib().mlp_solution_cutoff_bounds(self._h, float(cutoff), None if vm is None else _p(vm, C.c_uint8),
-                                                n if vm is None else len(vm), _p(v, C.c_uint32), _p(lo, C.c_double), _p(hi, C.c_double), n,
+        _raise(lib().mlp_solution_cutoff_bounds(self._h, float(cutoff), *self._mask_args(vm, n), _p(v, C.c_uint32), _p(lo, C.c_double), _p(hi, C.c_double), n,
                                                 C.byref(count), C.byref(pruned)))
         k = int(count.value)
         return v[:k].copy(), lo[:k].copy(), hi[:k].copy(), bool(pruned.value)
@@ -787,9 +757,7 @@ class Solution:
 
     def fix_info(self):
         """Counters of the last cutoff_bounds / fix_vars / unfix_vars call (mlp_fix_info) as a dict."""
-        r = MlpFixInfo()
-        _raise(lib().mlp_solution_fix_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpFixInfo._fields_}
+        return self._report(lib().mlp_solution_fix_info, MlpFixInfo)
 
     # ---- new bounds for structural variables (include/minilp_hip.h: mlp_solution_set_var_bounds ...; semantics there)
     def set_var_bounds(self, vars, lo, hi):
@@ -812,8 +780,7 @@ class Solution:
         vm = None if integer_vars is None else self._int_mask(integer_vars, n)
         h = self._take()
         count, pruned = C.c_uint64(), C.c_int()
-        _raise(lib().mlp_solution_tighten_by_reduced_cost(C.byref(h), float(cutoff), None if vm is None else _p(vm, C.c_uint8),
-                                                          n if vm is None else len(vm), C.byref(count), C.byref(pruned)))
+        _raise(lib().mlp_solution_tighten_by_reduced_cost(C.byref(h), float(cutoff), *self._mask_args(vm, n), C.byref(count), C.byref(pruned)))
         return Solution(h), int(count.value), bool(pruned.value)
 
     def var_bounds(self, vars=None):
@@ -826,9 +793,7 @@ class Solution:
 
     def bounds_info(self):
         """Counters of the last set_var_bounds / tighten_by_reduced_cost call (mlp_bounds_info) as a dict."""
-        r = MlpBoundsInfo()
-        _raise(lib().mlp_solution_bounds_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpBoundsInfo._fields_}
+        return self._report(lib().mlp_solution_bounds_info, MlpBoundsInfo)
 
     # ---- bound propagation from row activities (include/minilp_hip.h: mlp_solution_propagate_bounds ...; semantics there)
     def propagate_bounds(self, integer_vars=None, max_rounds=10):
@@ -841,8 +806,7 @@ class Solution:
         vm = None if integer_vars is None else self._int_mask(integer_vars, n)
         v, lo, hi = np.zeros(n, dtype=np.uint32), np.zeros(n), np.zeros(n)
         count, infeasible = C.c_uint64(), C.c_int()
-        _raise(lib().mlp_solution_propagate_bounds(self._h, None if vm is None else _p(vm, C.c_uint8), n if vm is None else len(vm),
-                                                   int(max_rounds), _p(v, C.c_uint32), _p(lo, C.c_double), _p(hi, C.c_double), n,
+        _raise(lib().mlp_solution_propagate_bounds(self._h, *self._mask_args(vm, n), int(max_rounds), _p(v, C.c_uint32), _p(lo, C.c_double), _p(hi, C.c_double), n,
                                                    C.byref(count), C.byref(infeasible)))
         k = int(count.value)
         return v[:k].copy(), lo[:k].copy(), hi[:k].copy(), bool(infeasible.value)
@@ -854,22 +818,16 @@ class Solution:
         vm = None if integer_vars is None else self._int_mask(integer_vars, n)
         h = self._take()
         count, infeasible = C.c_uint64(), C.c_int()
-        _raise(lib().mlp_solution_tighten_by_propagation(C.byref(h), None if vm is None else _p(vm, C.c_uint8),
-                                                         n if vm is None else len(vm), int(max_rounds), C.byref(count),
-                                                         C.byref(infeasible)))
+        _raise(lib().mlp_solution_tighten_by_propagation(C.byref(h), *self._mask_args(vm, n), int(max_rounds), C.byref(count), C.byref(infeasible)))
         return Solution(h), int(count.value), bool(infeasible.value)
 
     def propagate_info(self):
         """Counters of the last propagate_bounds / tighten_by_propagation call (mlp_propagate_info) as a dict."""
-        r = MlpPropagateInfo()
-        _raise(lib().mlp_solution_propagate_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpPropagateInfo._fields_}
+        return self._report(lib().mlp_solution_propagate_info, MlpPropagateInfo)
 
     def cut_info(self):
         """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""
-        r = MlpCutInfo()
-        _raise(lib().mlp_solution_cut_info(self._h, C.byref(r)))
-        return {n: getattr(r, n) for n, _ in MlpCutInfo._fields_}
+        return self._report(lib().mlp_solution_cut_info, MlpCutInfo)
 
     def save_basis(self, mode=2):
         """Basis checkpoint as bytes (include/minilp_hip.h): 0 sets + flags + x_N, 1 + f32 weights, 2 full f64 state."""

@@ -19,33 +19,19 @@ struct mlp_solution {
     // dual values / reduced costs / certificate of the current state (mlp_solution_dual_values ...), computed once per state
     bool duals_valid = false;
     Engine::Duals duals;
-    Engine::RangingInfo ranging;  // of the last mlp_solution_cost_ranging / mlp_solution_rhs_ranging call
-    Engine::CutInfo cuts;         // of the last mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts call
-    Engine::TableauInfo tableau;  // of the last tableau call
-    Engine::GmiInfo gmi;          // of the last mlp_solution_add_gmi_cuts call
-    Engine::BranchInfo branch;    // of the last mlp_solution_branch_penalties call
-    Engine::FixInfo fix;          // of the last mlp_solution_cutoff_bounds / mlp_solution_fix_vars / mlp_solution_unfix_vars call
-    Engine::BoundsInfo bounds;    // of the last mlp_solution_set_var_bounds / mlp_solution_tighten_by_reduced_cost call
-    Engine::PropagateInfo prop;   // of the last mlp_solution_propagate_bounds / mlp_solution_tighten_by_propagation call
+    Engine::RangingInfo ranging{};  // of the last mlp_solution_cost_ranging / mlp_solution_rhs_ranging call
+    Engine::CutInfo cuts{};         // of the last mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts call
+    Engine::TableauInfo tableau{};  // of the last tableau call
+    Engine::GmiInfo gmi{};          // of the last mlp_solution_add_gmi_cuts call
+    Engine::BranchInfo branch{};    // of the last mlp_solution_branch_penalties call
+    Engine::FixInfo fix{};          // of the last mlp_solution_cutoff_bounds / mlp_solution_fix_vars / mlp_solution_unfix_vars call
+    Engine::BoundsInfo bounds{};    // of the last mlp_solution_set_var_bounds / mlp_solution_tighten_by_reduced_cost call
+    Engine::PropagateInfo prop{};   // of the last mlp_solution_propagate_bounds / mlp_solution_tighten_by_propagation call
     std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
     std::vector<uint32_t> tab_indices;
     std::vector<double> tab_values;
     ~mlp_solution() { delete eng; }
 };
-// every entry point that can change the state of a solution drops the cached duals
-static void stale(mlp_solution* s) {
-    if (s) s->duals_valid = false;
-}
-static const Engine::Duals& duals_of(mlp_solution* s) {
-    if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
-    // (any solution sharding was enabled on, a one-rank pump included: its pivots belong to the collective)
-    if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "duals are not available on a sharded solution");
-    if (!s->duals_valid) {
-        s->eng->compute_duals(s->duals);
-        s->duals_valid = true;
-    }
-    return s->duals;
-}
 struct mlp_mps {
     MpsData d;
 };
@@ -67,25 +53,90 @@ static int guarded(F f) {
         return MLP_EINVAL;
     }
 }
-static void refuse_if_sharded(mlp_solution* s) {
-    if (s->eng->sharded()) throw MlpError(MLP_EINVAL, "not available on a sharded solution");
+
+// ---- the guards of the entry points ("The boundary"): one per kind
+// Every entry point that takes a handle which a failed mutator may have consumed starts here.  `refuse`: which solutions the call is not
+// available on, `what`: the subject of that refusal ("the tableau is ").
+enum Refuse {
+    NOTHING,        // any live handle
+    SHARDED,        // a solution sharded over several ranks
+    SHARDING_ON,    // any solution sharding was enabled on, a one-rank pump included: its pivots belong to the collective
+};
+static mlp_solution& live(const mlp_solution* s, Refuse refuse, const char* what) {
+    if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+    if (refuse != NOTHING && (s->eng->sharded() || (refuse == SHARDING_ON && s->eng->transport != "none")))
+        throw MlpError(MLP_EINVAL, std::string(what) + "not available on a sharded solution");
+    return *const_cast<mlp_solution*>(s);
 }
-static void require(mlp_solution** s) {
-    if (!s || !*s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
-}
-static int consume_on_error(mlp_solution** s, int st) {  // lib.rs:359, 385
+// A mutator (mlp_solution**): f(solution) runs on a live, unsharded handle; any failure frees the solution and clears the handle
+// (lib.rs:359, 385).
+template <class F>
+static int mutate(mlp_solution** s, F f) {
+    const int st = guarded([&] { f(live(s ? *s : nullptr, SHARDED, "")); });
     if (st != 0 && s && *s) {
         delete *s;
         *s = nullptr;
     }
     return st;
 }
+// Whatever can change the state of a solution drops the cached duals; a mutator that is about to re-solve also lifts the pivot budget
+// of the initial solve.  Called once the arguments have passed and the call is not a no-op.
+static void drop_cached_duals(mlp_solution* s) {
+    if (s) s->duals_valid = false;
+}
+static void begin_change(mlp_solution& s) {
+    s.eng->pivot_budget = -1;
+    drop_cached_duals(&s);
+}
+// The engine-level controls (continue, stepping, re-inversion, recomputation): a non-NULL handle, the cached duals dropped.
+static Engine* control(mlp_solution* s) {
+    if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
+    drop_cached_duals(s);
+    return s->eng;
+}
+static const Engine::Duals& duals_of(const mlp_solution* cs) {
+    mlp_solution& s = live(cs, SHARDING_ON, "duals are ");
+    if (!s.duals_valid) {
+        s.eng->compute_duals(s.duals);
+        s.duals_valid = true;
+    }
+    return s.duals;
+}
+// A report of the last call of its family: a copy of the struct the engine filled (engine.h names the public structs).
+template <class T>
+static int report(const mlp_solution* s, T mlp_solution::*which, T* out, const char* null_text) {
+    return guarded([&] {
+        if (!s || !out) throw MlpError(MLP_EINVAL, null_text);
+        *out = s->*which;
+    });
+}
+// A list of structural variables as the engine takes it (each index is checked as it is read, nothing is sized by n).
+static std::vector<int> var_list(const mlp_solution& s, const uint32_t* vars, uint64_t n, const char* out_of_range) {
+    std::vector<int> v;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (vars[i] >= (uint32_t)s.eng->num_vars) throw MlpError(MLP_EINVAL, out_of_range);
+        v.push_back((int)vars[i]);
+    }
+    return v;
+}
+// A (vars, lo, hi) list for the caller: the count is always set; a cap below it or a NULL array refuses and writes nothing.
+static void copy_bound_list(const std::string& who, const std::vector<uint32_t>& v, const std::vector<double>& lo, const std::vector<double>& hi,
+                            uint32_t* vars, double* new_lo, double* new_hi, uint64_t cap, uint64_t* count) {
+    *count = (uint64_t)v.size();
+    if (cap < *count) throw MlpError(MLP_EINVAL, who + ": cap is below the count (num_vars always suffices)");
+    if (*count && (!vars || !new_lo || !new_hi)) throw MlpError(MLP_EINVAL, who + ": NULL output");
+    if (*count) {
+        std::memcpy(vars, v.data(), sizeof(uint32_t) * v.size());
+        std::memcpy(new_lo, lo.data(), sizeof(double) * v.size());
+        std::memcpy(new_hi, hi.data(), sizeof(double) * v.size());
+    }
+}
 
 template <class I>
 static int ranging_call(const mlp_solution* cs, int kind, const I* which, uint64_t n, double* lo, double* hi) {
     return guarded([&] {
+        const Engine::Duals& d = duals_of(cs);  // (refuses a NULL handle and a sharded solution; the reduced costs come from the cached read)
         mlp_solution* s = const_cast<mlp_solution*>(cs);
-        const Engine::Duals& d = duals_of(s);  // (refuses a NULL handle and a sharded solution; the reduced costs come from the cached read)
         const uint64_t all = kind == 0 ? (uint64_t)s->eng->num_vars : (uint64_t)s->eng->num_constraints();
         if (!which && n != all) throw MlpError(MLP_EINVAL, "ranging: without an index list the length must be the number of variables / constraints");
         if (n && (!lo || !hi)) throw MlpError(MLP_EINVAL, "ranging: NULL output");
@@ -96,12 +147,7 @@ static int ranging_call(const mlp_solution* cs, int kind, const I* which, uint64
 }
 
 // the tableau reads: refuse a NULL handle and a sharded solution (a one-rank pump included), check the list and the caller's buffer
-static mlp_solution* tableau_handle(const mlp_solution* cs) {
-    mlp_solution* s = const_cast<mlp_solution*>(cs);
-    if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
-    if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "the tableau is not available on a sharded solution");
-    return s;
-}
+static mlp_solution* tableau_handle(const mlp_solution* cs) { return &live(cs, SHARDING_ON, "the tableau is "); }
 static std::vector<uint64_t> tableau_list(const uint64_t* idx, uint64_t n, const double* out, uint64_t out_len, uint64_t row_len) {
     if (n && !idx) throw MlpError(MLP_EINVAL, "tableau: NULL index list");
     if (out_len != n * row_len || (out_len && !out)) throw MlpError(MLP_EINVAL, "tableau: the output length must be n times the row length");
@@ -223,12 +269,11 @@ int mlp_solution_set_sampling(mlp_solution* s, int every_iteration) {
     });
 }
 int mlp_solution_continue(mlp_solution* s, int64_t budget) {
-        stale(s);
     return guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
-        s->eng->pivot_budget = budget;
-        s->eng->budget_exhausted = false;
-        s->eng->initial_solve();
+        Engine* e = control(s);
+        e->pivot_budget = budget;
+        e->budget_exhausted = false;
+        e->initial_solve();
     });
 }
 static void copy_info(const Engine::StepInfo& si, mlp_iter_info* out) {
@@ -241,10 +286,8 @@ static void copy_info(const Engine::StepInfo& si, mlp_iter_info* out) {
 int mlp_engine_open(mlp_solution* s, mlp_iter_info* out) {
     int status = MLP_EINVAL;
     int rc = guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
         Engine::StepInfo si{};
-        stale(s);
-        status = s->eng->step_open(&si);
+        status = control(s)->step_open(&si);
         copy_info(si, out);
     });
     return rc != 0 ? (rc > 0 ? MLP_EINVAL : rc) : status;
@@ -252,10 +295,8 @@ int mlp_engine_open(mlp_solution* s, mlp_iter_info* out) {
 int mlp_engine_stage(mlp_solution* s, int stage, mlp_iter_info* out) {
     int status = MLP_EINVAL;
     int rc = guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
         Engine::StepInfo si{};
-        stale(s);
-        status = s->eng->step_stage(stage, &si);
+        status = control(s)->step_stage(stage, &si);
         copy_info(si, out);
     });
     return rc != 0 ? (rc > 0 ? MLP_EINVAL : rc) : status;
@@ -263,23 +304,20 @@ int mlp_engine_stage(mlp_solution* s, int stage, mlp_iter_info* out) {
 int mlp_solution_budget_exhausted(const mlp_solution* s) { return (s && s->eng->budget_exhausted) ? 1 : 0; }
 int mlp_solution_reinvert(mlp_solution* s, double* max_diff) {
     return guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
-        stale(s);
-        double d = s->eng->reinvert(true);
+        double d = control(s)->reinvert(true);
         if (max_diff) *max_diff = d;
     });
 }
 
 int mlp_solution_recompute_basic_values(mlp_solution* s) {
     return guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution");
         // x_B, then the objective of the recomputed point (and the reduced costs with it: solver.rs:1199-1231), so that
         // mlp_solution_objective and the values agree afterwards
         // — except inside the artificial-objective feasibility phase of a budget-paused solve (d = +-1 / 0 there: initial_solve
         // itself never recomputes d on a budget resume); the basic values are recomputed, d and the objective are left alone
-        stale(s);
-        s->eng->recalc_basic_vals();
-        if (!s->eng->in_artificial_phase()) s->eng->refresh_objective();
+        Engine* e = control(s);
+        e->recalc_basic_vals();
+        if (!e->in_artificial_phase()) e->refresh_objective();
     });
 }
 uint32_t mlp_abi_version(void) { return MLP_ABI_VERSION; }
@@ -330,9 +368,7 @@ int mlp_solution_certificate(mlp_solution* s, mlp_certificate* out) {
 // ---- basis status, cost / rhs ranging (ranging.inc)
 int mlp_solution_basis_status(const mlp_solution* cs, int32_t* var_status, uint32_t n_vars, int32_t* cons_status, uint64_t n_cons) {
     return guarded([&] {
-        mlp_solution* s = const_cast<mlp_solution*>(cs);
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
-        if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "the basis status is not available on a sharded solution");
+        mlp_solution* s = &live(cs, SHARDING_ON, "the basis status is ");
         if ((int)n_vars != s->eng->num_vars || n_cons != s->eng->num_constraints() || (n_vars && !var_status) || (n_cons && !cons_status))
             throw MlpError(MLP_EINVAL, "basis_status: lengths must be mlp_solution_num_vars and mlp_solution_num_constraints");
         std::vector<int32_t> v, c;
@@ -347,21 +383,14 @@ int mlp_solution_cost_ranging(const mlp_solution* s, const uint32_t* vars, uint6
 int mlp_solution_rhs_ranging(const mlp_solution* s, const uint64_t* cons, uint64_t n, double* lo, double* hi) {
     return ranging_call(s, 1, cons, n, lo, hi);
 }
-int mlp_solution_ranging_info(const mlp_solution* s, mlp_ranging_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / ranging info");
-        std::memset(out, 0, sizeof(*out));
-        out->requests = s->ranging.requests; out->solves = s->ranging.solves; out->batches = s->ranging.batches;
-        out->bytes = s->ranging.bytes; out->device_ms = s->ranging.device_ms;
-    });
-}
+int mlp_solution_ranging_info(const mlp_solution* s, mlp_ranging_info* out) { return report(s, &mlp_solution::ranging, out, "NULL solution / ranging info"); }
 uint64_t mlp_ranging_info_size(void) { return (uint64_t)sizeof(mlp_ranging_info); }
 uint64_t mlp_stats_size(void) { return (uint64_t)sizeof(mlp_stats); }
 
 int mlp_solution_enable_sharding(mlp_solution* s, int rank, int world, const char* shm_name) {
     return guarded([&] {
         if (!s || !shm_name) throw MlpError(MLP_EINVAL, "NULL solution / rendezvous name");
-        stale(s);
+        drop_cached_duals(s);
         s->eng->enable_sharding(rank, world, shm_name);
     });
 }
@@ -369,7 +398,7 @@ int mlp_solution_enable_sharding(mlp_solution* s, int rank, int world, const cha
 int mlp_solution_enable_sharding_ex(mlp_solution* s, int rank, int world, const char* shm_name, const char* transport, const void* rccl_id) {
     return guarded([&] {
         if (!s || !shm_name) throw MlpError(MLP_EINVAL, "NULL solution / rendezvous name");
-        stale(s);
+        drop_cached_duals(s);
         s->eng->enable_sharding(rank, world, shm_name, transport, rccl_id);
     });
 }
@@ -400,108 +429,78 @@ double mlp_solution_objective(const mlp_solution* s) {  // lib.rs:334-339
 uint32_t mlp_solution_num_vars(const mlp_solution* s) { return s ? (uint32_t)s->eng->num_vars : 0; }
 int mlp_solution_var_value(const mlp_solution* s, uint32_t var, double* out) {
     return guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+        live(s, NOTHING, "");
         if ((int)var >= s->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:345)");
         *out = s->eng->get_value((int)var);
     });
 }
 int mlp_solution_values(const mlp_solution* s, double* out, uint32_t n) {
     return guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+        live(s, NOTHING, "");
         if ((int)n > s->eng->num_vars) throw MlpError(MLP_EINVAL, "too many values requested");
         s->eng->get_values(out, (int)n);
     });
 }
-int mlp_solution_add_constraint(mlp_solution** s, const uint32_t* vars, const double* coeffs, uint64_t k, int op, double rhs) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
+int mlp_solution_add_constraint(mlp_solution** h, const uint32_t* vars, const double* coeffs, uint64_t k, int op, double rhs) {
+    return mutate(h, [&](mlp_solution& s) {
         ProblemData tmp;
-        tmp.obj.resize((*s)->eng->num_vars);  // lib.rs:376: dimension = num_vars
+        tmp.obj.resize(s.eng->num_vars);  // lib.rs:376: dimension = num_vars
         tmp.add_constraint(vars, coeffs, k, op, rhs);
-        refuse_if_sharded(*s);
-        (*s)->eng->pivot_budget = -1;
-        stale(*s);
-        (*s)->eng->add_constraint(tmp.cons[0]);
-    }));
+        begin_change(s);
+        s.eng->add_constraint(tmp.cons[0]);
+    });
 }
-int mlp_solution_fix_var(mlp_solution** s, uint32_t var, double val) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        if ((int)var >= (*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:391)");
-        refuse_if_sharded(*s);
-        (*s)->eng->pivot_budget = -1;
-        stale(*s);
-        (*s)->eng->fix_var((int)var, val);
-    }));
+int mlp_solution_fix_var(mlp_solution** h, uint32_t var, double val) {
+    return mutate(h, [&](mlp_solution& s) {
+        if ((int)var >= s.eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:391)");
+        begin_change(s);
+        s.eng->fix_var((int)var, val);
+    });
 }
-int mlp_solution_unfix_var(mlp_solution** s, uint32_t var, int* was_fixed) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        if ((int)var >= (*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:400)");
-        refuse_if_sharded(*s);
-        (*s)->eng->pivot_budget = -1;
-        stale(*s);
-        *was_fixed = (*s)->eng->unfix_var((int)var) ? 1 : 0;
-    }));
+int mlp_solution_unfix_var(mlp_solution** h, uint32_t var, int* was_fixed) {
+    return mutate(h, [&](mlp_solution& s) {
+        if ((int)var >= s.eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:400)");
+        begin_change(s);
+        *was_fixed = s.eng->unfix_var((int)var) ? 1 : 0;
+    });
 }
-int mlp_solution_add_gomory_cut(mlp_solution** s, uint32_t var) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        if ((int)var >= (*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:420)");
-        refuse_if_sharded(*s);
-        (*s)->eng->pivot_budget = -1;
-        stale(*s);
-        (*s)->eng->add_gomory_cut((int)var);
-    }));
+int mlp_solution_add_gomory_cut(mlp_solution** h, uint32_t var) {
+    return mutate(h, [&](mlp_solution& s) {
+        if ((int)var >= s.eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:420)");
+        begin_change(s);
+        s.eng->add_gomory_cut((int)var);
+    });
 }
 
 // ---- a round of cuts in one call (cuts.inc)
-int mlp_solution_add_constraints_csr(mlp_solution** s, uint64_t m, const uint64_t* indptr, const uint32_t* vars, const double* coeffs,
+int mlp_solution_add_constraints_csr(mlp_solution** h, uint64_t m, const uint64_t* indptr, const uint32_t* vars, const double* coeffs,
                                      const int32_t* cmp_ops, const double* rhs) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
+    return mutate(h, [&](mlp_solution& s) {
         if (m && (!indptr || !cmp_ops || !rhs)) throw MlpError(MLP_EINVAL, "add_constraints_csr: NULL array");
         ProblemData tmp;
-        tmp.obj.resize((*s)->eng->num_vars);  // lib.rs:376: dimension = num_vars
+        tmp.obj.resize(s.eng->num_vars);  // lib.rs:376: dimension = num_vars
         for (uint64_t i = 0; i < m; ++i) {
             if (indptr[i + 1] < indptr[i]) throw MlpError(MLP_EINVAL, "add_constraints_csr: indptr must not decrease");
             if (indptr[i + 1] > indptr[i] && (!vars || !coeffs)) throw MlpError(MLP_EINVAL, "add_constraints_csr: NULL array");
             tmp.add_constraint(vars + indptr[i], coeffs + indptr[i], indptr[i + 1] - indptr[i], cmp_ops[i], rhs[i]);
         }
-        (*s)->cuts = Engine::CutInfo();
+        s.cuts = Engine::CutInfo();
         if (m == 0) return;
-        (*s)->eng->pivot_budget = -1;
-        stale(*s);
-        (*s)->eng->add_constraints(std::move(tmp.cons), (*s)->cuts);
-    }));
-}
-int mlp_solution_add_gomory_cuts(mlp_solution** s, const uint32_t* vars, uint64_t n) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
-        if (n && !vars) throw MlpError(MLP_EINVAL, "add_gomory_cuts: NULL variable list");
-        std::vector<int> v((size_t)n);
-        for (uint64_t i = 0; i < n; ++i) {
-            if (vars[i] >= (uint32_t)(*s)->eng->num_vars) throw MlpError(MLP_EINVAL, "variable out of range (lib.rs:420)");
-            v[i] = (int)vars[i];
-        }
-        (*s)->cuts = Engine::CutInfo();
-        if (n == 0) return;
-        (*s)->eng->pivot_budget = -1;
-        stale(*s);
-        (*s)->eng->add_gomory_cuts(v, (*s)->cuts);
-    }));
-}
-int mlp_solution_cut_info(const mlp_solution* s, mlp_cut_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / cut info");
-        const Engine::CutInfo& c = s->cuts;
-        out->rows = c.rows; out->rows_without_terms = c.rows_without_terms; out->nnz = c.nnz; out->batches = c.batches;
-        out->relayouts = c.relayouts; out->reinversions = c.reinversions; out->pivots = c.pivots;
-        out->bytes = c.bytes; out->device_ms = c.device_ms; out->wall_ms = c.wall_ms;
+        begin_change(s);
+        s.eng->add_constraints(std::move(tmp.cons), s.cuts);
     });
 }
+int mlp_solution_add_gomory_cuts(mlp_solution** h, const uint32_t* vars, uint64_t n) {
+    return mutate(h, [&](mlp_solution& s) {
+        if (n && !vars) throw MlpError(MLP_EINVAL, "add_gomory_cuts: NULL variable list");
+        const std::vector<int> v = var_list(s, vars, n, "variable out of range (lib.rs:420)");
+        s.cuts = Engine::CutInfo();
+        if (n == 0) return;
+        begin_change(s);
+        s.eng->add_gomory_cuts(v, s.cuts);
+    });
+}
+int mlp_solution_cut_info(const mlp_solution* s, mlp_cut_info* out) { return report(s, &mlp_solution::cuts, out, "NULL solution / cut info"); }
 uint64_t mlp_cut_info_size(void) { return (uint64_t)sizeof(mlp_cut_info); }
 
 // ---- reading the tableau (tableau.inc)
@@ -570,51 +569,27 @@ int mlp_solution_basis_solve(const mlp_solution* cs, int transpose, const double
         s->eng->basis_solve(transpose != 0, rhs, (size_t)n, out, s->tableau);
     });
 }
-int mlp_solution_tableau_info(const mlp_solution* s, mlp_tableau_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / tableau info");
-        std::memset(out, 0, sizeof(*out));
-        const Engine::TableauInfo& t = s->tableau;
-        out->requests = t.requests; out->solves = t.solves; out->batches = t.batches; out->nnz = t.nnz;
-        out->bytes = t.bytes; out->device_ms = t.device_ms;
-    });
-}
+int mlp_solution_tableau_info(const mlp_solution* s, mlp_tableau_info* out) { return report(s, &mlp_solution::tableau, out, "NULL solution / tableau info"); }
 uint64_t mlp_tableau_info_size(void) { return (uint64_t)sizeof(mlp_tableau_info); }
 
 // ---- a round of Gomory mixed-integer cuts (gmi.inc)
-int mlp_solution_add_gmi_cuts(mlp_solution** s, const uint32_t* vars, uint64_t n, const uint8_t* var_is_int, uint32_t num_vars,
+int mlp_solution_add_gmi_cuts(mlp_solution** h, const uint32_t* vars, uint64_t n, const uint8_t* var_is_int, uint32_t num_vars,
                               const uint8_t* con_is_int, uint64_t num_constraints, double away, int32_t* status_out) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
-        Engine* e = (*s)->eng;
+    return mutate(h, [&](mlp_solution& s) {
+        Engine* e = s.eng;
         if (n && !vars) throw MlpError(MLP_EINVAL, "add_gmi_cuts: NULL variable list");
         if (num_vars != (uint32_t)e->num_vars || (num_vars && !var_is_int)) throw MlpError(MLP_EINVAL, "add_gmi_cuts: var_is_int must have num_vars entries");
         if (con_is_int && num_constraints != (uint64_t)e->num_constraints())
             throw MlpError(MLP_EINVAL, "add_gmi_cuts: con_is_int must have num_constraints entries");
-        if (!(away > 0.0 && away <= 0.5)) throw MlpError(MLP_EINVAL, "add_gmi_cuts: away must be in (0, 0.5]");
-        std::vector<int> v;
-        for (uint64_t i = 0; i < n; ++i) {  // (each index is checked as it is read, nothing is sized by n)
-            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "add_gmi_cuts: variable out of range");
-            v.push_back((int)vars[i]);
-        }
-        (*s)->cuts = Engine::CutInfo();
-        (*s)->gmi = Engine::GmiInfo();
+        const std::vector<int> v = var_list(s, vars, n, "add_gmi_cuts: variable out of range");
+        s.cuts = Engine::CutInfo();
+        s.gmi = Engine::GmiInfo();
         if (n == 0) return;
-        e->pivot_budget = -1;
-        stale(*s);
-        e->add_gmi_cuts(v, var_is_int, con_is_int, away, status_out, (*s)->cuts, (*s)->gmi);
-    }));
-}
-int mlp_solution_gmi_info(const mlp_solution* s, mlp_gmi_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / gmi info");
-        std::memset(out, 0, sizeof(*out));
-        const Engine::GmiInfo& g = s->gmi;
-        out->requests = g.requests; out->rows = g.rows; out->skipped_fraction = g.skipped_fraction; out->skipped_free = g.skipped_free;
-        out->nnz = g.nnz; out->batches = g.batches; out->bytes = g.bytes; out->device_ms = g.device_ms;
+        begin_change(s);
+        e->add_gmi_cuts(v, var_is_int, con_is_int, away, status_out, s.cuts, s.gmi);
     });
 }
+int mlp_solution_gmi_info(const mlp_solution* s, mlp_gmi_info* out) { return report(s, &mlp_solution::gmi, out, "NULL solution / gmi info"); }
 uint64_t mlp_gmi_info_size(void) { return (uint64_t)sizeof(mlp_gmi_info); }
 
 // ---- branching penalties (branch.inc)
@@ -622,253 +597,150 @@ int mlp_solution_branch_penalties(const mlp_solution* cs, const uint32_t* vars, 
                                   const uint8_t* con_is_int, uint64_t num_constraints, double* down, double* up, int64_t* down_col,
                                   int64_t* up_col, double* frac, int32_t* status) {
     return guarded([&] {
-        mlp_solution* s = const_cast<mlp_solution*>(cs);
-        const Engine::Duals& d = duals_of(s);  // (refuses a NULL handle and a sharded solution; the reduced costs come from the cached read)
-        Engine* e = s->eng;
+        const Engine::Duals& d = duals_of(cs);  // (refuses a NULL handle and a sharded solution; the reduced costs come from the cached read)
+        mlp_solution& s = *const_cast<mlp_solution*>(cs);
+        Engine* e = s.eng;
         if (n && !vars) throw MlpError(MLP_EINVAL, "branch_penalties: NULL variable list");
         if (n && (!down || !up || !down_col || !up_col || !frac || !status)) throw MlpError(MLP_EINVAL, "branch_penalties: NULL output");
         if (var_is_int ? num_vars != (uint32_t)e->num_vars : con_is_int != nullptr)
             throw MlpError(MLP_EINVAL, "branch_penalties: var_is_int must have num_vars entries (and con_is_int needs it)");
         if (con_is_int && num_constraints != e->num_constraints())
             throw MlpError(MLP_EINVAL, "branch_penalties: con_is_int must have num_constraints entries");
-        std::vector<int> v((size_t)n);
-        for (uint64_t i = 0; i < n; ++i) {
-            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "branch_penalties: variable out of range");
-            v[i] = (int)vars[i];
-        }
-        e->branch_penalties(v, var_is_int, con_is_int, d, down, up, down_col, up_col, frac, status, s->branch);
+        const std::vector<int> v = var_list(s, vars, n, "branch_penalties: variable out of range");
+        e->branch_penalties(v, var_is_int, con_is_int, d, down, up, down_col, up_col, frac, status, s.branch);
     });
 }
-int mlp_solution_branch_info(const mlp_solution* s, mlp_branch_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / branch info");
-        std::memset(out, 0, sizeof(*out));
-        out->requests = s->branch.requests; out->solves = s->branch.solves; out->batches = s->branch.batches;
-        out->bytes = s->branch.bytes; out->device_ms = s->branch.device_ms;
-    });
-}
+int mlp_solution_branch_info(const mlp_solution* s, mlp_branch_info* out) { return report(s, &mlp_solution::branch, out, "NULL solution / branch info"); }
 uint64_t mlp_branch_info_size(void) { return (uint64_t)sizeof(mlp_branch_info); }
 
 // ---- reduced-cost bounds from a cutoff, batched fixing (fixing.inc)
 int mlp_solution_cutoff_bounds(const mlp_solution* cs, double cutoff, const uint8_t* var_is_int, uint32_t num_vars, uint32_t* vars,
                                double* new_lo, double* new_hi, uint64_t cap, uint64_t* count, int* pruned) {
     return guarded([&] {
-        mlp_solution* s = const_cast<mlp_solution*>(cs);
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
-        if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "cutoff_bounds is not available on a sharded solution");
-        Engine* e = s->eng;
+        mlp_solution& s = live(cs, SHARDING_ON, "cutoff_bounds is ");
+        Engine* e = s.eng;
         if (!count || !pruned) throw MlpError(MLP_EINVAL, "cutoff_bounds: NULL count / pruned");
         *count = 0;
         *pruned = 0;
         if (std::isnan(cutoff)) throw MlpError(MLP_EINVAL, "cutoff_bounds: the cutoff is NaN");
         if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "cutoff_bounds: num_vars must be mlp_solution_num_vars");
-        if (!e->solved()) throw MlpError(MLP_EINVAL, "cutoff_bounds: model not solved");
-        const double obj = e->cur_obj_val();                         // internal: min c^.x
-        const double user = e->direction == 1 ? -obj : obj;          // what mlp_solution_objective returns
-        const double g = e->direction == 1 ? user - cutoff : cutoff - user;  // exact: no tolerance
-        if (std::isnan(g)) throw MlpError(MLP_EINVAL, "cutoff_bounds: the gap is NaN");
-        Engine::FixInfo info;
+        const double g = e->cutoff_gap(cutoff, "cutoff_bounds");
+        Engine::FixInfo info{};
         if (g < 0.0) {  // the node is worse than the cutoff
             *pruned = 1;
-            s->fix = info;
+            s.fix = info;
             return;
         }
         std::vector<uint32_t> v;
         std::vector<double> lo, hi;
         e->cutoff_bounds(g, var_is_int, v, lo, hi, info);
-        *count = (uint64_t)v.size();
-        if (cap < *count) throw MlpError(MLP_EINVAL, "cutoff_bounds: cap is below the count (num_vars always suffices)");
-        if (*count && (!vars || !new_lo || !new_hi)) throw MlpError(MLP_EINVAL, "cutoff_bounds: NULL output");
-        if (*count) {
-            std::memcpy(vars, v.data(), sizeof(uint32_t) * v.size());
-            std::memcpy(new_lo, lo.data(), sizeof(double) * v.size());
-            std::memcpy(new_hi, hi.data(), sizeof(double) * v.size());
-        }
-        s->fix = info;
+        copy_bound_list("cutoff_bounds", v, lo, hi, vars, new_lo, new_hi, cap, count);
+        s.fix = info;
     });
 }
-int mlp_solution_fix_vars(mlp_solution** s, const uint32_t* vars, const double* vals, uint64_t n) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
-        Engine* e = (*s)->eng;
+int mlp_solution_fix_vars(mlp_solution** h, const uint32_t* vars, const double* vals, uint64_t n) {
+    return mutate(h, [&](mlp_solution& s) {
         if (n && (!vars || !vals)) throw MlpError(MLP_EINVAL, "fix_vars: NULL list");
-        std::vector<int> v;
-        std::vector<double> x;
-        for (uint64_t i = 0; i < n; ++i) {  // (each index is checked as it is read, nothing is sized by n)
-            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "fix_vars: variable out of range");
-            v.push_back((int)vars[i]);
-            x.push_back(vals[i]);
-        }
-        (*s)->fix = Engine::FixInfo();
+        const std::vector<int> v = var_list(s, vars, n, "fix_vars: variable out of range");
+        s.fix = Engine::FixInfo();
         if (n == 0) return;
-        e->pivot_budget = -1;
-        stale(*s);
-        e->fix_vars(v, x, (*s)->fix);
-    }));
+        begin_change(s);
+        s.eng->fix_vars(v, std::vector<double>(vals, vals + n), s.fix);
+    });
 }
-int mlp_solution_unfix_vars(mlp_solution** s, const uint32_t* vars, uint64_t n, uint64_t* unfixed) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
-        Engine* e = (*s)->eng;
+int mlp_solution_unfix_vars(mlp_solution** h, const uint32_t* vars, uint64_t n, uint64_t* unfixed) {
+    return mutate(h, [&](mlp_solution& s) {
         if (unfixed) *unfixed = 0;
         if (n && !vars) throw MlpError(MLP_EINVAL, "unfix_vars: NULL list");
-        std::vector<int> v;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "unfix_vars: variable out of range");
-            v.push_back((int)vars[i]);
-        }
-        (*s)->fix = Engine::FixInfo();
+        const std::vector<int> v = var_list(s, vars, n, "unfix_vars: variable out of range");
+        s.fix = Engine::FixInfo();
         if (n == 0) return;
-        e->pivot_budget = -1;
-        stale(*s);
-        const uint64_t k = e->unfix_vars(v, (*s)->fix);
+        begin_change(s);
+        const uint64_t k = s.eng->unfix_vars(v, s.fix);
         if (unfixed) *unfixed = k;
-    }));
-}
-int mlp_solution_fix_info(const mlp_solution* s, mlp_fix_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / fix info");
-        std::memset(out, 0, sizeof(*out));
-        const Engine::FixInfo& f = s->fix;
-        out->requests = f.requests; out->nonbasic = f.nonbasic; out->shifted = f.shifted; out->forced_pivots = f.forced_pivots;
-        out->solves = f.solves; out->unfixed = f.unfixed; out->listed = f.listed; out->listed_fixed = f.listed_fixed; out->pivots = f.pivots;
-        out->bytes = f.bytes; out->device_ms = f.device_ms; out->wall_ms = f.wall_ms;
     });
 }
+int mlp_solution_fix_info(const mlp_solution* s, mlp_fix_info* out) { return report(s, &mlp_solution::fix, out, "NULL solution / fix info"); }
 uint64_t mlp_fix_info_size(void) { return (uint64_t)sizeof(mlp_fix_info); }
 
 // ---- new bounds for structural variables (bounds.inc)
-int mlp_solution_set_var_bounds(mlp_solution** s, const uint32_t* vars, const double* lo, const double* hi, uint64_t n) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
-        Engine* e = (*s)->eng;
+int mlp_solution_set_var_bounds(mlp_solution** h, const uint32_t* vars, const double* lo, const double* hi, uint64_t n) {
+    return mutate(h, [&](mlp_solution& s) {
         if (n && (!vars || !lo || !hi)) throw MlpError(MLP_EINVAL, "set_var_bounds: NULL list");
-        std::vector<int> v;
-        std::vector<double> l, h;
-        for (uint64_t i = 0; i < n; ++i) {  // (each index is checked as it is read, nothing is sized by n)
-            if (vars[i] >= (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "set_var_bounds: variable out of range");
-            v.push_back((int)vars[i]);
-            l.push_back(lo[i]);
-            h.push_back(hi[i]);
-        }
-        (*s)->bounds = Engine::BoundsInfo();
+        const std::vector<int> v = var_list(s, vars, n, "set_var_bounds: variable out of range");
+        s.bounds = Engine::BoundsInfo();
         if (n == 0) return;
-        if (!e->solved()) throw MlpError(MLP_EINVAL, "set_var_bounds: model not solved");
-        e->pivot_budget = -1;
-        stale(*s);
-        e->set_var_bounds(v, l, h, (*s)->bounds);
-    }));
+        begin_change(s);
+        s.eng->set_var_bounds(v, std::vector<double>(lo, lo + n), std::vector<double>(hi, hi + n), s.bounds);
+    });
 }
-int mlp_solution_tighten_by_reduced_cost(mlp_solution** s, double cutoff, const uint8_t* var_is_int, uint32_t num_vars, uint64_t* tightened,
+int mlp_solution_tighten_by_reduced_cost(mlp_solution** h, double cutoff, const uint8_t* var_is_int, uint32_t num_vars, uint64_t* tightened,
                                          int* pruned) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
-        Engine* e = (*s)->eng;
-        if (e->transport != "none") throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost is not available on a sharded solution");
+    return mutate(h, [&](mlp_solution& s) {
+        live(&s, SHARDING_ON, "tighten_by_reduced_cost is ");
+        Engine* e = s.eng;
         if (!tightened || !pruned) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: NULL tightened / pruned");
         *tightened = 0;
         *pruned = 0;
         if (std::isnan(cutoff)) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: the cutoff is NaN");
         if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: num_vars must be mlp_solution_num_vars");
-        if (!e->solved()) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: model not solved");
-        const double obj = e->cur_obj_val();                                 // the gap exactly as mlp_solution_cutoff_bounds forms it
-        const double user = e->direction == 1 ? -obj : obj;
-        const double g = e->direction == 1 ? user - cutoff : cutoff - user;
-        if (std::isnan(g)) throw MlpError(MLP_EINVAL, "tighten_by_reduced_cost: the gap is NaN");
-        (*s)->bounds = Engine::BoundsInfo();
+        const double g = e->cutoff_gap(cutoff, "tighten_by_reduced_cost");
+        s.bounds = Engine::BoundsInfo();
         if (g < 0.0) {  // the node is worse than the cutoff: nothing changes
             *pruned = 1;
             return;
         }
-        e->pivot_budget = -1;
-        stale(*s);
-        *tightened = e->tighten_by_reduced_cost(g, var_is_int, (*s)->bounds);
-    }));
+        begin_change(s);
+        *tightened = e->tighten_by_reduced_cost(g, var_is_int, s.bounds);
+    });
 }
 int mlp_solution_var_bounds(const mlp_solution* s, const uint32_t* vars, uint64_t n, double* lo, double* hi) {
     return guarded([&] {
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
+        live(s, NOTHING, "");
         if (!vars && n != (uint64_t)s->eng->num_vars) throw MlpError(MLP_EINVAL, "var_bounds: without a list the length must be the number of variables");
         if (n && (!lo || !hi)) throw MlpError(MLP_EINVAL, "var_bounds: NULL output");
         s->eng->var_bounds(vars, n, lo, hi);
     });
 }
-int mlp_solution_bounds_info(const mlp_solution* s, mlp_bounds_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / bounds info");
-        std::memset(out, 0, sizeof(*out));
-        const Engine::BoundsInfo& f = s->bounds;
-        out->requests = f.requests; out->basic = f.basic; out->nonbasic = f.nonbasic; out->shifted = f.shifted; out->solves = f.solves;
-        out->tightened = f.tightened; out->pivots = f.pivots; out->bytes = f.bytes; out->device_ms = f.device_ms; out->wall_ms = f.wall_ms;
-    });
-}
+int mlp_solution_bounds_info(const mlp_solution* s, mlp_bounds_info* out) { return report(s, &mlp_solution::bounds, out, "NULL solution / bounds info"); }
 uint64_t mlp_bounds_info_size(void) { return (uint64_t)sizeof(mlp_bounds_info); }
 
 // ---- bound propagation from row activities (propagate.inc)
 int mlp_solution_propagate_bounds(const mlp_solution* cs, const uint8_t* var_is_int, uint32_t num_vars, int32_t max_rounds, uint32_t* vars,
                                   double* new_lo, double* new_hi, uint64_t cap, uint64_t* count, int* infeasible) {
     return guarded([&] {
-        mlp_solution* s = const_cast<mlp_solution*>(cs);
-        if (!s) throw MlpError(MLP_EINVAL, "NULL solution (consumed by a failed mutator?)");
-        if (s->eng->sharded() || s->eng->transport != "none") throw MlpError(MLP_EINVAL, "propagate_bounds is not available on a sharded solution");
-        Engine* e = s->eng;
+        mlp_solution& s = live(cs, SHARDING_ON, "propagate_bounds is ");
         if (!count || !infeasible) throw MlpError(MLP_EINVAL, "propagate_bounds: NULL count / infeasible");
         *count = 0;
         *infeasible = 0;
-        if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "propagate_bounds: num_vars must be mlp_solution_num_vars");
-        if (max_rounds < 1 || max_rounds > 64) throw MlpError(MLP_EINVAL, "propagate_bounds: max_rounds must lie in 1..64");
-        Engine::PropagateInfo info;
+        if (num_vars != (uint32_t)s.eng->num_vars) throw MlpError(MLP_EINVAL, "propagate_bounds: num_vars must be mlp_solution_num_vars");
+        Engine::PropagateInfo info{};
         std::vector<uint32_t> v;
         std::vector<double> lo, hi;
         bool inf = false;
-        e->propagate_bounds(var_is_int, (int)max_rounds, v, lo, hi, inf, info);
+        s.eng->propagate_bounds(var_is_int, (int)max_rounds, v, lo, hi, inf, info);
         *infeasible = inf ? 1 : 0;
-        *count = (uint64_t)v.size();
-        if (cap < *count) throw MlpError(MLP_EINVAL, "propagate_bounds: cap is below the count (num_vars always suffices)");
-        if (*count && (!vars || !new_lo || !new_hi)) throw MlpError(MLP_EINVAL, "propagate_bounds: NULL output");
-        if (*count) {
-            std::memcpy(vars, v.data(), sizeof(uint32_t) * v.size());
-            std::memcpy(new_lo, lo.data(), sizeof(double) * v.size());
-            std::memcpy(new_hi, hi.data(), sizeof(double) * v.size());
-        }
-        s->prop = info;
+        copy_bound_list("propagate_bounds", v, lo, hi, vars, new_lo, new_hi, cap, count);
+        s.prop = info;
     });
 }
-int mlp_solution_tighten_by_propagation(mlp_solution** s, const uint8_t* var_is_int, uint32_t num_vars, int32_t max_rounds,
+int mlp_solution_tighten_by_propagation(mlp_solution** h, const uint8_t* var_is_int, uint32_t num_vars, int32_t max_rounds,
                                         uint64_t* tightened, int* infeasible) {
-    return consume_on_error(s, guarded([&] {
-        require(s);
-        refuse_if_sharded(*s);
-        Engine* e = (*s)->eng;
-        if (e->transport != "none") throw MlpError(MLP_EINVAL, "tighten_by_propagation is not available on a sharded solution");
+    return mutate(h, [&](mlp_solution& s) {
+        live(&s, SHARDING_ON, "tighten_by_propagation is ");
         if (!tightened || !infeasible) throw MlpError(MLP_EINVAL, "tighten_by_propagation: NULL tightened / infeasible");
         *tightened = 0;
         *infeasible = 0;
-        if (num_vars != (uint32_t)e->num_vars) throw MlpError(MLP_EINVAL, "tighten_by_propagation: num_vars must be mlp_solution_num_vars");
-        if (max_rounds < 1 || max_rounds > 64) throw MlpError(MLP_EINVAL, "tighten_by_propagation: max_rounds must lie in 1..64");
-        if (!e->solved()) throw MlpError(MLP_EINVAL, "tighten_by_propagation: model not solved");
-        (*s)->bounds = Engine::BoundsInfo();
-        (*s)->prop = Engine::PropagateInfo();
-        e->pivot_budget = -1;
-        stale(*s);
+        if (num_vars != (uint32_t)s.eng->num_vars) throw MlpError(MLP_EINVAL, "tighten_by_propagation: num_vars must be mlp_solution_num_vars");
+        s.bounds = Engine::BoundsInfo();
+        s.prop = Engine::PropagateInfo();
+        begin_change(s);
         bool inf = false;
-        *tightened = e->tighten_by_propagation(var_is_int, (int)max_rounds, inf, (*s)->prop, (*s)->bounds);
+        *tightened = s.eng->tighten_by_propagation(var_is_int, (int)max_rounds, inf, s.prop, s.bounds);
         *infeasible = inf ? 1 : 0;
-    }));
-}
-int mlp_solution_propagate_info(const mlp_solution* s, mlp_propagate_info* out) {
-    return guarded([&] {
-        if (!s || !out) throw MlpError(MLP_EINVAL, "NULL solution / propagate info");
-        std::memset(out, 0, sizeof(*out));
-        const Engine::PropagateInfo& f = s->prop;
-        out->requests = f.requests; out->rounds = f.rounds; out->accepted = f.accepted; out->listed = f.listed;
-        out->listed_fixed = f.listed_fixed; out->bytes = f.bytes; out->device_ms = f.device_ms;
     });
 }
+int mlp_solution_propagate_info(const mlp_solution* s, mlp_propagate_info* out) { return report(s, &mlp_solution::prop, out, "NULL solution / propagate info"); }
 uint64_t mlp_propagate_info_size(void) { return (uint64_t)sizeof(mlp_propagate_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {

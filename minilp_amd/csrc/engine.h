@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/minilp_hip.h"  // the report structs (mlp_cut_info ...) are defined there, once
 #include "kernels.h"
 #include "settings.h"
 
@@ -186,20 +187,14 @@ public:
     // A round of cuts in one call (cuts.inc; include/minilp_hip.h mlp_solution_add_constraints_csr / mlp_solution_add_gomory_cuts): all
     // rows appended with ONE re-layout of the CSC, at most one re-inversion, the edge norms of every new row, ONE re-solve.  The model
     // left behind is that of the single forms called in the same order; only the pivot path of the re-solve differs.
-    struct CutInfo {
-        uint64_t rows = 0, rows_without_terms = 0, nnz = 0, batches = 0, relayouts = 0, reinversions = 0, pivots = 0;
-        double bytes = 0, device_ms = 0, wall_ms = 0;
-    };
+    using CutInfo = mlp_cut_info;  // (the report structs are the public ones: no default initialisers, every declaration value-initialises)
     void add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gomory = false);
     void add_gomory_cuts(const std::vector<int>& vars, CutInfo& info);  // the cut of add_gomory_cut for every listed (basic) variable
     // A round of Gomory mixed-integer cuts (gmi.inc; include/minilp_hip.h mlp_solution_add_gmi_cuts): one cut per listed
     // basic integer variable, all from the basis the call finds, appended through add_constraints.  var_is_int: num_vars marks;
     // con_is_int: num_constraints() marks of the slacks, or nullptr (all slacks continuous); status_out: vars.size() codes (0 emitted,
     // 1 skipped: fraction within away, 2 skipped: free non-basic column in the row), or nullptr.
-    struct GmiInfo {
-        uint64_t requests = 0, rows = 0, skipped_fraction = 0, skipped_free = 0, nnz = 0, batches = 0;
-        double bytes = 0, device_ms = 0;
-    };
+    using GmiInfo = mlp_gmi_info;
     void add_gmi_cuts(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, double away, int32_t* status_out,
                       CutInfo& info, GmiInfo& gmi);
     double get_value(int var);                                              // solver.rs:371-376
@@ -223,31 +218,25 @@ public:
     // Status codes: 0 basic, 1 at lower, 2 at upper, 3 non-basic at neither bound, 4 non-basic fixed.  ranging(): kind 0 = cost ranges of
     // the structural variables idx[], kind 1 = rhs ranges of the constraints idx[], both in the user's sense; du = the duals of the same
     // state.  Reads the state only, like compute_duals.
-    struct RangingInfo {
-        uint64_t requests = 0, solves = 0, batches = 0;
-        double bytes = 0, device_ms = 0;
-    };
+    using RangingInfo = mlp_ranging_info;
     void basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons);
     void ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du, double* lo, double* hi, RangingInfo& info);
     // Branching penalties of the current basis (branch.inc; include/minilp_hip.h mlp_solution_branch_penalties): for every
     // listed structural variable the Driebeek–Tomlin bounds of its down and up branch, the columns that would enter (numbering of the
     // tableau reads, -1: none) and its fraction; status 0 = basic and fractional (served on the device, RG_BATCH per pass over A),
     // 1 = non-basic or integral (zeros).  var_is_int == nullptr: plain penalties.  Reads the state only, like ranging.
-    struct BranchInfo {
-        uint64_t requests = 0, solves = 0, batches = 0;
-        double bytes = 0, device_ms = 0;
-    };
+    using BranchInfo = mlp_branch_info;
     void branch_penalties(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, const Duals& du, double* down,
                           double* up, int64_t* down_col, int64_t* up_col, double* frac, int32_t* status, BranchInfo& info);
     // Reduced-cost bounds from a cutoff and the batched fixing of variables (fixing.inc; include/minilp_hip.h mlp_solution_cutoff_bounds,
     // mlp_solution_fix_vars, mlp_solution_unfix_vars).  FixInfo describes the last of the three calls.
-    struct FixInfo {
-        uint64_t requests = 0, nonbasic = 0, shifted = 0, forced_pivots = 0, solves = 0, unfixed = 0, listed = 0, listed_fixed = 0, pivots = 0;
-        double bytes = 0, device_ms = 0, wall_ms = 0;
-    };
+    using FixInfo = mlp_fix_info;
     bool solved() const { return primal_feasible && dual_feasible && !budget_exhausted; }
-    // g = cutoff - objective in the internal minimisation sense (>= 0, finite); var_is_int: num_vars marks or nullptr.  The list comes
-    // back in ascending variable number.  Reads the state only, like ranging.
+    // g = cutoff - objective in the internal minimisation sense, exact: no tolerance (g < 0: the node is worse than the cutoff).  Refuses
+    // a model that is not solved (the bound is a weak-duality argument: it needs a dual-feasible basis) and a NaN gap, in `who`'s name.
+    double cutoff_gap(double cutoff, const std::string& who);
+    // g from cutoff_gap (>= 0); var_is_int: num_vars marks or nullptr.  The list comes back in ascending variable number.  Reads the state
+    // only, like ranging.
     void cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint32_t>& vars, std::vector<double>& lo, std::vector<double>& hi,
                        FixInfo& info);
     // the model that fix_var(vars[i], vals[i]) for i = 0, 1, ... would leave: the requests non-basic at the basis the call finds are
@@ -256,10 +245,7 @@ public:
     uint64_t unfix_vars(const std::vector<int>& vars, FixInfo& info);  // unfix_var's rule per request, ONE optimize(); returns the released count
     // New bounds for structural variables of a solved model (fixing.inc, bounds.inc; include/minilp_hip.h mlp_solution_set_var_bounds,
     // mlp_solution_tighten_by_reduced_cost).  BoundsInfo describes the last of the two mutators.
-    struct BoundsInfo {
-        uint64_t requests = 0, basic = 0, nonbasic = 0, shifted = 0, solves = 0, tightened = 0, pivots = 0;
-        double bytes = 0, device_ms = 0, wall_ms = 0;
-    };
+    using BoundsInfo = mlp_bounds_info;
     // every non-basic request keeps its side and moves with its bound (one FTRAN for all, none when nothing moves), a basic request
     // only gets its bounds; ONE dual re-solve when a value moved or a basic value now violates its bounds
     void set_var_bounds(const std::vector<int>& vars, const std::vector<double>& lo, const std::vector<double>& hi, BoundsInfo& info);
@@ -270,10 +256,7 @@ public:
     // mlp_solution_tighten_by_propagation).  The read works on any state and reads neither basis nor values: Jacobi
     // rounds over the model's rows, the bounds and the fixed flags; the list comes back in ascending variable number, empty when the
     // rounds prove the model infeasible.
-    struct PropagateInfo {
-        uint64_t requests = 0, rounds = 0, accepted = 0, listed = 0, listed_fixed = 0;
-        double bytes = 0, device_ms = 0;
-    };
+    using PropagateInfo = mlp_propagate_info;
     void propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::vector<uint32_t>& vars, std::vector<double>& lo,
                           std::vector<double>& hi, bool& infeasible, PropagateInfo& info);
     // the read, then the whole list through set_var_bounds (binfo describes that application); returns the length of the list
@@ -282,10 +265,7 @@ public:
     // j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by CONSTRAINT (0 / ignored for one
     // without a row), vectors by position have length num_rows().  Internal form A x + s = b: no sign turn for Maximize.  Requests are
     // served in batches of RG_BATCH.  Reads the state only, like compute_duals.
-    struct TableauInfo {
-        uint64_t requests = 0, solves = 0, batches = 0, nnz = 0;
-        double bytes = 0, device_ms = 0;
-    };
+    using TableauInfo = mlp_tableau_info;
     int num_rows() const { return m_; }
     void basis_head(std::vector<uint64_t>& out);  // column basic at each position
     void binv_rows(const std::vector<uint64_t>& cols, double* out, TableauInfo& info);  // out[t][constraint] = (e_p^T B^-1), p = position of the basic column

@@ -2667,7 +2667,7 @@ int Engine::fix_var_apply(int var, double val) {
 
 bool Engine::unfix_var(int var) {  // solver.rs:418-438
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    FixInfo unreported;   // (the single form reports nothing: what mlp_fix_info shows stays)
+    FixInfo unreported{};  // (the single form reports nothing: what mlp_fix_info shows stays)
     return release_fixed(std::vector<int>(1, var), unreported, "unfix_var") != 0;
 }
 
@@ -2702,7 +2702,7 @@ void Engine::add_constraint(Constraint c) {
     if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_constraint: model not solved (solver.rs:555-556)");
     std::vector<Constraint> one;
     one.push_back(std::move(c));
-    CutInfo unused;
+    CutInfo unused{};
     add_constraints(std::move(one), unused, false);
 }
 
@@ -3041,7 +3041,6 @@ std::vector<int> Engine::cut_round_positions(const std::vector<int>& vars, const
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, who + ": duplicate variable");
     std::vector<int> pos(vars.size());
     for (size_t t = 0; t < vars.size(); ++t) {
-        if (vars[t] < 0 || vars[t] >= num_vars) throw MlpError(-1, who + ": variable out of range" + (refs ? " (lib.rs:420)" : ""));
         if (var_is_int && !var_is_int[vars[t]]) throw MlpError(-1, who + ": variable is not marked integer");
         if (h_var_loc[vars[t]] < 0) throw MlpError(-1, who + ": variable is not basic" + (refs ? " (solver.rs:458)" : ""));
         pos[t] = h_var_loc[vars[t]];
@@ -3081,8 +3080,8 @@ void Engine::add_gomory_cuts(const std::vector<int>& vars, CutInfo& info) {
 void Engine::add_gmi_cuts(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, double away,
                           int32_t* status_out, CutInfo& info, GmiInfo& gmi) {
     const double t0 = now_s();
-    if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_gmi_cuts: model not solved (solver.rs:555-556)");
     if (!(away > 0.0 && away <= 0.5)) throw MlpError(-1, "add_gmi_cuts: away must be in (0, 0.5]");
+    if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_gmi_cuts: model not solved (solver.rs:555-556)");
     const std::vector<int> pos = cut_round_positions(vars, "add_gmi_cuts", var_is_int, false);
     gmi.requests = vars.size();
     if (vars.empty()) return;
@@ -3693,7 +3692,6 @@ namespace mlp {
 // Dual values, reduced costs and the KKT certificate of the current basis (duals.inc).  Nothing here writes solver state: the
 // kernels write private buffers, the pending rank-1 terms are applied, not folded, and the compact factor is not re-peeled.
 void Engine::compute_duals(Duals& out) {
-    if (sharded()) throw MlpError(-1, "duals are not available on a sharded solution");
     pull_ctl();  // (k_ and the count of pending terms as the device holds them)
     sync_view();
     const DevView& dv = hview;
@@ -3759,7 +3757,6 @@ void Engine::compute_duals(Duals& out) {
 
 // Basis status of every structural variable and every constraint (= its slack); a constraint without terms has no row: basic.
 void Engine::basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons) {
-    if (sharded()) throw MlpError(-1, "the basis status is not available on a sharded solution");
     pull_ctl();
     std::vector<uint8_t> fl((size_t)num_vars);
     if (num_vars) HIPCHECK(hipMemcpyAsync(fl.data(), d_nbflags.p, fl.size(), hipMemcpyDeviceToHost, st));
@@ -3777,7 +3774,6 @@ void Engine::basis_status(std::vector<int32_t>& vars, std::vector<int32_t>& cons
 // Cost / rhs ranging (ranging.inc).  The requests that need a row / a column of B^-1 are served in batches of RG_BATCH; the others
 // (non-basic variables, rows whose slack is basic, constraints without a row) are answered from the reduced costs / x_B directly.
 void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du, double* lo, double* hi, RangingInfo& info) {
-    if (sharded()) throw MlpError(-1, "ranging is not available on a sharded solution");
     const double inf = std::numeric_limits<double>::infinity();
     const size_t nreq = idx.size();
     for (uint64_t id : idx)
@@ -3891,10 +3887,7 @@ void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du
 // cached copy of the point (fetch_values, as get_values).
 void Engine::branch_penalties(const std::vector<int>& vars, const uint8_t* var_is_int, const uint8_t* con_is_int, const Duals& du,
                               double* down, double* up, int64_t* down_col, int64_t* up_col, double* frac, int32_t* status, BranchInfo& info) {
-    if (sharded()) throw MlpError(-1, "branch_penalties is not available on a sharded solution");
     const size_t nreq = vars.size();
-    for (int j : vars)
-        if (j < 0 || j >= num_vars) throw MlpError(-1, "branch_penalties: variable out of range");
     if ((int)du.r_int.size() != N_) throw MlpError(-1, "branch_penalties: the duals belong to another state");
     info = BranchInfo();
     info.requests = nreq;
@@ -3992,7 +3985,6 @@ int Engine::tab_internal_col(uint64_t col, const char* what) const {
     return num_vars + h_cons_row[c];
 }
 void Engine::basis_head(std::vector<uint64_t>& out) {
-    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
     pull_ctl();
     std::vector<uint64_t> cons_of_row((size_t)m_, 0);
     for (size_t c = 0; c < h_cons_row.size(); ++c)
@@ -4090,7 +4082,6 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
     info.device_ms = ms_total;
 }
 void Engine::binv_rows(const std::vector<uint64_t>& cols, double* out, TableauInfo& info) {
-    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
     pull_ctl();
     std::vector<int> req(cols.size());
     for (size_t t = 0; t < cols.size(); ++t) {
@@ -4103,7 +4094,6 @@ void Engine::binv_rows(const std::vector<uint64_t>& cols, double* out, TableauIn
     tab_dense(0, req, nullptr, out, info);
 }
 void Engine::binv_cols(const std::vector<uint64_t>& cons, double* out, TableauInfo& info) {
-    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
     std::vector<int> req(cons.size());
     for (size_t t = 0; t < cons.size(); ++t) {
         if (cons[t] >= h_cons_row.size()) throw MlpError(-1, "binv_cols: constraint out of range");
@@ -4115,7 +4105,6 @@ void Engine::binv_cols(const std::vector<uint64_t>& cons, double* out, TableauIn
     tab_dense(1, req, nullptr, out, info);
 }
 void Engine::tableau_cols(const std::vector<uint64_t>& cols, double* out, TableauInfo& info) {
-    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
     pull_ctl();
     std::vector<int> req(cols.size());
     std::vector<std::pair<size_t, int>> basic;
@@ -4135,7 +4124,6 @@ void Engine::tableau_cols(const std::vector<uint64_t>& cols, double* out, Tablea
     }
 }
 void Engine::basis_solve(bool transpose, const double* rhs, size_t n, double* out, TableauInfo& info) {
-    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
     info = TableauInfo();
     info.requests = n;
     if (transpose && m_ == 0) std::fill(out, out + n * h_cons_row.size(), 0.0);
@@ -4143,7 +4131,6 @@ void Engine::basis_solve(bool transpose, const double* rhs, size_t n, double* ou
 }
 void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_t>& indptr, std::vector<uint32_t>& indices,
                           std::vector<double>& values, TableauInfo& info) {
-    if (sharded()) throw MlpError(-1, "the tableau is not available on a sharded solution");
     pull_ctl();
     std::vector<int> pos(cols.size());
     for (size_t t = 0; t < cols.size(); ++t) {
@@ -4217,12 +4204,18 @@ void Engine::cutoff_alloc(const uint8_t* var_is_int, CutoffRun& r) {
     b.tcnt = r.tcnt.p; b.toff = r.toff.p; b.svar = r.svar.p; b.slo = r.slo.p; b.shi = r.shi.p; b.ovar = r.ovar.p; b.olo = r.olo.p; b.ohi = r.ohi.p;
     b.nv = nv; b.g = 0.0;
 }
+double Engine::cutoff_gap(double cutoff, const std::string& who) {
+    if (!solved()) throw MlpError(-1, who + ": model not solved");
+    const double obj = cur_obj_val();                         // internal: min c^.x
+    const double user = direction == 1 ? -obj : obj;          // what mlp_solution_objective returns
+    const double g = direction == 1 ? user - cutoff : cutoff - user;
+    if (std::isnan(g)) throw MlpError(-1, who + ": the gap is NaN");
+    return g;
+}
 // The read: nothing is written but private buffers; the reduced costs are the engine's own d on the device, the host reads back the
 // length of the list and then the list.
 void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint32_t>& vars, std::vector<double>& lo, std::vector<double>& hi,
                            FixInfo& info) {
-    if (sharded()) throw MlpError(-1, "cutoff_bounds is not available on a sharded solution");
-    if (!solved()) throw MlpError(-1, "cutoff_bounds: model not solved (the bound is a weak-duality argument: it needs a dual-feasible basis)");
     info = FixInfo();
     vars.clear(); lo.clear(); hi.clear();
     const int nv = num_vars;
@@ -4353,14 +4346,12 @@ struct CallTimer {
 
 // The batched forms.  Checks first, nothing is changed before they pass.
 void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& vals, FixInfo& info) {
-    if (sharded()) throw MlpError(-1, "fix_vars is not available on a sharded solution");
     info = FixInfo();
     info.requests = vars.size();
     if (vars.empty()) return;
     {
         std::vector<int> sorted(vars);
         std::sort(sorted.begin(), sorted.end());
-        if (sorted.front() < 0 || sorted.back() >= num_vars) throw MlpError(-1, "fix_vars: variable out of range");
         if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "fix_vars: a variable is listed twice");
     }
     host_bounds();
@@ -4408,9 +4399,6 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
 }
 
 uint64_t Engine::unfix_vars(const std::vector<int>& vars, FixInfo& info) {
-    if (sharded()) throw MlpError(-1, "unfix_vars is not available on a sharded solution");
-    for (int j : vars)
-        if (j < 0 || j >= num_vars) throw MlpError(-1, "unfix_vars: variable out of range");
     return release_fixed(vars, info, "unfix_vars");
 }
 // unfix_var's rule (solver.rs:418-438) per request: a basic or not-fixed variable is skipped; the flags of a released column come from
@@ -4473,8 +4461,7 @@ void Engine::var_bounds(const uint32_t* vars, uint64_t n, double* lo, double* hi
 
 // Checks first, nothing is changed before they pass (the classification writes private buffers only).
 void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<double>& lo, const std::vector<double>& hi, BoundsInfo& info) {
-    if (sharded()) throw MlpError(-1, "set_var_bounds is not available on a sharded solution");
-    if (!solved()) throw MlpError(-1, "set_var_bounds: model not solved (the re-solve is the dual one: it needs a dual-feasible basis)");
+    if (!solved()) throw MlpError(-1, "set_var_bounds: model not solved");  // (the re-solve is the dual one: it needs a dual-feasible basis)
     info = BoundsInfo();
     info.requests = vars.size();
     if (vars.empty()) return;
@@ -4483,7 +4470,6 @@ void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<doub
     std::vector<size_t> ord(n);  // the requests in ascending variable number
     for (size_t i = 0; i < n; ++i) ord[i] = i;
     std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return vars[a] < vars[b]; });
-    if (vars[ord.front()] < 0 || vars[ord.back()] >= num_vars) throw MlpError(-1, "set_var_bounds: variable out of range");
     for (size_t i = 1; i < n; ++i)
         if (vars[ord[i]] == vars[ord[i - 1]]) throw MlpError(-1, "set_var_bounds: a variable is listed twice");
     for (size_t i = 0; i < n; ++i)
@@ -4534,8 +4520,6 @@ void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<doub
 }
 
 uint64_t Engine::tighten_by_reduced_cost(double g, const uint8_t* var_is_int, BoundsInfo& info) {
-    if (sharded()) throw MlpError(-1, "tighten_by_reduced_cost is not available on a sharded solution");
-    if (!solved()) throw MlpError(-1, "tighten_by_reduced_cost: model not solved (the bound is a weak-duality argument: it needs a dual-feasible basis)");
     info = BoundsInfo();
     const int nv = num_vars;
     if (nv <= 0 || !(g < std::numeric_limits<double>::infinity())) return 0;  // g = +inf: nothing is tightened
@@ -4561,7 +4545,6 @@ uint64_t Engine::tighten_by_reduced_cost(double g, const uint8_t* var_is_int, Bo
 // infeasible); at the end the length of the list and the list.
 void Engine::propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::vector<uint32_t>& vars, std::vector<double>& lo,
                               std::vector<double>& hi, bool& infeasible, PropagateInfo& info) {
-    if (sharded()) throw MlpError(-1, "propagate_bounds is not available on a sharded solution");
     if (max_rounds < 1 || max_rounds > 64) throw MlpError(-1, "propagate_bounds: max_rounds must lie in 1..64");
     info = PropagateInfo();
     infeasible = false;
@@ -4626,8 +4609,8 @@ void Engine::propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::ve
 }
 
 uint64_t Engine::tighten_by_propagation(const uint8_t* var_is_int, int max_rounds, bool& infeasible, PropagateInfo& info, BoundsInfo& binfo) {
-    if (sharded()) throw MlpError(-1, "tighten_by_propagation is not available on a sharded solution");
-    if (!solved()) throw MlpError(-1, "tighten_by_propagation: model not solved (the re-solve is the dual one: it needs a dual-feasible basis)");
+    if (max_rounds < 1 || max_rounds > 64) throw MlpError(-1, "tighten_by_propagation: max_rounds must lie in 1..64");
+    if (!solved()) throw MlpError(-1, "tighten_by_propagation: model not solved");  // (the re-solve is the dual one: it needs a dual-feasible basis)
     binfo = BoundsInfo();
     std::vector<uint32_t> v;
     std::vector<double> lo, hi;
