@@ -4,7 +4,7 @@ minimise, print the objective and the non-zero variables.
 
     python examples/solve_mps.py model.mps [--max] [--all] [--ranging] [--tableau VAR] [--gomory-rounds K]
                                  [--gmi-rounds K [--continuous NAME,...]] [--branch-penalties [--continuous NAME,...]]
-                                 [--cutoff VALUE [--tighten] [--continuous NAME,...]]
+                                 [--cutoff VALUE [--tighten] [--continuous NAME,...]] [--rhs-sweep ROW:FROM:TO:STEPS]
 
 --ranging adds a sensitivity table: per variable its value, basis status, reduced cost and cost range; per row its dual value and
 rhs range (rows in file order).  --tableau VAR prints the tableau row of the basic variable VAR (by name): its non-zero coefficients on the
@@ -19,6 +19,9 @@ unless listed in --continuous, the slacks are continuous), the child bounds they
 prints the bounds that the reduced costs imply once an incumbent of objective VALUE is known (Solution.cutoff_bounds; every structural
 variable is integer unless listed in --continuous): per tightened variable its bounds and whether it can be fixed.  --tighten then applies
 all of them to the solution on the device (Solution.tighten_by_reduced_cost) and prints the count and the objective, which does not move.
+--rhs-sweep ROW:FROM:TO:STEPS moves the right-hand side of row ROW (its number in file order) from FROM to TO in STEPS equal steps: first
+ONE Solution.rhs_scenarios call prints, per step, the value of the current dual solution there and whether the current basis stays
+feasible; then a chain of Solution.set_rhs calls, each from the basis of the step before, prints the optimum and the pivots of every step.
 
 Runs on the MI355X engine (libminilp_hip.so); there is no CPU back end.  `run(B, ...)` takes the module that
 provides the reference's API so that the tests can drive the same code with their checker."""
@@ -31,7 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0, tableau=None, gmi_rounds=0, continuous=(), branch_penalties=False, cutoff=None, tighten=False,
-        propagate=False):
+        propagate=False, rhs_sweep=None):
     text = open(path).read()
     t0 = time.time()
     f = B.MpsFile(text, B.MAXIMIZE if maximize else B.MINIMIZE)  # MpsFile::parse (mps.rs:39)
@@ -126,6 +129,29 @@ def run(B, path, maximize=False, show_all=False, ranging=False, gomory_rounds=0,
             print("propagation: the rows prove the model infeasible, %s" % sol.propagate_info())
             return 1
         print("propagation: %d variables tightened, objective %.12g, %s %s" % (count, sol.objective(), sol.propagate_info(), sol.bounds_info()))
+    if rhs_sweep is not None:
+        try:
+            row, lo, hi, steps = rhs_sweep.split(":")
+            row, lo, hi, steps = int(row), float(lo), float(hi), int(steps)
+            if not (0 <= row < sol.num_constraints and steps >= 1):
+                raise ValueError(rhs_sweep)
+        except ValueError:
+            print("rhs sweep: expected ROW:FROM:TO:STEPS with a row below %d" % sol.num_constraints)
+            return 1
+        grid = [lo + (hi - lo) * t / max(1, steps - 1) for t in range(steps)]
+        if steps > 1:
+            grid[-1] = hi
+        res = sol.rhs_scenarios([row], [[v] for v in grid])
+        print("rhs sweep of row %d (now %.12g), %s" % (row, sol.constraint_rhs([row])[0], sol.rhs_info()))
+        for v, bound, ok in zip(grid, res["bound"], res["feasible"]):
+            print("what-if  row %d = %r: bound %.12g %s" % (row, v, bound, "feasible" if ok else "pivots needed"))
+        for v in grid:
+            try:
+                sol = sol.set_rhs([row], [v])
+            except B.Infeasible:
+                print("set_rhs  row %d = %r: infeasible" % (row, v))
+                return 0
+            print("set_rhs  row %d = %r: optimum %.12g, %d pivots" % (row, v, sol.objective(), sol.rhs_info()["pivots"]))
     for k in range(gomory_rounds):
         x = sol.values()
         vs, _ = sol.basis_status()
@@ -186,10 +212,12 @@ def main():
                     help="with --cutoff: apply the listed bounds to the solution (Solution.tighten_by_reduced_cost)")
     ap.add_argument("--propagate", action="store_true",
                     help="tighten the bounds by propagation over the rows (Solution.tighten_by_propagation) and print the count and the counters")
+    ap.add_argument("--rhs-sweep", default=None, metavar="ROW:FROM:TO:STEPS",
+                    help="move the right-hand side of row ROW from FROM to TO: one Solution.rhs_scenarios call, then a chain of Solution.set_rhs calls")
     a = ap.parse_args()
     import minilp_amd as B
     return run(B, a.file, a.max, a.all, a.ranging, a.gomory_rounds, a.tableau, a.gmi_rounds, [nm for nm in a.continuous.split(",") if nm],
-               a.branch_penalties, a.cutoff, a.tighten, a.propagate)
+               a.branch_penalties, a.cutoff, a.tighten, a.propagate, a.rhs_sweep)
 
 
 if __name__ == "__main__":

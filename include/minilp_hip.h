@@ -55,6 +55,8 @@ enum { MLP_OK = 0, MLP_INFEASIBLE = 1, MLP_UNBOUNDED = 2,
  * mlp_bounds_info with its own mlp_bounds_info_size()) are additive in the same way. */
 /* Still version 5: the bound propagation (mlp_solution_propagate_bounds, mlp_solution_tighten_by_propagation, mlp_propagate_info with
  * its own mlp_propagate_info_size()) is additive in the same way. */
+/* Still version 5: the right-hand-side changes (mlp_solution_set_rhs, mlp_solution_constraint_rhs, mlp_solution_rhs_scenarios,
+ * mlp_rhs_info with its own mlp_rhs_info_size()) are additive in the same way. */
 #define MLP_ABI_VERSION 5u
 uint32_t mlp_abi_version(void);
 uint64_t mlp_stats_size(void);
@@ -661,6 +663,70 @@ typedef struct mlp_propagate_info {
 } mlp_propagate_info;
 int mlp_solution_propagate_info(const mlp_solution* s, mlp_propagate_info* out);
 uint64_t mlp_propagate_info_size(void);
+
+/* ---- New right-hand sides for a solved model, and the batched what-if read ---------------------------------------------------------------
+ * mlp_solution_set_rhs gives constraint constraints[i] the right-hand side rhs[i] (the user's terms: no sign is turned for Maximize) and
+ *   re-solves with the dual simplex from the basis it finds.  Constraints are numbered as mlp_solution_num_constraints counts them:
+ *   mlp_problem_add_constraint order, then the rows appended to the solution, cut rows included.  Operators and slack bounds stay as
+ *   they are: internally the row stays a.x + s = rhs with s in [0, inf) for '<=', (-inf, 0] for '>=', [0, 0] for '='.  The reduced costs
+ *   do not depend on the right-hand side, so the basis stays dual feasible and the primal loop is never entered.  It needs a solved model
+ *   (primal and dual feasible, no exhausted pivot budget), as mlp_solution_set_var_bounds does.
+ *   Checked before anything changes, each MLP_EINVAL: a NULL handle or a NULL array (n > 0); a constraint out of range or listed twice; a
+ *   NaN or infinite value; a solution that is not solved; a solution sharded over several ranks.  (A one-rank pump is accepted, as by
+ *   every mutator; mlp_solution_rhs_scenarios below refuses that one too.)
+ *   A constraint without terms has no row: its new right-hand side is stored and read back by mlp_solution_constraint_rhs; if 0 op rhs
+ *   is then false the call is status 1 (Infeasible), as mlp_problem_solve treats such a row.  Then
+ *     1. the host sorts the requests by row, forms delta_r = rhs' - rhs against the vector it holds and drops exact zeros.
+ *     2. if any delta is non-zero: the deltas are scattered into a zeroed block, ONE FTRAN y = B^-1 delta follows (the dense
+ *        right-hand-side path of whichever representation of B^-1 is live), x_B += y by position, and the objective moves by
+ *        sum_p c_B[p] y[p] (c_B: the internal cost of the column basic at p), summed over the positions in a fixed order: bit-identical
+ *        from run to run and whatever the order of the list.
+ *     3. the host's right-hand-side vector follows; it is the only resident copy, and the certificate, the propagation, the
+ *        recomputation of the basic values, the row append and mlp_solution_clone all read it.
+ *     4. ONE dual re-solve if a basic value now violates its bounds (an Infeasible verdict is status 1).  Otherwise there is no pivot.
+ *   A call whose values all equal the current ones leaves every bit of the state (no FTRAN: mlp_rhs_info.solves == 0).
+ *   A basis blob saved after the call carries no right-hand side: it belongs with a Problem that has the same right-hand sides.
+ *   n == 0 is a successful no-op on any live handle that is not sharded over several ranks, one that is not solved included: as with
+ *   mlp_solution_set_var_bounds, the checks of the model's state run only when something is listed.  Any non-zero status
+ *   frees the solution and sets *s = NULL; a pivot budget is lifted; cached duals and ranges are dropped.
+ * mlp_solution_constraint_rhs reads the current right-hand sides of the listed constraints (constraints == NULL: all of them,
+ *   n = mlp_solution_num_constraints).  A host read that works on any state.  MLP_EINVAL: NULL handle / output, an index out of range.
+ * mlp_solution_rhs_scenarios evaluates num_scenarios candidate right-hand sides against the current basis, 16 per batch, on the device.
+ *   rhs is [num_scenarios][n], row-major: scenario s gives constraints[i] the right-hand side rhs[s * n + i], every other constraint keeps
+ *   its own.  Nothing is changed: only private buffers are written.  It needs a solved model; the refusals are those of set_rhs (like
+ *   the tableau reads, whose solve it runs, it also refuses a solution sharding was enabled on, a one-rank pump included), and every
+ *   listed constraint must have a row (else MLP_EINVAL).  Per scenario, with y_s = B^-1 (b_s - b):
+ *     bound[s]     = mlp_solution_objective as the scenario's basis would report it: internally obj + sum_p c_B[p] y_s[p] (the order of
+ *                    set_rhs's sum), turned into the user's sense.  It is the value of the current dual solution at b_s: the scenario's
+ *                    optimum where feasible[s] is set, otherwise a bound on it from the dual side (below for Minimize, above for
+ *                    Maximize; an infeasible scenario has no optimum).
+ *     feasible[s]  = 1 if no position p has x_B[p] + y_s[p] outside [loB[p] - 1e-8, hiB[p] + 1e-8] — the test of the dual pricing, so
+ *                    it says "mlp_solution_set_rhs of this scenario would run zero pivots" — else 0.
+ *     worst[s]     = the largest such violation (0.0 when feasible).
+ *     worst_col[s] = the column basic at the position of that violation, the lowest position on a tie; -1 when feasible.  Column
+ *                    numbering of mlp_solution_basis_head.
+ *   A scenario's four results are bit-identical whatever else is in the call: its place, its neighbours, num_scenarios and the order of
+ *   the constraints do not enter.  n == 0: every scenario is feasible with bound = mlp_solution_objective.  The host reads back four
+ *   numbers per scenario, never a block.
+ * mlp_rhs_info: what the last of mlp_solution_set_rhs / mlp_solution_rhs_scenarios on this solution did (zeros before the first).  Only
+ *   grows at its end; mlp_rhs_info_size() is its size as the library was built. */
+int mlp_solution_set_rhs(mlp_solution** s, const uint64_t* constraints, const double* rhs, uint64_t n);
+int mlp_solution_constraint_rhs(const mlp_solution* s, const uint64_t* constraints, uint64_t n, double* rhs);
+int mlp_solution_rhs_scenarios(const mlp_solution* s, const uint64_t* constraints, uint64_t n, const double* rhs, uint64_t num_scenarios,
+                               double* bound, uint8_t* feasible, double* worst, int64_t* worst_col);
+typedef struct mlp_rhs_info {
+    uint64_t requests;   /* constraints listed */
+    uint64_t changed;    /* set_rhs: of them with a right-hand side that differs from the current one (rowless ones included) */
+    uint64_t scenarios;  /* rhs_scenarios: scenarios evaluated */
+    uint64_t solves;     /* right-hand sides sent through the FTRAN (set_rhs: 0 or 1) */
+    uint64_t batches;    /* batches of 16 right-hand sides */
+    uint64_t pivots;     /* set_rhs: iterations of the dual re-solve */
+    double bytes;        /* algorithmic bytes of the device work (without the re-solve) */
+    double device_ms;    /* its time on the device (HIP events around the launches) */
+    double wall_ms;      /* the whole call on the host, re-solve included */
+} mlp_rhs_info;
+int mlp_solution_rhs_info(const mlp_solution* s, mlp_rhs_info* out);
+uint64_t mlp_rhs_info_size(void);
 
 /* ---- MPS (mps.rs:39 MpsFile::parse) ------------------------------------------------------ */
 typedef struct mlp_mps mlp_mps;

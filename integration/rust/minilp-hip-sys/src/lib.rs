@@ -131,6 +131,12 @@ extern "C" {
     pub fn mlp_solution_tighten_by_propagation(s: *mut *mut mlp_solution, var_is_int: *const u8, num_vars: u32, max_rounds: i32, tightened: *mut u64, infeasible: *mut c_int) -> c_int;
     pub fn mlp_solution_propagate_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
     pub fn mlp_propagate_info_size() -> u64;
+    // new right-hand sides and the batched what-if read (additive: the ABI version stays 5)
+    pub fn mlp_solution_set_rhs(s: *mut *mut mlp_solution, constraints: *const u64, rhs: *const f64, n: u64) -> c_int;
+    pub fn mlp_solution_constraint_rhs(s: *const mlp_solution, constraints: *const u64, n: u64, rhs: *mut f64) -> c_int;
+    pub fn mlp_solution_rhs_scenarios(s: *const mlp_solution, constraints: *const u64, n: u64, rhs: *const f64, num_scenarios: u64, bound: *mut f64, feasible: *mut u8, worst: *mut f64, worst_col: *mut i64) -> c_int;
+    pub fn mlp_solution_rhs_info(s: *const mlp_solution, out: *mut std::os::raw::c_void) -> c_int;
+    pub fn mlp_rhs_info_size() -> u64;
     // reading the tableau: rows / columns of B^-1 A and of B^-1, solves with the basis (additive: the ABI version stays 5)
     pub fn mlp_solution_num_rows(s: *const mlp_solution) -> u64;
     pub fn mlp_solution_basis_head(s: *const mlp_solution, head: *mut u64, num_rows: u64) -> c_int;

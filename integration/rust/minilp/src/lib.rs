@@ -700,6 +700,63 @@ impl Solution {
         (lo, hi)
     }
 
+    /// New right-hand sides `(constraint, rhs)` for constraints of a solved model (numbering of
+    /// [`num_constraints`](Self::num_constraints)), then one dual re-solve from the current basis (none when every basic value
+    /// stays within its bounds).  Operators stay as they are (extension: no counterpart in the reference; semantics in
+    /// `minilp_hip.h`).
+    ///
+    /// # Errors
+    ///
+    /// Will return an error if the problem becomes infeasible with the new right-hand sides.
+    ///
+    /// # Panics
+    ///
+    /// Will panic if a constraint is out of range or listed twice.
+    pub fn set_rhs(self, changes: &[(usize, f64)]) -> Result<Solution, Error> {
+        let m = self.num_constraints();
+        assert!(changes.iter().all(|x| x.0 < m));
+        let mut seen: Vec<usize> = changes.iter().map(|x| x.0).collect();
+        seen.sort_unstable();
+        assert!(seen.windows(2).all(|w| w[0] != w[1]), "set_rhs: a constraint is listed twice");
+        let cons: Vec<u64> = changes.iter().map(|x| x.0 as u64).collect();
+        let rhs: Vec<f64> = changes.iter().map(|x| x.1).collect();
+        self.consume(|s| unsafe { sys::mlp_solution_set_rhs(s, cons.as_ptr(), rhs.as_ptr(), cons.len() as u64) })
+    }
+
+    /// Right-hand side of a constraint as the solution holds it now (extension).
+    pub fn constraint_rhs(&self, constraint: usize) -> f64 {
+        let (c, mut rhs) = (constraint as u64, 0.0f64);
+        let st = unsafe { sys::mlp_solution_constraint_rhs(self.raw, &c, 1, &mut rhs) };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        rhs
+    }
+
+    /// Candidate right-hand sides against the current basis, 16 per batch on the device: scenario `s` gives `constraints[i]` the
+    /// right-hand side `rhs[s][i]`.  Per scenario `(bound, feasible, worst, worst_col)`: the objective its basis would report (the
+    /// optimum where `feasible`, else a bound from the dual side), whether every basic value stays within its bounds (then
+    /// [`set_rhs`](Self::set_rhs) runs no pivot), the largest violation and the column basic where it occurs (numbering of
+    /// [`basis_head`](Self::basis_head)).  The solution is left as it is (extension).
+    ///
+    /// # Panics
+    ///
+    /// Will panic if a scenario's length differs from the list's, or if the library refuses the call (a constraint out of range,
+    /// listed twice or without terms, a model that is not solved).
+    pub fn rhs_scenarios(&self, constraints: &[usize], rhs: &[Vec<f64>]) -> Vec<(f64, bool, f64, Option<usize>)> {
+        let n = constraints.len();
+        assert!(rhs.iter().all(|r| r.len() == n), "rhs_scenarios: every scenario needs one value per listed constraint");
+        let cons: Vec<u64> = constraints.iter().map(|&c| c as u64).collect();
+        let flat: Vec<f64> = rhs.iter().flat_map(|r| r.iter().copied()).collect();
+        let s = rhs.len();
+        let (mut bound, mut worst) = (vec![0.0f64; s], vec![0.0f64; s]);
+        let (mut feasible, mut col) = (vec![0u8; s], vec![0i64; s]);
+        let st = unsafe {
+            sys::mlp_solution_rhs_scenarios(self.raw, cons.as_ptr(), n as u64, flat.as_ptr(), s as u64, bound.as_mut_ptr(),
+                                            feasible.as_mut_ptr(), worst.as_mut_ptr(), col.as_mut_ptr())
+        };
+        assert_eq!(st, sys::MLP_OK, "{}", last_error());
+        (0..s).map(|i| (bound[i], feasible[i] != 0, worst[i], if col[i] < 0 { None } else { Some(col[i] as usize) })).collect()
+    }
+
     /// Add a Gomory cut constraint to the problem and return the solution.  (`lib.rs:419-423`)
     ///
     /// # Errors

@@ -96,6 +96,11 @@ class MlpPropagateInfo(C.Structure):  # include/minilp_hip.h: mlp_propagate_info
                 ("listed_fixed", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double)]
 
 
+class MlpRhsInfo(C.Structure):  # include/minilp_hip.h: mlp_rhs_info (only grows at its end)
+    _fields_ = [("requests", C.c_uint64), ("changed", C.c_uint64), ("scenarios", C.c_uint64), ("solves", C.c_uint64),
+                ("batches", C.c_uint64), ("pivots", C.c_uint64), ("bytes", C.c_double), ("device_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
 # basis status of a variable / of a constraint's slack (include/minilp_hip.h)
 MLP_BASIC, MLP_AT_LOWER, MLP_AT_UPPER, MLP_NB_FREE, MLP_NB_FIXED = range(5)
 
@@ -103,7 +108,8 @@ ABI_VERSION = 5  # include/minilp_hip.h: MLP_ABI_VERSION
 # (size function of the library, the class here): lib() refuses a library whose struct differs in size
 _STRUCT_SIZES = (("mlp_certificate_size", MlpCertificate), ("mlp_ranging_info_size", MlpRangingInfo), ("mlp_cut_info_size", MlpCutInfo),
                  ("mlp_tableau_info_size", MlpTableauInfo), ("mlp_gmi_info_size", MlpGmiInfo), ("mlp_branch_info_size", MlpBranchInfo),
-                 ("mlp_fix_info_size", MlpFixInfo), ("mlp_bounds_info_size", MlpBoundsInfo), ("mlp_propagate_info_size", MlpPropagateInfo))
+                 ("mlp_fix_info_size", MlpFixInfo), ("mlp_bounds_info_size", MlpBoundsInfo), ("mlp_propagate_info_size", MlpPropagateInfo),
+                 ("mlp_rhs_info_size", MlpRhsInfo))
 
 
 class MlpIterInfo(C.Structure):  # include/minilp_hip.h: mlp_iter_info
@@ -238,6 +244,10 @@ def lib():
     sig("mlp_solution_propagate_bounds", i32, vp, pu8, u32, C.c_int32, pu32, pdbl, pdbl, u64, pu64, C.POINTER(i32))
     sig("mlp_solution_tighten_by_propagation", i32, C.POINTER(vp), pu8, u32, C.c_int32, pu64, C.POINTER(i32))
     sig("mlp_solution_propagate_info", i32, vp, C.POINTER(MlpPropagateInfo))
+    sig("mlp_solution_set_rhs", i32, C.POINTER(vp), pu64, pdbl, u64)
+    sig("mlp_solution_constraint_rhs", i32, vp, pu64, u64, pdbl)
+    sig("mlp_solution_rhs_scenarios", i32, vp, pu64, u64, pdbl, u64, pdbl, pu8, pdbl, C.POINTER(C.c_int64))
+    sig("mlp_solution_rhs_info", i32, vp, C.POINTER(MlpRhsInfo))
     sig("mlp_engine_open", i32, vp, C.POINTER(MlpIterInfo))
     sig("mlp_engine_stage", i32, vp, i32, C.POINTER(MlpIterInfo))
     _lib = L
@@ -824,6 +834,56 @@ class Solution:
     def propagate_info(self):
         """Counters of the last propagate_bounds / tighten_by_propagation call (mlp_propagate_info) as a dict."""
         return self._report(lib().mlp_solution_propagate_info, MlpPropagateInfo)
+
+    # ---- new right-hand sides and the batched what-if read (include/minilp_hip.h: mlp_solution_set_rhs ...; semantics there)
+    @staticmethod
+    def _cons_list(constraints, who):
+        c = np.ascontiguousarray(list(constraints), dtype=np.int64).reshape(-1)
+        if len(c) and c.min() < 0:
+            raise InternalError(-1, who + ": constraint out of range")
+        return c.astype(np.uint64)
+
+    def set_rhs(self, constraints, rhs):
+        """New right-hand sides rhs[i] for the listed constraints of a solved model (numbering of num_constraints, the user's terms),
+        then one dual re-solve from the current basis (none when every basic value stays within its bounds).  Raises Infeasible when
+        the changed model has no solution.  Like every mutator it consumes the receiver, also when the library refuses the call; only
+        what the binding itself refuses before the call (a negative index, lists of different lengths) leaves the receiver usable."""
+        c = self._cons_list(constraints, "set_rhs")
+        b = np.ascontiguousarray(list(rhs), dtype=np.float64).reshape(-1)
+        if len(b) != len(c):
+            raise InternalError(-1, "set_rhs: constraints and rhs differ in length")
+        h = self._take()
+        _raise(lib().mlp_solution_set_rhs(C.byref(h), _p(c, C.c_uint64), _p(b, C.c_double), len(c)))
+        return Solution(h)
+
+    def constraint_rhs(self, constraints=None):
+        """The right-hand sides of the listed constraints as the solution holds them now; constraints=None: all of them."""
+        c = None if constraints is None else self._cons_list(constraints, "constraint_rhs")
+        n = self.num_constraints if c is None else len(c)
+        out = np.zeros(n, dtype=np.float64)
+        _raise(lib().mlp_solution_constraint_rhs(self._h, None if c is None else _p(c, C.c_uint64), n, _p(out, C.c_double)))
+        return out
+
+    def rhs_scenarios(self, constraints, rhs):
+        """S candidate right-hand sides against the current basis, 16 per batch on the device: rhs is float64 [S, n], scenario s gives
+        constraints[i] the right-hand side rhs[s, i].  Returns a dict of arrays of length S: bound (the objective the scenario's basis
+        would report: its optimum where feasible, else a bound from the dual side), feasible (bool: set_rhs of the scenario would run no
+        pivot), worst (the largest bound violation of a basic value, 0.0 when feasible), worst_col (the column basic there, numbering of
+        basis_head; -1 when feasible).  The solution is left as it is."""
+        c = self._cons_list(constraints, "rhs_scenarios")
+        r = np.ascontiguousarray(rhs, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] != len(c):
+            raise InternalError(-1, f"rhs_scenarios: rhs must be [S, {len(c)}]")
+        S = r.shape[0]
+        bound, worst = np.zeros(S, dtype=np.float64), np.zeros(S, dtype=np.float64)
+        feasible, worst_col = np.zeros(S, dtype=np.uint8), np.zeros(S, dtype=np.int64)
+        _raise(lib().mlp_solution_rhs_scenarios(self._h, _p(c, C.c_uint64), len(c), _p(r, C.c_double), S, _p(bound, C.c_double),
+                                                _p(feasible, C.c_uint8), _p(worst, C.c_double), _p(worst_col, C.c_int64)))
+        return {"bound": bound, "feasible": feasible.astype(bool), "worst": worst, "worst_col": worst_col}
+
+    def rhs_info(self):
+        """Counters of the last set_rhs / rhs_scenarios call (mlp_rhs_info) as a dict."""
+        return self._report(lib().mlp_solution_rhs_info, MlpRhsInfo)
 
     def cut_info(self):
         """Counters of the last add_constraints / add_constraints_csr / add_gomory_cuts call (mlp_cut_info) as a dict."""

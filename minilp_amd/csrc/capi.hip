@@ -27,6 +27,7 @@ struct mlp_solution {
     Engine::FixInfo fix{};          // of the last mlp_solution_cutoff_bounds / mlp_solution_fix_vars / mlp_solution_unfix_vars call
     Engine::BoundsInfo bounds{};    // of the last mlp_solution_set_var_bounds / mlp_solution_tighten_by_reduced_cost call
     Engine::PropagateInfo prop{};   // of the last mlp_solution_propagate_bounds / mlp_solution_tighten_by_propagation call
+    Engine::RhsInfo rhs{};          // of the last mlp_solution_set_rhs / mlp_solution_rhs_scenarios call
     std::vector<uint64_t> tab_indptr;  // rows of the last mlp_solution_tableau_rows call (library-owned results)
     std::vector<uint32_t> tab_indices;
     std::vector<double> tab_values;
@@ -742,6 +743,40 @@ int mlp_solution_tighten_by_propagation(mlp_solution** h, const uint8_t* var_is_
 }
 int mlp_solution_propagate_info(const mlp_solution* s, mlp_propagate_info* out) { return report(s, &mlp_solution::prop, out, "NULL solution / propagate info"); }
 uint64_t mlp_propagate_info_size(void) { return (uint64_t)sizeof(mlp_propagate_info); }
+
+// ---- new right-hand sides and the batched what-if read (rhs.inc)
+int mlp_solution_set_rhs(mlp_solution** h, const uint64_t* constraints, const double* rhs, uint64_t n) {
+    return mutate(h, [&](mlp_solution& s) {
+        if (n && (!constraints || !rhs)) throw MlpError(MLP_EINVAL, "set_rhs: NULL list");
+        s.rhs = Engine::RhsInfo();
+        if (n == 0) return;  // (the no-op of every mutator: the engine's checks, solved() among them, run only on a list)
+        begin_change(s);
+        // a constraint index is not narrowed: its range, like a constraint listed twice, is Engine::check_rhs_list's alone
+        s.eng->set_rhs(std::vector<uint64_t>(constraints, constraints + n), std::vector<double>(rhs, rhs + n), s.rhs);
+    });
+}
+int mlp_solution_constraint_rhs(const mlp_solution* s, const uint64_t* constraints, uint64_t n, double* rhs) {
+    return guarded([&] {
+        live(s, NOTHING, "");
+        if (!constraints && n != (uint64_t)s->eng->num_constraints())
+            throw MlpError(MLP_EINVAL, "constraint_rhs: without a list the length must be the number of constraints");
+        if (n && !rhs) throw MlpError(MLP_EINVAL, "constraint_rhs: NULL output");
+        s->eng->constraint_rhs(constraints, n, rhs);
+    });
+}
+int mlp_solution_rhs_scenarios(const mlp_solution* cs, const uint64_t* constraints, uint64_t n, const double* rhs, uint64_t num_scenarios,
+                               double* bound, uint8_t* feasible, double* worst, int64_t* worst_col) {
+    return guarded([&] {
+        mlp_solution& s = live(cs, SHARDING_ON, "rhs_scenarios is ");  // (a read through the tableau's solve: refused like the tableau reads)
+        if (n && !constraints) throw MlpError(MLP_EINVAL, "rhs_scenarios: NULL constraint list");
+        if (n && num_scenarios && !rhs) throw MlpError(MLP_EINVAL, "rhs_scenarios: NULL right-hand sides");
+        if (num_scenarios && (!bound || !feasible || !worst || !worst_col)) throw MlpError(MLP_EINVAL, "rhs_scenarios: NULL output");
+        s.eng->rhs_scenarios(std::vector<uint64_t>(constraints, constraints + n), rhs, (size_t)num_scenarios, bound, feasible, worst, worst_col,
+                             s.rhs);
+    });
+}
+int mlp_solution_rhs_info(const mlp_solution* s, mlp_rhs_info* out) { return report(s, &mlp_solution::rhs, out, "NULL solution / rhs info"); }
+uint64_t mlp_rhs_info_size(void) { return (uint64_t)sizeof(mlp_rhs_info); }
 
 void mlp_solution_stats(const mlp_solution* s, mlp_stats* o) {
     if (!o) return;

@@ -5,6 +5,7 @@
 
 #include <cstdint>
 #include <functional>
+#include <map>
 #include <utility>
 #include <stdexcept>
 #include <string>
@@ -261,6 +262,16 @@ public:
                           std::vector<double>& hi, bool& infeasible, PropagateInfo& info);
     // the read, then the whole list through set_var_bounds (binfo describes that application); returns the length of the list
     uint64_t tighten_by_propagation(const uint8_t* var_is_int, int max_rounds, bool& infeasible, PropagateInfo& info, BoundsInfo& binfo);
+    // New right-hand sides for a solved model and the batched what-if read (rhs.inc; include/minilp_hip.h mlp_solution_set_rhs,
+    // mlp_solution_constraint_rhs, mlp_solution_rhs_scenarios).  RhsInfo describes the last of set_rhs / rhs_scenarios.
+    using RhsInfo = mlp_rhs_info;
+    // x_B += B^-1 (b' - b) with ONE FTRAN (none when no value differs), h_rhs follows, ONE dual re-solve if a basic value left its bounds
+    void set_rhs(const std::vector<uint64_t>& cons, const std::vector<double>& rhs, RhsInfo& info);
+    void constraint_rhs(const uint64_t* cons, uint64_t n, double* out) const;  // cons == nullptr: all num_constraints() of them
+    // rhs[S][cons.size()]; per scenario the objective its basis would report (user's sense), whether x_B + B^-1 (b_s - b) stays within
+    // the bounds, the largest violation and the column (numbering of basis_head, -1: none) basic where it occurs.  Reads the state only.
+    void rhs_scenarios(const std::vector<uint64_t>& cons, const double* rhs, size_t S, double* bound, uint8_t* feasible, double* worst,
+                       int64_t* worst_col, RhsInfo& info);
     // Reading the tableau of the current basis (tableau.inc; include/minilp_hip.h mlp_solution_binv_rows ...).  Columns:
     // j < num_vars structural, num_vars + c the slack of constraint c; vectors by row are exchanged by CONSTRAINT (0 / ignored for one
     // without a row), vectors by position have length num_rows().  Internal form A x + s = b: no sign turn for Maximize.  Requests are
@@ -333,6 +344,15 @@ private:
     int cutoff_read(const CutoffRun& r, const char* who, std::vector<uint32_t>* vars = nullptr, std::vector<double>* lo = nullptr,
                     std::vector<double>* hi = nullptr, uint64_t* listed_fixed = nullptr);
     std::vector<int> h_cons_row;  // constraint (Problem / Solution::add_constraint order) -> row; -1 for one without terms (no row)
+    // a constraint without terms keeps its operator and right-hand side here, by constraint (h_rhs is by row): set_rhs / constraint_rhs
+    struct Rowless {
+        int op;
+        double rhs;
+    };
+    std::map<uint64_t, Rowless> h_rowless_;
+    // the checks set_rhs and rhs_scenarios share (nothing is written): solved, in range, no constraint twice
+    void check_rhs_list(const std::vector<uint64_t>& cons, const char* who) const;
+    struct RhsRun;  // the private device buffers of one set_rhs / rhs_scenarios call
     std::vector<int> h_rptr, h_rcol;
     std::vector<double> h_rval;
     // Host view of the columns: only what the host logic needs — the length of every column and, for singleton

@@ -1238,9 +1238,11 @@ void Engine::try_new(const ProblemData& pd) {
     std::vector<double> xB, loB, hiB;
     std::vector<const Constraint*> kept;
     h_cons_row.clear();
+    h_rowless_.clear();
     for (const Constraint& c : pd.cons) {
         if (c.idx.empty()) {
             bool taut = c.op == 0 ? (0.0 == c.rhs) : c.op == 1 ? (0.0 <= c.rhs) : (0.0 >= c.rhs);
+            h_rowless_[h_cons_row.size()] = Rowless{c.op, c.rhs};
             h_cons_row.push_back(-1);
             if (taut) continue;
             throw LpFail{1};
@@ -2783,6 +2785,7 @@ void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gom
         if (c.idx.empty()) {
             const bool taut = c.op == 0 ? (0.0 == c.rhs) : c.op == 1 ? (0.0 <= c.rhs) : (0.0 >= c.rhs);
             if (!taut) throw LpFail{1};
+            h_rowless_[h_cons_row.size() + cons_row.size()] = Rowless{c.op, c.rhs};
             cons_row.push_back(-1);
             info.rows_without_terms += 1;
         } else {
@@ -3480,7 +3483,7 @@ Engine* Engine::clone() {
     e->m_ = m_; e->N_ = N_;
     host_bounds();
     e->h_obj = h_obj; e->h_lo = h_lo; e->h_hi = h_hi; e->h_rhs = h_rhs;
-    e->h_cons_row = h_cons_row;
+    e->h_cons_row = h_cons_row; e->h_rowless_ = h_rowless_;
     e->h_rptr = h_rptr; e->h_rcol = h_rcol; e->h_rval = h_rval;
     e->h_colnnz = h_colnnz; e->h_single_row = h_single_row; e->h_single_val = h_single_val;
     e->max_col_nnz_ = max_col_nnz_; e->max_row_nnz_ = max_row_nnz_; e->amax_ = amax_;
@@ -4620,5 +4623,210 @@ uint64_t Engine::tighten_by_propagation(const uint8_t* var_is_int, int max_round
     set_var_bounds(std::vector<int>(v.begin(), v.end()), lo, hi, binfo);
     binfo.tightened = (uint64_t)v.size();
     return (uint64_t)v.size();
+}
+
+// ------------------------------------------------------------------ right-hand sides (rhs.inc)
+// h_rhs (by row) and h_rowless_ (by constraint) are the only resident copies of b: compute_duals, propagate_bounds, recalc_basic_vals and
+// the rhs ranging read h_rhs on every call, add_constraints appends to it, clone copies both.
+void Engine::check_rhs_list(const std::vector<uint64_t>& cons, const char* who) const {
+    if (!solved()) throw MlpError(-1, std::string(who) + ": model not solved");  // (the re-solve is the dual one: it needs a dual-feasible basis)
+    for (uint64_t c : cons)
+        if (c >= h_cons_row.size()) throw MlpError(-1, std::string(who) + ": constraint out of range");
+    std::vector<uint64_t> sorted(cons);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, std::string(who) + ": a constraint is listed twice");
+}
+void Engine::constraint_rhs(const uint64_t* cons, uint64_t n, double* out) const {
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t c = cons ? cons[i] : i;
+        if (c >= h_cons_row.size()) throw MlpError(-1, "constraint_rhs: constraint out of range");
+        out[i] = h_cons_row[c] >= 0 ? h_rhs[h_cons_row[c]] : h_rowless_.at(c).rhs;
+    }
+}
+// The blocks of one call: X and Y of launch_tab_solve with the nucleus parts of the explicit inverse, the scan's partials and results.
+struct Engine::RhsRun {
+    static constexpr int R = RG_BATCH;
+    ReqContext ctx;
+    DevBuf<double> X, Y, XK, YK, lrh, psum, pviol, osum, oviol;
+    DevBuf<int> ppos, opos;
+    TabBufs tb{};
+    RhsBufs b{};
+    int J;
+    RhsRun(Engine& e, size_t nbat) : ctx(e, std::vector<int>(1, 0), false), J(ctx.J) {
+        hipStream_t st = e.st;
+        const size_t m = (size_t)e.m_, blk = m * R + R, nblk = (size_t)rhs_blocks(e.m_), k = e.fac_on_ ? 0 : (size_t)e.k_;
+        X.ensure(blk, 0, st); Y.ensure(blk, 0, st);
+        if (k > 0) {
+            XK.ensure(k * R + R, 0, st); YK.ensure(k * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
+        }
+        psum.ensure(nblk * R, 0, st); pviol.ensure(nblk * R, 0, st); ppos.ensure(nblk * R, 0, st);
+        osum.ensure(nbat * R, 0, st); oviol.ensure(nbat * R, 0, st); opos.ensure(nbat * R, 0, st);
+        static_cast<SolveBufs&>(tb) = ctx.sb;
+        tb.X = X.p; tb.Y = Y.p; tb.XK = XK.p; tb.YK = YK.p; tb.lrh = lrh.p;
+        b.X = X.p; b.Y = Y.p; b.psum = psum.p; b.pviol = pviol.p; b.ppos = ppos.p;
+    }
+    void batch(size_t q) { b.osum = osum.p + q * R; b.oviol = oviol.p + q * R; b.opos = opos.p + q * R; }
+    // algorithmic bytes of one batch of nreq right-hand sides over n listed rows: the scatter (row, value | current value, the write),
+    // the blocks X and Y (cleared, written, read) and the solve as tab_dense counts it, the scan (per position the basic column, its
+    // cost, value and bounds, per right-hand side its y; apply writes x_B), the partials written and read
+    double bytes(const Engine& e, size_t n, int nreq, bool apply) const {
+        const double m = e.m_, k = e.fac_on_ ? 0 : e.k_, nz = (double)e.h_rcol.size();
+        return (apply ? 20.0 : 28.0) * (double)n * nreq + 32.0 * m * R +
+               (e.fac_on_ ? nreq * (24.0 + 16.0 * J) * m : 8.0 * k * k + 16.0 * J * k + 32.0 * k * R + nz * (12.0 + 8.0 * R)) +
+               (36.0 + 8.0 * nreq + (apply ? 8.0 : 0.0)) * m + 40.0 * (double)rhs_blocks(e.m_) * R;
+    }
+};
+
+// Checks first, nothing is changed before they pass.
+void Engine::set_rhs(const std::vector<uint64_t>& cons, const std::vector<double>& rhs, RhsInfo& info) {
+    check_rhs_list(cons, "set_rhs");
+    for (double v : rhs)
+        if (!std::isfinite(v)) throw MlpError(-1, "set_rhs: a right-hand side is NaN or infinite");
+    info = RhsInfo();
+    info.requests = cons.size();
+    if (cons.empty()) return;
+    // a constraint without terms: 0 op rhs must stay true (try_new's rule)
+    for (size_t i = 0; i < cons.size(); ++i) {
+        if (h_cons_row[cons[i]] >= 0) continue;
+        const int op = h_rowless_.at(cons[i]).op;
+        if (!(op == 0 ? (0.0 == rhs[i]) : op == 1 ? (0.0 <= rhs[i]) : (0.0 >= rhs[i]))) throw LpFail{1};
+    }
+    CallTimer timer(stats);
+    // step 1: the requests by row, delta = rhs' - rhs, exact zeros dropped
+    std::vector<std::pair<int, double>> moves;  // (row, new right-hand side)
+    for (size_t i = 0; i < cons.size(); ++i) {
+        const int row = h_cons_row[cons[i]];
+        if (row < 0) {
+            Rowless& r = h_rowless_.at(cons[i]);
+            if (r.rhs != rhs[i]) info.changed += 1;
+            r.rhs = rhs[i];
+        } else if (rhs[i] - h_rhs[row] != 0.0) {
+            moves.emplace_back(row, rhs[i]);
+        }
+    }
+    std::sort(moves.begin(), moves.end());
+    info.changed += moves.size();
+    budget_exhausted = false;
+    if (moves.empty() || m_ == 0) {  // (every bit of the state stays)
+        timer.finish(info.pivots, info.wall_ms);
+        return;
+    }
+    cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
+    // step 2: the scatter, ONE FTRAN, x_B += y and obj += c_B . y
+    pull_ctl();  // (k_ and the count of pending terms as the device holds them)
+    sync_view();
+    const size_t n = moves.size();
+    std::vector<int> hrow(n);
+    std::vector<double> hdelta(n);
+    for (size_t i = 0; i < n; ++i) {
+        hrow[i] = moves[i].first;
+        hdelta[i] = moves[i].second - h_rhs[moves[i].first];
+    }
+    DevBuf<int> drow;
+    DevBuf<double> ddelta;
+    drow.upload(hrow, st); ddelta.upload(hdelta, st);
+    RhsRun run(*this, 1);
+    run.b.row = drow.p; run.b.val = ddelta.p; run.b.cur = nullptr; run.b.n = (long)n;
+    run.batch(0);
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
+    launch_rhs_scatter(hview, run.b, 0, 1, st);
+    launch_tab_solve(hview, geom(), run.tb, 0, 1, st);
+    launch_rhs_scan(hview, run.b, 1, 1, st);
+    HIPCHECK(hipEventRecord(ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(st));
+    info.solves = 1;
+    info.batches = 1;
+    info.device_ms = ev.ms();
+    info.bytes = run.bytes(*this, n, 1, true);
+    // step 3: the host's vector follows
+    for (const auto& mv : moves) h_rhs[mv.first] = mv.second;
+    values_dirty = true;
+    // steps 4, 5: ONE dual re-solve when a basic value left its bounds
+    if (!basic_values_feasible()) {
+        ensure_beta();  // (only in front of a re-solve)
+        primal_feasible = false;
+        restore_feasibility();
+    }
+    timer.finish(info.pivots, info.wall_ms);
+}
+
+// The read: nothing is written but private buffers.  Per batch the host reads back nothing; at the end four numbers per scenario.
+void Engine::rhs_scenarios(const std::vector<uint64_t>& cons, const double* rhs, size_t S, double* bound, uint8_t* feasible, double* worst,
+                           int64_t* worst_col, RhsInfo& info) {
+    constexpr int R = RG_BATCH;
+    check_rhs_list(cons, "rhs_scenarios");
+    const size_t n = cons.size();
+    for (uint64_t c : cons)
+        if (h_cons_row[c] < 0) throw MlpError(-1, "rhs_scenarios: the constraint has no terms, hence no row");
+    for (size_t i = 0; i < S * n; ++i)
+        if (!std::isfinite(rhs[i])) throw MlpError(-1, "rhs_scenarios: a right-hand side is NaN or infinite");
+    info = RhsInfo();
+    info.requests = n;
+    info.scenarios = S;
+    if (S == 0) return;
+    const double t0 = now_s();
+    const double sg = direction == 1 ? -1.0 : 1.0, obj = cur_obj_val();  // (pull_ctl: k_ and the pending terms as the device holds them)
+    if (n == 0 || m_ == 0) {  // the current point itself: a solved model is feasible
+        for (size_t s = 0; s < S; ++s) {
+            bound[s] = sg * obj;
+            feasible[s] = 1;
+            worst[s] = 0.0;
+            worst_col[s] = -1;
+        }
+        info.wall_ms = (now_s() - t0) * 1e3;
+        return;
+    }
+    sync_view();
+    const size_t nbat = (S + R - 1) / R;
+    std::vector<int> hrow(n);
+    std::vector<double> hcur(n);
+    for (size_t i = 0; i < n; ++i) {
+        hrow[i] = h_cons_row[cons[i]];
+        hcur[i] = h_rhs[hrow[i]];
+    }
+    DevBuf<int> drow;
+    DevBuf<double> dcur, dval;
+    drow.upload(hrow, st); dcur.upload(hcur, st);
+    dval.ensure(S * n, 0, st);
+    HIPCHECK(hipMemcpyAsync(dval.p, rhs, sizeof(double) * S * n, hipMemcpyHostToDevice, st));
+    RhsRun run(*this, nbat);
+    run.b.row = drow.p; run.b.val = dval.p; run.b.cur = dcur.p; run.b.n = (long)n;
+    const Geom g = geom();
+    EventPair ev;
+    HIPCHECK(hipEventRecord(ev.e[0], st));
+    for (size_t q = 0; q < nbat; ++q) {
+        const int nreq = (int)std::min<size_t>(R, S - q * R);
+        run.batch(q);
+        launch_rhs_scatter(hview, run.b, (long)(q * R), nreq, st);
+        launch_tab_solve(hview, g, run.tb, 0, nreq, st);
+        launch_rhs_scan(hview, run.b, nreq, 0, st);
+        info.bytes += run.bytes(*this, n, nreq, false);
+    }
+    HIPCHECK(hipEventRecord(ev.e[1], st));
+    HIPCHECK(hipGetLastError());
+    std::vector<double> hsum(nbat * R), hviol(nbat * R);
+    std::vector<int> hpos(nbat * R);
+    HIPCHECK(hipMemcpyAsync(hsum.data(), run.osum.p, sizeof(double) * hsum.size(), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(hviol.data(), run.oviol.p, sizeof(double) * hviol.size(), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(hpos.data(), run.opos.p, sizeof(int) * hpos.size(), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
+    std::vector<int64_t> cons_of_row((size_t)m_, -1);
+    for (size_t c = 0; c < h_cons_row.size(); ++c)
+        if (h_cons_row[c] >= 0) cons_of_row[h_cons_row[c]] = (int64_t)c;
+    for (size_t s = 0; s < S; ++s) {
+        const int p = hpos[s];
+        if (p >= m_) throw MlpError(-3, "rhs_scenarios: the scan returned an impossible position");
+        bound[s] = sg * (obj + hsum[s]);
+        feasible[s] = p < 0 ? 1 : 0;
+        worst[s] = p < 0 ? 0.0 : hviol[s];
+        const int v = p < 0 ? -1 : h_basic_vars[p];
+        worst_col[s] = v < 0 ? -1 : (v < num_vars ? (int64_t)v : (int64_t)num_vars + cons_of_row[v - num_vars]);
+    }
+    info.solves = S;
+    info.batches = nbat;
+    info.device_ms = ev.ms();
+    info.wall_ms = (now_s() - t0) * 1e3;
 }
 }  // namespace mlp

@@ -724,6 +724,28 @@ int tab_wt_stripes(int k);
 void launch_tab_rhs(const DevView& dv, const TabBufs& b, const int* req, int nreq, int mode, hipStream_t st);
 // one batch of solves: Y = B^-1 X, or transposed Y = B^-T X
 void launch_tab_solve(const DevView& dv, const Geom& g, const TabBufs& b, int transpose, int nreq, hipStream_t st);
+// new right-hand sides of a solved model and the batched what-if read (rhs.inc): the changes go into the interleaved block X of TabBufs,
+// launch_tab_solve runs between the two launches here
+struct RhsBufs {
+    const int* row;     // n: row of a listed constraint (the rows of a call are distinct)
+    const double* val;  // set_rhs: n changes of the right-hand side; scenarios: [S][n] new right-hand sides as the caller gave them
+    const double* cur;  // scenarios: n current right-hand sides of the listed rows; set_rhs: nullptr (val holds the changes themselves)
+    double* X;          // [m][RG_BATCH]: the changes by row, zero elsewhere
+    const double* Y;    // [m][RG_BATCH]: B^-1 X by position
+    double* psum;       // rhs_blocks(m) x RG_BATCH: per-workgroup partial sums of c_B y
+    double* pviol;      // rhs_blocks(m) x RG_BATCH: per-workgroup largest violation of x_B + y
+    int* ppos;          // rhs_blocks(m) x RG_BATCH: its position (lowest on a tie; INT_MAX: none)
+    double* osum;       // RG_BATCH per batch: sum_p c_B[p] y[p]
+    double* oviol;      // RG_BATCH per batch: largest violation (0: none)
+    int* opos;          // RG_BATCH per batch: its position (-1: none)
+    long n;
+};
+int rhs_blocks(int m);  // workgroups of the scan (= rows of psum / pviol / ppos)
+// X = 0, then column r < nreq of X gets val[(s0 + r) * n + i] - cur[i] at row[i]
+void launch_rhs_scatter(const DevView& dv, const RhsBufs& b, long s0, int nreq, hipStream_t st);
+// per column r < nreq over all positions: sum c_B y and the (violation, position) maximum of x_B + y against [loB - EPS, hiB + EPS];
+// apply = 1 (set_rhs, nreq = 1): x_B += y of column 0 and the sum added to the device-held objective
+void launch_rhs_scan(const DevView& dv, const RhsBufs& b, int nreq, int apply, hipStream_t st);
 // blocked in-place Gauss-Jordan inversion of the nucleus held in dv.W (inverse.inc); *flag = 1: singular
 void launch_blocked_inverse(const DevView& dv, int k, double* rowbuf, int nrowbuf, int* piv, int* src, double* prow, double* ckey,
                             int* cidx, int* flag, hipStream_t st);

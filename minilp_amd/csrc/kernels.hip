@@ -5752,6 +5752,7 @@ void launch_build_nucleus(const DevView& dv, const Geom& g, double* Kd, int k, h
 #include "fixing.inc"  // reduced-cost bounds from a cutoff (one classifying pass, deterministic compaction; side-effect free) and the kernels of fix_vars / unfix_vars
 #include "bounds.inc"  // new bounds for structural variables: classification, commit, and the device-to-device list of the reduced-cost bounds
 #include "propagate.inc"  // bound propagation from row activities: a CSR pass and a CSC pass per Jacobi round, the list by fixing.inc's compaction (side-effect free)
+#include "rhs.inc"  // new right-hand sides: the changes scattered into the block of tableau.inc, one scan of x_B + B^-1 db after its FTRAN (16 what-if reads per batch)
 
 void launch_gauss_jordan(double* Kd, double* Winv, int k, int ld, int* d_flag, double* d_scratch, hipStream_t st) {
     if (k <= 0) return;
