@@ -326,8 +326,9 @@ private:
     bool bounds_mirror_stale_ = false;
     void host_bounds();
     struct CutoffRun;  // the private device buffers of one run of launch_cutoff_bounds
-    struct ShiftBufs;  // the blocks of the shift that fix_vars and set_var_bounds share
-    double shift_basic_values(BoundBufs& b, ShiftBufs& w);
+    struct BasisRep;    // the representation of B^-1 one call finds, with the compact factor's private vectors (engine.hip)
+    struct SolveBlock;  // the one owner of the blocks of a dense solve and of the TabBufs around them (engine.hip)
+    double shift_basic_values(BoundBufs& b, SolveBlock& w, DevBuf<double>& delta);  // the shift that fix_vars and set_var_bounds share
     // The body that fix_vars and set_var_bounds share: classify the requests (ascending variable number), shift the basic values if a
     // request moves, commit, follow with the host mirrors.  before_commit sees the counts while nothing has changed yet and may refuse.
     struct Moves {
@@ -352,7 +353,14 @@ private:
     std::map<uint64_t, Rowless> h_rowless_;
     // the checks set_rhs and rhs_scenarios share (nothing is written): solved, in range, no constraint twice
     void check_rhs_list(const std::vector<uint64_t>& cons, const char* who) const;
-    struct RhsRun;  // the private device buffers of one set_rhs / rhs_scenarios call
+    struct RhsRun;  // the SolveBlock, the scan's partials and the outputs of one set_rhs / rhs_scenarios call
+    // variable of [A | I] -> user column (j structural, num_vars + c the slack of constraint c; -1 stays -1), through row -> constraint
+    struct ColumnMap {
+        int num_vars;
+        std::vector<int64_t> cons_of_row;
+        int64_t operator()(int v) const { return v < 0 ? -1 : (v < num_vars ? (int64_t)v : (int64_t)num_vars + cons_of_row[v - num_vars]); }
+    };
+    ColumnMap user_columns() const;
     std::vector<int> h_rptr, h_rcol;
     std::vector<double> h_rval;
     // Host view of the columns: only what the host logic needs — the length of every column and, for singleton
@@ -621,6 +629,7 @@ private:
     void watch_drift(bool pivoted);  // drift monitor of the inverse, after the records of a batch
     void optimize();              // solver.rs:487-511
     void restore_feasibility();   // solver.rs:513-547
+    void warm_resolve();          // restore_feasibility from the current basis with a fresh budget: the tail of every mutator
     void recalc_obj_coeffs();     // solver.rs:1199-1231
     int fix_var_apply(int var, double val);  // fix_var without its re-solve: forced dual pivot (basic) or shift (non-basic), then the fixed flags; returns the column
     void calc_col_coeffs(int col);                          // solver.rs:671-677
@@ -648,7 +657,7 @@ private:
         double device_ms = 0;                // HIP events around the launches
         double bytes = 0;                    // algorithmic bytes of the generation
     };
-    struct ReqContext;  // the padded requests and the private compact-factor vectors of one batched read (engine.hip)
+    struct ReqContext;  // the padded requests of one batched read, around the BasisRep they are served from (engine.hip)
     std::vector<int> cut_round_positions(const std::vector<int>& vars, const std::string& who, const uint8_t* var_is_int, bool refs) const;
     RowBatches sparse_row_batches(const std::vector<int>& pos, int mode, const std::function<void(size_t, const RowBatch&)>& emit,
                                   const uint8_t* gmi_mask = nullptr, double gmi_away = 0.0);

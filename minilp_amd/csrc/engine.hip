@@ -2616,17 +2616,36 @@ void Engine::recalc_basic_vals() {
     values_dirty = true;
 }
 
+// What a mutator reports about its own run: the pivots and the wall time of the call.
+struct CallTimer {
+    Stats& stats;
+    const double t0 = now_s();
+    const uint64_t it0;
+    explicit CallTimer(Stats& s) : stats(s), it0(s.iterations) {}
+    double ms() const { return (now_s() - t0) * 1e3; }
+    void finish() { stats.solve_wall_s += now_s() - t0; }
+    void finish(uint64_t& pivots, double& wall_ms, bool add = false) {  // add: on top of what the info holds already (a round of cuts)
+        finish();
+        pivots = (add ? pivots : 0) + stats.iterations - it0;
+        wall_ms = (add ? wall_ms : 0.0) + ms();
+    }
+};
+// The warm re-solve of every mutator that moved the point: the dual loop from the current basis, with a fresh budget.
+void Engine::warm_resolve() {
+    primal_feasible = false;
+    budget_exhausted = false;
+    restore_feasibility();
+}
+
 void Engine::fix_var(int var, double val) {  // solver.rs:378-415
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    double t0 = now_s();
+    CallTimer timer(stats);
     ensure_beta();
     host_bounds();
     if (val < h_lo[var] || val > h_hi[var]) throw LpFail{1};
     fix_var_apply(var, val);
-    primal_feasible = false;
-    budget_exhausted = false;
-    restore_feasibility();
-    stats.solve_wall_s += now_s() - t0;
+    warm_resolve();
+    timer.finish();
 }
 int Engine::fix_var_apply(int var, double val) {
     int col;
@@ -2769,7 +2788,7 @@ void Engine::append_rows_on_device(const std::vector<Constraint>& cs, size_t old
 // singleton column (then: rebuild).
 void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gomory) {
     cold_start_ = false;  // a warm-start re-solve: short, lazy graph capture
-    const double t0 = now_s();
+    CallTimer timer(stats);
     if (!primal_feasible || !dual_feasible) throw MlpError(-1, "add_constraints: model not solved (solver.rs:555-556)");
     // The compact factor SURVIVES new rows.  A new slack is a column singleton on its new row — the first level of the peel, whatever
     // else the row holds — so the factor of the extended basis is one more refactorisation (a re-peel of the current basis, ~1 ms:
@@ -2796,7 +2815,7 @@ void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gom
     h_cons_row.insert(h_cons_row.end(), cons_row.begin(), cons_row.end());
     const int R = (int)rows.size();
     if (R == 0) {
-        info.wall_ms += (now_s() - t0) * 1e3;
+        info.wall_ms += timer.ms();
         return;
     }
     fetch_values();
@@ -2886,13 +2905,8 @@ void Engine::add_constraints(std::vector<Constraint> cs, CutInfo& info, bool gom
         }
     }
     info.rows += (uint64_t)R;
-    primal_feasible = false;
-    budget_exhausted = false;
-    const uint64_t it0 = stats.iterations;
-    restore_feasibility();
-    info.pivots += stats.iterations - it0;
-    stats.solve_wall_s += now_s() - t0;
-    info.wall_ms += (now_s() - t0) * 1e3;
+    warm_resolve();
+    timer.finish(info.pivots, info.wall_ms, true);  // (on top of the cut generation's own figures)
 }
 
 namespace {
@@ -2905,29 +2919,33 @@ struct EventPair {  // (destroyed on every way out, a throwing HIPCHECK included
         for (auto& x : e)
             if (x) (void)hipEventDestroy(x);
     }
+    void start(hipStream_t st) { HIPCHECK(hipEventRecord(e[0], st)); }  // in front of the timed launches
+    void stop(hipStream_t st) {                                         // behind them: the second record and the launch check
+        HIPCHECK(hipEventRecord(e[1], st));
+        HIPCHECK(hipGetLastError());
+    }
     double ms() const {  // between the two records, once the stream has been synchronised
         float t = 0.0f;
         HIPCHECK(hipEventElapsedTime(&t, e[0], e[1]));
         return (double)t;
     }
 };
+// "Listed twice" for every list of variables or constraints; `text` is the caller's whole message.
+template <class T>
+void require_distinct(std::vector<T> list, const std::string& text) {
+    std::sort(list.begin(), list.end());
+    if (std::adjacent_find(list.begin(), list.end()) != list.end()) throw MlpError(-1, text);
+}
 }  // namespace
-// What one call of a batched read holds for its batches (sparse_row_batches, ranging, tab_dense): the requests padded to whole batches of
-// RG_BATCH (-1 at the empty places) with their device copy, the representation of B^-1 the kernels will find and the private vectors of
-// the compact factor's one-solve-per-request path.  The caller has called pull_ctl().
-struct Engine::ReqContext {
-    static constexpr int R = RG_BATCH;
-    const size_t n, nbat;
-    std::vector<int> h;
-    DevBuf<int> d;
+// The representation of B^-1 that the kernels of one call will find, and the private vectors of the compact factor's
+// one-solve-per-request path.  The caller has called pull_ctl().
+struct Engine::BasisRep {
     DevBuf<double> unit, tau;
     DevBuf<double2> rv;
     SolveBufs sb{};
     int N, J;            // total variables; pending rank-1 terms
     size_t rows_binv;    // stored length of a row / column of B^-1: m (compact factor) or the nucleus size
-    ReqContext(Engine& e, const std::vector<int>& ids, bool on_device = true) : n(ids.size()), nbat((n + R - 1) / R), h(nbat * R, -1) {
-        std::copy(ids.begin(), ids.end(), h.begin());
-        if (on_device) d.upload(h, e.st);
+    explicit BasisRep(Engine& e) {
         const size_t m = (size_t)e.m_;
         sb.k = e.fac_on_ ? 0 : e.k_;
         sb.fac = e.fac_on_ ? 1 : 0;
@@ -2941,26 +2959,75 @@ struct Engine::ReqContext {
         J = e.fac_on_ || e.hview.lrJ ? e.h_ctl->nlow : 0;
         rows_binv = e.fac_on_ ? m : (size_t)e.k_;
     }
+};
+// What one call of a batched read holds for its batches (sparse_row_batches, ranging, branch_penalties, tab_dense): the requests padded to
+// whole batches of RG_BATCH (-1 at the empty places) with their device copy, around the representation they are served from.
+struct Engine::ReqContext {
+    static constexpr int R = RG_BATCH;
+    const BasisRep& rep;
+    const size_t n, nbat;
+    std::vector<int> h;
+    DevBuf<int> d;
+    ReqContext(Engine& e, const BasisRep& rep_, const std::vector<int>& ids, bool on_device = true)
+        : rep(rep_), n(ids.size()), nbat((n + R - 1) / R), h(nbat * R, -1) {
+        std::copy(ids.begin(), ids.end(), h.begin());
+        if (on_device) d.upload(h, e.st);
+    }
     int count(size_t q) const { return (int)std::min<size_t>(R, n - q * R); }  // requests of batch q
     const int* host(size_t q) const { return h.data() + q * R; }
     const int* dev(size_t q) const { return d.p + q * R; }
     RangingBufs bufs(size_t q, double* blk) const {  // of batch q, around the caller's block
         RangingBufs b{};
-        static_cast<SolveBufs&>(b) = sb;
+        static_cast<SolveBufs&>(b) = rep.sb;
         b.blk = blk;
         b.req = d.p ? dev(q) : nullptr;
-        b.N = N;
+        b.N = rep.N;
         return b;
     }
     // Algorithmic bytes the batched reads share.  Per batch: a block of `rows` x R (cleared, then written) and one pass over A (12 bytes
     // per entry) with a gather of R doubles per entry; per request: the stored row / column of B^-1 the block is made of with its
     // pending terms (the compact factor's solve is counted as its pending terms).
-    double block_bytes(size_t rows) const { return (double)nbat * 16.0 * (double)rows * R + (double)n * (8.0 + 16.0 * J) * (double)rows_binv; }
+    double block_bytes(size_t rows) const {
+        return (double)nbat * 16.0 * (double)rows * R + (double)n * (8.0 + 16.0 * rep.J) * (double)rep.rows_binv;
+    }
     double pass_bytes(double nz) const { return (double)nbat * nz * (12.0 + 8.0 * R); }
     // ... and of the sparse rows: per batch the dense block [N][R] (written once, read by the count and by the fill) with `per_var` bytes
     // per variable and `per_cnt` per counter on top; the emitted rows (12 bytes per term)
     double rows_bytes(size_t m, double nz, double per_var, double per_cnt, size_t ncnt, size_t nnz) const {
-        return block_bytes(m) + pass_bytes(nz) + (double)nbat * (24.0 * (double)N * R + per_var * N + per_cnt * (double)ncnt) + 12.0 * (double)nnz;
+        return block_bytes(m) + pass_bytes(nz) + (double)nbat * (24.0 * (double)rep.N * R + per_var * rep.N + per_cnt * (double)ncnt) + 12.0 * (double)nnz;
+    }
+};
+// The one owner of the blocks of a dense solve (launch_tab_solve) and of the TabBufs around them: X and Y [m][R] interleaved, and for the
+// explicit inverse with a nucleus the nucleus parts XK, YK with the scratch of the pending terms.  solve = false: rows of B^-1, which are
+// no solve (Y alone is the block); transposed: the BTRAN partials.  Nothing here synchronises: the block must outlive the stream's work.
+struct Engine::SolveBlock {
+    static constexpr int R = RG_BATCH;
+    static constexpr double F_BATCH = 12.0 + 8.0 * R, F_SINGLE = 20.0;  // bytes per entry of the F product: R gathers, or one (solve_bytes)
+    const BasisRep rep;
+    const double m, k, nz, part_bytes;
+    const size_t len;  // of X and Y
+    DevBuf<double> X, Y, XK, YK, part, lrh;
+    TabBufs tb{};
+    SolveBlock(Engine& e, bool solve = true, bool transposed = false)
+        : rep(e), m(e.m_), k(rep.sb.k), nz((double)e.h_rcol.size()),
+          part_bytes(transposed ? 16.0 * (double)tab_wt_stripes(rep.sb.k) * k * R : 0.0), len((size_t)e.m_ * R + R) {
+        hipStream_t st = e.st;
+        const size_t kk = (size_t)rep.sb.k;
+        Y.ensure(len, 0, st);
+        if (solve) X.ensure(len, 0, st);
+        if (solve && kk > 0) {
+            XK.ensure(kk * R + R, 0, st); YK.ensure(kk * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
+            if (transposed) part.ensure((size_t)tab_wt_stripes(rep.sb.k) * kk * R + R, 0, st);
+        }
+        static_cast<SolveBufs&>(tb) = rep.sb;
+        tb.X = X.p; tb.Y = Y.p; tb.XK = XK.p; tb.YK = YK.p; tb.part = part.p; tb.lrh = lrh.p;
+    }
+    // Algorithmic bytes of one batch of nreq right-hand sides: the blocks X and Y (cleared / written, read), one read of W0 (8 k^2) with
+    // its pending terms, the gathered nucleus parts (and the BTRAN partials), one pass over the basis columns of A for the F product at
+    // f_width bytes per entry; compact factor: counted as its pending terms per solve, like the ranging.
+    double solve_bytes(int nreq, double f_width) const {
+        return 32.0 * m * R + (rep.sb.fac ? nreq * (24.0 + 16.0 * rep.J) * m
+                                          : 8.0 * k * k + 16.0 * rep.J * k + 32.0 * k * R + part_bytes + nz * f_width);
     }
 };
 // Sparse rows out of dense blocks [N][RG_BATCH], batch by batch: the host side that add_gomory_cuts, add_gmi_cuts and tableau_rows share.  Per
@@ -2974,7 +3041,8 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int m
     const Geom g = geom();
     constexpr int R = RG_BATCH;
     const int m = m_, N = N_;
-    ReqContext ctx(*this, pos);
+    const BasisRep rep(*this);
+    ReqContext ctx(*this, rep, pos);
     RowBatches out;
     out.nbat = ctx.nbat;
     const int nseg = cut_segments(N);
@@ -2997,10 +3065,9 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int m
     std::vector<double> hv;
     for (size_t q = 0; q < out.nbat; ++q) {
         const int nreq = ctx.count(q);
-        HIPCHECK(hipEventRecord(e0.e[0], st));
+        e0.start(st);
         launch_rows_generate(dv, g, ctx.bufs(q, blk.p), (RowKind)mode, &gb, nreq, ctx.host(q), dense.p, cnt.p, off.p, scan.p, len.p, rhs.p, st);
-        HIPCHECK(hipEventRecord(e0.e[1], st));
-        HIPCHECK(hipGetLastError());
+        e0.stop(st);
         int hlen[R];
         double hrhs[R];
         int hstatus[R];
@@ -3011,10 +3078,9 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int m
         size_t total = 0;
         for (int r = 0; r < R; ++r) total += (size_t)hlen[r];
         ocol.ensure(total + 8, 0, st); oval.ensure(total + 8, 0, st);
-        HIPCHECK(hipEventRecord(e1.e[0], st));
+        e1.start(st);
         launch_cut_fill(dv, dense.p, N, off.p, ocol.p, oval.p, mode != 0 && enable_pse, st);
-        HIPCHECK(hipEventRecord(e1.e[1], st));
-        HIPCHECK(hipGetLastError());
+        e1.stop(st);
         hc.resize(total);
         hv.resize(total);
         if (total) {
@@ -3039,9 +3105,7 @@ Engine::RowBatches Engine::sparse_row_batches(const std::vector<int>& pos, int m
 // What a round of cuts asks of its variables, Gomory or GMI: no duplicates, in range, (GMI: marked integer,) basic.  Returns their basic
 // positions; refs: the reference's lines as the messages of the Gomory round quote them.
 std::vector<int> Engine::cut_round_positions(const std::vector<int>& vars, const std::string& who, const uint8_t* var_is_int, bool refs) const {
-    std::vector<int> sorted(vars);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, who + ": duplicate variable");
+    require_distinct(vars, who + ": duplicate variable");
     std::vector<int> pos(vars.size());
     for (size_t t = 0; t < vars.size(); ++t) {
         if (var_is_int && !var_is_int[vars[t]]) throw MlpError(-1, who + ": variable is not marked integer");
@@ -3720,10 +3784,9 @@ void Engine::compute_duals(Duals& out) {
     b.bpart = bpart.p; b.rpart = rpart.p; b.cert = cert.p; b.rhs = rhs.p;
     b.N = N; b.nv = nv; b.k = k; b.fac = fac_on_ ? 1 : 0;
     EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
+    ev.start(st);
     launch_duals(dv, g, b, st);
-    HIPCHECK(hipEventRecord(ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    ev.stop(st);
     std::vector<double> hr((size_t)N), hpi((size_t)m), hc(16);
     if (N) HIPCHECK(hipMemcpyAsync(hr.data(), r.p, sizeof(double) * N, hipMemcpyDeviceToHost, st));
     if (m) HIPCHECK(hipMemcpyAsync(hpi.data(), pi.p, sizeof(double) * m, hipMemcpyDeviceToHost, st));
@@ -3744,11 +3807,8 @@ void Engine::compute_duals(Duals& out) {
     out.max_bound_viol = hc[2]; out.bound_viol_at = (int64_t)hc[3];
     out.max_dual_inf = hc[4]; out.dual_inf_at = (int64_t)hc[5];
     out.btran_residual = hc[6]; out.btran_residual_at = (int64_t)hc[7];
-    out.max_row_viol = hc[10]; out.row_viol_at = -1;
-    if (hc[11] >= 0.0) {  // row -> constraint
-        for (size_t c = 0; c < h_cons_row.size(); ++c)
-            if (h_cons_row[c] == (int64_t)hc[11]) { out.row_viol_at = (int64_t)c; break; }
-    }
+    out.max_row_viol = hc[10];
+    out.row_viol_at = hc[11] >= 0.0 && hc[11] < (double)m ? user_columns().cons_of_row[(size_t)hc[11]] : -1;  // row -> constraint
     // algorithmic bytes: one read of W0 (8 k^2) and of the pending terms (16 J k), or the compact factor's solve (counted as its
     // pending terms, 16 J m); two passes over A (12 bytes per entry + an 8-byte gather), the per-variable and per-row vectors
     const double nz = (double)h_rcol.size();
@@ -3846,7 +3906,8 @@ void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du
         }
         std::vector<int> ids(solve.size());
         for (size_t q = 0; q < solve.size(); ++q) ids[q] = solve[q].first;
-        ReqContext ctx(*this, ids);
+        const BasisRep rep(*this);
+        ReqContext ctx(*this, rep, ids);
         const size_t nbat = ctx.nbat;
         const int nblk = ranging_blocks(g, kind, N);
         const size_t rows = (kind == 0 || fac_on_) ? (size_t)m : (size_t)k;
@@ -3854,14 +3915,13 @@ void Engine::ranging(int kind, const std::vector<uint64_t>& idx, const Duals& du
         blk.ensure(rows * R + R, 0, st); part.ensure((size_t)nblk * 2 * R, 0, st); out.ensure(nbat * 2 * R, 0, st);
         if (kind == 0) r.upload(du.r_int, st);
         EventPair ev;
-        HIPCHECK(hipEventRecord(ev.e[0], st));
+        ev.start(st);
         for (size_t q = 0; q < nbat; ++q) {
             RangingBufs b = ctx.bufs(q, blk.p);
             b.r = r.p; b.part = part.p; b.out = out.p + q * 2 * R;
             launch_ranging_batch(dv, g, b, kind, ctx.count(q), ctx.host(q), st);
         }
-        HIPCHECK(hipEventRecord(ev.e[1], st));
-        HIPCHECK(hipGetLastError());
+        ev.stop(st);
         std::vector<double> ho(nbat * 2 * R);
         HIPCHECK(hipMemcpyAsync(ho.data(), out.p, sizeof(double) * ho.size(), hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
@@ -3919,7 +3979,8 @@ void Engine::branch_penalties(const std::vector<int>& vars, const uint8_t* var_i
     constexpr int R = RG_BATCH;
     std::vector<int> ids(solve.size());
     for (size_t q = 0; q < solve.size(); ++q) ids[q] = solve[q].first;
-    ReqContext ctx(*this, ids);
+    const BasisRep rep(*this);
+    ReqContext ctx(*this, rep, ids);
     const size_t nbat = ctx.nbat;
     const int nblk = ranging_blocks(g, 0, N);
     DevBuf<double> blk, r, f, pval, oval;
@@ -3941,7 +4002,7 @@ void Engine::branch_penalties(const std::vector<int>& vars, const uint8_t* var_i
     bb.mask = var_is_int ? dmask.p : nullptr;
     bb.pval = pval.p; bb.pcol = pcol.p;
     EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
+    ev.start(st);
     launch_branch_heads(dv, ctx.dev(0), f.p, (int)nbat, st);
     for (size_t q = 0; q < nbat; ++q) {
         RangingBufs b = ctx.bufs(q, blk.p);
@@ -3950,17 +4011,13 @@ void Engine::branch_penalties(const std::vector<int>& vars, const uint8_t* var_i
         bb.oval = oval.p + q * 2 * R; bb.ocol = ocol.p + q * 2 * R;
         launch_branch_batch(dv, g, b, bb, ctx.count(q), ctx.host(q), st);
     }
-    HIPCHECK(hipEventRecord(ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    ev.stop(st);
     std::vector<double> hv(nbat * 2 * R);
     std::vector<int> hc(nbat * 2 * R);
     HIPCHECK(hipMemcpyAsync(hv.data(), oval.p, sizeof(double) * hv.size(), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(hc.data(), ocol.p, sizeof(int) * hc.size(), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    std::vector<int64_t> cons_of_row((size_t)m, -1);
-    for (size_t c = 0; c < h_cons_row.size(); ++c)
-        if (h_cons_row[c] >= 0) cons_of_row[h_cons_row[c]] = (int64_t)c;
-    auto column = [&](int v) -> int64_t { return v < 0 ? -1 : (v < num_vars ? (int64_t)v : (int64_t)num_vars + cons_of_row[v - num_vars]); };
+    const ColumnMap column = user_columns();
     for (size_t q = 0; q < solve.size(); ++q) {
         const size_t t = solve[q].second;
         down[t] = hv[2 * q];
@@ -3989,14 +4046,16 @@ int Engine::tab_internal_col(uint64_t col, const char* what) const {
 }
 void Engine::basis_head(std::vector<uint64_t>& out) {
     pull_ctl();
-    std::vector<uint64_t> cons_of_row((size_t)m_, 0);
-    for (size_t c = 0; c < h_cons_row.size(); ++c)
-        if (h_cons_row[c] >= 0) cons_of_row[h_cons_row[c]] = c;
+    const ColumnMap column = user_columns();
     out.resize((size_t)m_);
-    for (int p = 0; p < m_; ++p) {
-        const int v = h_basic_vars[p];
-        out[p] = v < num_vars ? (uint64_t)v : (uint64_t)num_vars + cons_of_row[v - num_vars];
-    }
+    for (int p = 0; p < m_; ++p) out[p] = (uint64_t)column(h_basic_vars[p]);
+}
+// variable of [A | I] -> user column, through row -> constraint (the inverse of h_cons_row); built per call
+Engine::ColumnMap Engine::user_columns() const {
+    ColumnMap map{num_vars, std::vector<int64_t>((size_t)m_, -1)};
+    for (size_t c = 0; c < h_cons_row.size(); ++c)
+        if (h_cons_row[c] >= 0) map.cons_of_row[h_cons_row[c]] = (int64_t)c;
+    return map;
 }
 void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, double* out, TableauInfo& info) {
     constexpr int R = RG_BATCH;
@@ -4004,7 +4063,7 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
     sync_view();
     const DevView& dv = hview;
     const Geom g = geom();
-    const int m = m_, k = fac_on_ ? 0 : k_;
+    const int m = m_;
     const size_t ncons = h_cons_row.size();
     const bool by_cons_out = op == 0 || op == 4;  // result by row -> by constraint
     const size_t out_stride = by_cons_out ? ncons : (size_t)m, in_stride = op == 3 ? ncons : (size_t)m;
@@ -4016,24 +4075,15 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
     std::vector<int> ids(solve.size(), -1);
     if (op < 3)
         for (size_t q = 0; q < solve.size(); ++q) ids[q] = req[solve[q]];
-    ReqContext ctx(*this, ids, op < 3);
+    SolveBlock blk(*this, op != 0, op == 4);
+    ReqContext ctx(*this, blk.rep, ids, op < 3);
     const size_t nbat = ctx.nbat;
-    DevBuf<double> X, Y, XK, YK, part, lrh;
-    const size_t blk = (size_t)m * R + R;
-    Y.ensure(blk, 0, st);
-    if (op != 0) X.ensure(blk, 0, st);
-    if (!fac_on_ && k > 0 && op != 0) {
-        XK.ensure((size_t)k * R + R, 0, st); YK.ensure((size_t)k * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
-        if (op == 4) part.ensure((size_t)tab_wt_stripes(k) * k * R + R, 0, st);
-    }
-    TabBufs b{};
-    static_cast<SolveBufs&>(b) = ctx.sb;
-    b.X = X.p; b.Y = Y.p; b.XK = XK.p; b.YK = YK.p; b.part = part.p; b.lrh = lrh.p;
+    const TabBufs& b = blk.tb;
     std::vector<int> row_of_cons(h_cons_row);
-    std::vector<double> hX, hY(blk);
-    if (op >= 3) hX.resize(blk);
+    std::vector<double> hX, hY(blk.len);
+    if (op >= 3) hX.resize(blk.len);
     EventPair ev;
-    double ms_total = 0.0;
+    double ms_total = 0.0, bytes = 0.0;  // (the solves, batch by batch; rows of B^-1: as the ranging block)
     for (size_t q = 0; q < nbat; ++q) {
         const int nreq = ctx.count(q);
         if (op >= 3) {  // the right-hand sides of the batch, interleaved
@@ -4047,20 +4097,20 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
                     for (int p = 0; p < m; ++p) hX[(size_t)p * R + r] = src[p];
                 }
             }
-            HIPCHECK(hipMemcpyAsync(X.p, hX.data(), sizeof(double) * (size_t)m * R, hipMemcpyHostToDevice, st));
+            HIPCHECK(hipMemcpyAsync(blk.X.p, hX.data(), sizeof(double) * (size_t)m * R, hipMemcpyHostToDevice, st));
         }
-        HIPCHECK(hipEventRecord(ev.e[0], st));
+        ev.start(st);
         if (op == 0) {  // the block of rows IS the result
-            launch_ranging_block(dv, g, ctx.bufs(q, Y.p), 0, nreq, ctx.host(q), st);
+            launch_ranging_block(dv, g, ctx.bufs(q, blk.Y.p), 0, nreq, ctx.host(q), st);
         } else {
             if (op < 3) launch_tab_rhs(dv, b, ctx.dev(q), nreq, op, st);
             launch_tab_solve(dv, g, b, op == 4 ? 1 : 0, nreq, st);
         }
-        HIPCHECK(hipEventRecord(ev.e[1], st));
-        HIPCHECK(hipGetLastError());
-        HIPCHECK(hipMemcpyAsync(hY.data(), Y.p, sizeof(double) * (size_t)m * R, hipMemcpyDeviceToHost, st));
+        ev.stop(st);
+        HIPCHECK(hipMemcpyAsync(hY.data(), blk.Y.p, sizeof(double) * (size_t)m * R, hipMemcpyDeviceToHost, st));
         HIPCHECK(hipStreamSynchronize(st));
         ms_total += ev.ms();
+        bytes += blk.solve_bytes(nreq, SolveBlock::F_BATCH);
         for (int r = 0; r < nreq; ++r) {
             double* dst = out + solve[q * R + r] * out_stride;
             if (by_cons_out) {
@@ -4070,17 +4120,7 @@ void Engine::tab_dense(int op, const std::vector<int>& req, const double* rhs, d
             }
         }
     }
-    // algorithmic bytes per batch: the blocks X and Y (cleared / written, read), one read of W0 (8 k^2) with its pending terms, the
-    // gathered nucleus parts, one pass over the basis columns of A for the F product (12 bytes per entry + a gather of R doubles);
-    // rows of B^-1: as the ranging block; compact factor: counted as its pending terms per solve, like the ranging
-    const int J = ctx.J;
-    if (op == 0)
-        info.bytes = ctx.block_bytes((size_t)m);
-    else if (fac_on_)
-        info.bytes = (double)nbat * 32.0 * (double)m * R + (double)solve.size() * (24.0 + 16.0 * J) * m;
-    else
-        info.bytes = (double)nbat * (32.0 * (double)m * R + 8.0 * (double)k * k + 16.0 * J * k + 32.0 * (double)k * R
-                                     + (op == 4 ? 16.0 * (double)tab_wt_stripes(k) * k * R : 0.0)) + ctx.pass_bytes((double)h_rcol.size());
+    info.bytes = op == 0 ? ctx.block_bytes((size_t)m) : bytes;
     info.batches = nbat;
     info.device_ms = ms_total;
 }
@@ -4149,16 +4189,12 @@ void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_
     if (cols.empty()) return;
     sync_view();
     constexpr int R = RG_BATCH;
-    const int N = N_;
-    std::vector<uint32_t> col_of_var((size_t)N);  // variable of [A | I] -> user column (monotone: rows are numbered in constraint order)
-    for (int j = 0; j < num_vars; ++j) col_of_var[j] = (uint32_t)j;
-    for (size_t c = 0; c < h_cons_row.size(); ++c)
-        if (h_cons_row[c] >= 0) col_of_var[(size_t)num_vars + h_cons_row[c]] = (uint32_t)(num_vars + c);
+    const ColumnMap column = user_columns();  // (monotone: rows are numbered in constraint order)
     const RowBatches rb = sparse_row_batches(pos, 0, [&](size_t q, const RowBatch& bt) {
         size_t at = 0;
         for (int r = 0; r < bt.nreq; ++r) {  // rows are request-major, each sorted by variable
             for (int e = 0; e < bt.len[r]; ++e) {
-                indices.push_back(col_of_var[bt.col[at + e]]);
+                indices.push_back((uint32_t)column(bt.col[at + e]));
                 values.push_back(bt.val[at + e]);
             }
             at += (size_t)bt.len[r];
@@ -4173,7 +4209,7 @@ void Engine::tableau_rows(const std::vector<uint64_t>& cols, std::vector<uint64_
 
 // ------------------------------------------------------------------ fixing (fixing.inc)
 // One run of launch_cutoff_bounds on private buffers (nothing is read back here): the list lies in ovar / olo / ohi, its length at count();
-// ev.e[0] is recorded in front of the launches, the caller records ev.e[1] behind its own.
+// ev.start() stands in front of the launches, the caller's ev.stop() behind its own.
 struct Engine::CutoffRun {
     EventPair ev;
     DevBuf<int> tcnt, toff, sums;
@@ -4187,7 +4223,7 @@ struct Engine::CutoffRun {
 void Engine::cutoff_launch(double g, const uint8_t* var_is_int, CutoffRun& r) {
     cutoff_alloc(var_is_int, r);
     r.b.g = g;
-    HIPCHECK(hipEventRecord(r.ev.e[0], st));
+    r.ev.start(st);
     launch_cutoff_bounds(hview, r.b, r.sums.p, st);
 }
 // the staging, the list and the uploaded marks of one compaction over the structural variables (propagate_bounds compacts its list
@@ -4225,8 +4261,7 @@ void Engine::cutoff_bounds(double g, const uint8_t* var_is_int, std::vector<uint
     if (nv <= 0 || !(g < std::numeric_limits<double>::infinity())) return;  // g = +inf: nothing is tightened
     CutoffRun r;
     cutoff_launch(g, var_is_int, r);
-    HIPCHECK(hipEventRecord(r.ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    r.ev.stop(st);
     const int total = cutoff_read(r, "cutoff_bounds", &vars, &lo, &hi, &info.listed_fixed);
     info.listed = (uint64_t)total;
     // algorithmic bytes: per variable its location (4), and for a non-basic one its flags, reduced cost and bounds (25; the value of a
@@ -4253,32 +4288,16 @@ int Engine::cutoff_read(const CutoffRun& r, const char* who, std::vector<uint32_
 }
 
 // The shift that fix_vars and set_var_bounds share: b.var / b.diff hold the moves of non-basic columns; r = A delta, ONE FTRAN through the
-// dense right-hand-side path of whichever representation of B^-1 is live, x_B -= B^-1 r.  Nothing is synchronised: w must outlive the
-// stream's work.  Returns the algorithmic bytes.
-struct Engine::ShiftBufs {
-    DevBuf<double> delta, X, Y, XK, YK, lrh;
-};
-double Engine::shift_basic_values(BoundBufs& b, ShiftBufs& w) {
-    constexpr int R = RG_BATCH;
-    const DevView& dv = hview;
-    const Geom g = geom();
-    const int m = m_, k = fac_on_ ? 0 : k_;
-    ReqContext ctx(*this, std::vector<int>(1, 0), false);
-    const size_t blk = (size_t)m * R + R;
-    w.delta.ensure((size_t)N_ + 1, 0, st); w.X.ensure(blk, 0, st); w.Y.ensure(blk, 0, st);
-    if (!fac_on_ && k > 0) {
-        w.XK.ensure((size_t)k * R + R, 0, st); w.YK.ensure((size_t)k * R + R, 0, st); w.lrh.ensure((size_t)LR_MAX * R, 0, st);
-    }
-    TabBufs tb{};
-    static_cast<SolveBufs&>(tb) = ctx.sb;
-    tb.X = w.X.p; tb.Y = w.Y.p; tb.XK = w.XK.p; tb.YK = w.YK.p; tb.lrh = w.lrh.p;
-    b.delta = w.delta.p; b.X = w.X.p; b.Y = w.Y.p;
-    launch_fix_rhs(dv, b, N_, st);
-    launch_tab_solve(dv, g, tb, 0, 1, st);
-    launch_fix_apply(dv, b, st);
-    // the blocks X and Y, delta and the CSR pass, then the solve as tab_dense counts it
-    return 32.0 * (double)m * R + 8.0 * (double)N_ + 20.0 * (double)h_rcol.size() + 16.0 * m +
-           (fac_on_ ? (24.0 + 16.0 * ctx.J) * m : 8.0 * (double)k * k + 16.0 * ctx.J * k + 32.0 * (double)k * R + 20.0 * (double)h_rcol.size());
+// dense right-hand-side path of whichever representation of B^-1 is live, x_B -= B^-1 r.  Nothing is synchronised: w and delta must
+// outlive the stream's work.  Returns the algorithmic bytes.
+double Engine::shift_basic_values(BoundBufs& b, SolveBlock& w, DevBuf<double>& delta) {
+    delta.ensure((size_t)N_ + 1, 0, st);
+    b.delta = delta.p; b.X = w.X.p; b.Y = w.Y.p;
+    launch_fix_rhs(hview, b, N_, st);
+    launch_tab_solve(hview, geom(), w.tb, 0, 1, st);
+    launch_fix_apply(hview, b, st);
+    // delta and the CSR pass, the move of x_B, then the solve of one column (the F product gathers one double per entry)
+    return 8.0 * (double)N_ + 20.0 * (double)h_rcol.size() + 16.0 * m_ + w.solve_bytes(1, SolveBlock::F_SINGLE);
 }
 
 // The body that fix_vars and set_var_bounds share (fixing.inc): the requests, sorted by variable — a fixing passes its non-basic ones only,
@@ -4298,7 +4317,7 @@ Engine::Moves Engine::move_nonbasic(const std::vector<int>& hvar, const std::vec
     b.var = dvar.p; b.lo = dlo.p; b.hi = dhi.p; b.target = dtarget.p; b.diff = ddiff.p; b.flags = dflags.p; b.cnt = dcnt.p;
     b.var_lo = d_lo.p; b.var_hi = d_hi.p; b.n = (long)n;
     EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
+    ev.start(st);
     launch_move_classify(hview, b, fix ? 1 : 0, st);
     int cnt[3] = {0, 0, 0};
     HIPCHECK(hipMemcpyAsync(cnt, dcnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
@@ -4311,14 +4330,15 @@ Engine::Moves Engine::move_nonbasic(const std::vector<int>& hvar, const std::vec
     mv.bytes = (fix ? 50.0 : 58.0) * (double)n;
     if (before_commit) before_commit(mv);
     // from here on the state changes: the shift (r = A delta, ONE FTRAN through the dense right-hand-side path, x_B -= B^-1 r), the commit
-    ShiftBufs w;
+    std::unique_ptr<SolveBlock> w;  // (alive until the synchronisation below)
+    DevBuf<double> delta;
     if (mv.shifted && m_ > 0) {
-        mv.bytes += shift_basic_values(b, w);
+        w = std::make_unique<SolveBlock>(*this);
+        mv.bytes += shift_basic_values(b, *w, delta);
         mv.solves = 1;
     }
     launch_move_commit(hview, b, fix ? 1 : 0, mv.shifted ? 1 : 0, st);
-    HIPCHECK(hipEventRecord(ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    ev.stop(st);
     HIPCHECK(hipStreamSynchronize(st));
     mv.device_ms = ev.ms();
     mv.bytes += (fix ? 18.0 : 41.0) * (double)n;  // commit: variable, location, diff, flags read and the flags written; new bounds: the bounds as well
@@ -4334,29 +4354,12 @@ Engine::Moves Engine::move_nonbasic(const std::vector<int>& hvar, const std::vec
     return mv;
 }
 
-// What fix_vars, unfix_vars and set_var_bounds report about their own run: the pivots and the wall time of the call.
-struct CallTimer {
-    Stats& stats;
-    const double t0 = now_s();
-    const uint64_t it0;
-    explicit CallTimer(Stats& s) : stats(s), it0(s.iterations) {}
-    void finish(uint64_t& pivots, double& wall_ms) {
-        pivots = stats.iterations - it0;
-        stats.solve_wall_s += now_s() - t0;
-        wall_ms = (now_s() - t0) * 1e3;
-    }
-};
-
 // The batched forms.  Checks first, nothing is changed before they pass.
 void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& vals, FixInfo& info) {
     info = FixInfo();
     info.requests = vars.size();
     if (vars.empty()) return;
-    {
-        std::vector<int> sorted(vars);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, "fix_vars: a variable is listed twice");
-    }
+    require_distinct(vars, "fix_vars: a variable is listed twice");
     host_bounds();
     for (size_t i = 0; i < vars.size(); ++i)
         if (!(vals[i] >= h_lo[vars[i]] && vals[i] <= h_hi[vars[i]])) throw LpFail{1};
@@ -4393,11 +4396,7 @@ void Engine::fix_vars(const std::vector<int>& vars, const std::vector<double>& v
         info.forced_pivots += 1;
     }
     // step 3: ONE re-solve (none when nothing moved at a primal-feasible point: only flags were written)
-    if (moved || !primal_feasible) {
-        primal_feasible = false;
-        budget_exhausted = false;
-        restore_feasibility();
-    }
+    if (moved || !primal_feasible) warm_resolve();
     timer.finish(info.pivots, info.wall_ms);
 }
 
@@ -4426,10 +4425,9 @@ uint64_t Engine::release_fixed(const std::vector<int>& vars, FixInfo& info, cons
     BoundBufs b{};
     b.var = dvar.p; b.n = (long)hvar.size();
     EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
+    ev.start(st);
     launch_fix_release(hview, b, st);
-    HIPCHECK(hipEventRecord(ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    ev.stop(st);
     HIPCHECK(hipStreamSynchronize(st));
     info.device_ms = ev.ms();
     info.bytes = 33.0 * (double)hvar.size();
@@ -4470,11 +4468,10 @@ void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<doub
     if (vars.empty()) return;
     const size_t n = vars.size();
     const double inf = std::numeric_limits<double>::infinity();
+    require_distinct(vars, "set_var_bounds: a variable is listed twice");
     std::vector<size_t> ord(n);  // the requests in ascending variable number
     for (size_t i = 0; i < n; ++i) ord[i] = i;
     std::sort(ord.begin(), ord.end(), [&](size_t a, size_t b) { return vars[a] < vars[b]; });
-    for (size_t i = 1; i < n; ++i)
-        if (vars[ord[i]] == vars[ord[i - 1]]) throw MlpError(-1, "set_var_bounds: a variable is listed twice");
     for (size_t i = 0; i < n; ++i)
         if (std::isnan(lo[i]) || std::isnan(hi[i]) || lo[i] == inf || hi[i] == -inf)
             throw MlpError(-1, "set_var_bounds: a bound is NaN, a lower bound +inf or an upper bound -inf");
@@ -4516,8 +4513,7 @@ void Engine::set_var_bounds(const std::vector<int>& vars, const std::vector<doub
     budget_exhausted = false;
     if (mv.shifted || (mv.basic && !basic_values_feasible())) {
         ensure_beta();  // (only in front of a re-solve: a call that moves nothing leaves every bit of the state)
-        primal_feasible = false;
-        restore_feasibility();
+        warm_resolve();
     }
     timer.finish(info.pivots, info.wall_ms);
 }
@@ -4530,8 +4526,7 @@ uint64_t Engine::tighten_by_reduced_cost(double g, const uint8_t* var_is_int, Bo
     CutoffRun r;
     cutoff_launch(g, var_is_int, r);
     launch_bounds_apply_list(hview, r.b, r.count(), d_lo.p, d_hi.p, st);
-    HIPCHECK(hipEventRecord(r.ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    r.ev.stop(st);
     const int total = cutoff_read(r, "tighten_by_reduced_cost");
     if (total) bounds_mirror_stale_ = true;
     cold_start_ = false;
@@ -4571,7 +4566,7 @@ void Engine::propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::ve
     b.rowfin = rowfin.p; b.rowinf = rowinf.p; b.word = word.p;
     b.m = m; b.N = N; b.nv = nv;
     info.requests = (uint64_t)N;
-    HIPCHECK(hipEventRecord(r.ev.e[0], st));
+    r.ev.start(st);
     launch_prop_setup(hview, b, st);
     int cur = 0;
     for (int rnd = 1; rnd <= max_rounds; ++rnd) {
@@ -4592,12 +4587,10 @@ void Engine::propagate_bounds(const uint8_t* var_is_int, int max_rounds, std::ve
     int total = 0;
     if (!infeasible) {
         launch_prop_list(hview, b, r.b, cur, r.sums.p, st);
-        HIPCHECK(hipEventRecord(r.ev.e[1], st));
-        HIPCHECK(hipGetLastError());
+        r.ev.stop(st);
         total = cutoff_read(r, "propagate_bounds", &vars, &lo, &hi, &info.listed_fixed);
     } else {
-        HIPCHECK(hipEventRecord(r.ev.e[1], st));
-        HIPCHECK(hipGetLastError());
+        r.ev.stop(st);
         HIPCHECK(hipStreamSynchronize(st));
     }
     info.listed = (uint64_t)total;
@@ -4632,9 +4625,7 @@ void Engine::check_rhs_list(const std::vector<uint64_t>& cons, const char* who) 
     if (!solved()) throw MlpError(-1, std::string(who) + ": model not solved");  // (the re-solve is the dual one: it needs a dual-feasible basis)
     for (uint64_t c : cons)
         if (c >= h_cons_row.size()) throw MlpError(-1, std::string(who) + ": constraint out of range");
-    std::vector<uint64_t> sorted(cons);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw MlpError(-1, std::string(who) + ": a constraint is listed twice");
+    require_distinct(cons, std::string(who) + ": a constraint is listed twice");
 }
 void Engine::constraint_rhs(const uint64_t* cons, uint64_t n, double* out) const {
     for (uint64_t i = 0; i < n; ++i) {
@@ -4643,37 +4634,27 @@ void Engine::constraint_rhs(const uint64_t* cons, uint64_t n, double* out) const
         out[i] = h_cons_row[c] >= 0 ? h_rhs[h_cons_row[c]] : h_rowless_.at(c).rhs;
     }
 }
-// The blocks of one call: X and Y of launch_tab_solve with the nucleus parts of the explicit inverse, the scan's partials and results.
+// What one call holds around its SolveBlock: the scan's partials and results.
 struct Engine::RhsRun {
     static constexpr int R = RG_BATCH;
-    ReqContext ctx;
-    DevBuf<double> X, Y, XK, YK, lrh, psum, pviol, osum, oviol;
+    SolveBlock blk;
+    DevBuf<double> psum, pviol, osum, oviol;
     DevBuf<int> ppos, opos;
-    TabBufs tb{};
     RhsBufs b{};
-    int J;
-    RhsRun(Engine& e, size_t nbat) : ctx(e, std::vector<int>(1, 0), false), J(ctx.J) {
+    const size_t nblk;
+    RhsRun(Engine& e, size_t nbat) : blk(e), nblk((size_t)rhs_blocks(e.m_)) {
         hipStream_t st = e.st;
-        const size_t m = (size_t)e.m_, blk = m * R + R, nblk = (size_t)rhs_blocks(e.m_), k = e.fac_on_ ? 0 : (size_t)e.k_;
-        X.ensure(blk, 0, st); Y.ensure(blk, 0, st);
-        if (k > 0) {
-            XK.ensure(k * R + R, 0, st); YK.ensure(k * R + R, 0, st); lrh.ensure((size_t)LR_MAX * R, 0, st);
-        }
         psum.ensure(nblk * R, 0, st); pviol.ensure(nblk * R, 0, st); ppos.ensure(nblk * R, 0, st);
         osum.ensure(nbat * R, 0, st); oviol.ensure(nbat * R, 0, st); opos.ensure(nbat * R, 0, st);
-        static_cast<SolveBufs&>(tb) = ctx.sb;
-        tb.X = X.p; tb.Y = Y.p; tb.XK = XK.p; tb.YK = YK.p; tb.lrh = lrh.p;
-        b.X = X.p; b.Y = Y.p; b.psum = psum.p; b.pviol = pviol.p; b.ppos = ppos.p;
+        b.X = blk.X.p; b.Y = blk.Y.p; b.psum = psum.p; b.pviol = pviol.p; b.ppos = ppos.p;
     }
     void batch(size_t q) { b.osum = osum.p + q * R; b.oviol = oviol.p + q * R; b.opos = opos.p + q * R; }
     // algorithmic bytes of one batch of nreq right-hand sides over n listed rows: the scatter (row, value | current value, the write),
-    // the blocks X and Y (cleared, written, read) and the solve as tab_dense counts it, the scan (per position the basic column, its
-    // cost, value and bounds, per right-hand side its y; apply writes x_B), the partials written and read
-    double bytes(const Engine& e, size_t n, int nreq, bool apply) const {
-        const double m = e.m_, k = e.fac_on_ ? 0 : e.k_, nz = (double)e.h_rcol.size();
-        return (apply ? 20.0 : 28.0) * (double)n * nreq + 32.0 * m * R +
-               (e.fac_on_ ? nreq * (24.0 + 16.0 * J) * m : 8.0 * k * k + 16.0 * J * k + 32.0 * k * R + nz * (12.0 + 8.0 * R)) +
-               (36.0 + 8.0 * nreq + (apply ? 8.0 : 0.0)) * m + 40.0 * (double)rhs_blocks(e.m_) * R;
+    // the solve, the scan (per position the basic column, its cost, value and bounds, per right-hand side its y; apply writes x_B), the
+    // partials written and read
+    double bytes(size_t n, int nreq, bool apply) const {
+        return (apply ? 20.0 : 28.0) * (double)n * nreq + blk.solve_bytes(nreq, SolveBlock::F_BATCH) +
+               (36.0 + 8.0 * nreq + (apply ? 8.0 : 0.0)) * blk.m + 40.0 * (double)nblk * R;
     }
 };
 
@@ -4729,25 +4710,23 @@ void Engine::set_rhs(const std::vector<uint64_t>& cons, const std::vector<double
     run.b.row = drow.p; run.b.val = ddelta.p; run.b.cur = nullptr; run.b.n = (long)n;
     run.batch(0);
     EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
+    ev.start(st);
     launch_rhs_scatter(hview, run.b, 0, 1, st);
-    launch_tab_solve(hview, geom(), run.tb, 0, 1, st);
+    launch_tab_solve(hview, geom(), run.blk.tb, 0, 1, st);
     launch_rhs_scan(hview, run.b, 1, 1, st);
-    HIPCHECK(hipEventRecord(ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    ev.stop(st);
     HIPCHECK(hipStreamSynchronize(st));
     info.solves = 1;
     info.batches = 1;
     info.device_ms = ev.ms();
-    info.bytes = run.bytes(*this, n, 1, true);
+    info.bytes = run.bytes(n, 1, true);
     // step 3: the host's vector follows
     for (const auto& mv : moves) h_rhs[mv.first] = mv.second;
     values_dirty = true;
     // steps 4, 5: ONE dual re-solve when a basic value left its bounds
     if (!basic_values_feasible()) {
         ensure_beta();  // (only in front of a re-solve)
-        primal_feasible = false;
-        restore_feasibility();
+        warm_resolve();
     }
     timer.finish(info.pivots, info.wall_ms);
 }
@@ -4795,34 +4774,30 @@ void Engine::rhs_scenarios(const std::vector<uint64_t>& cons, const double* rhs,
     run.b.row = drow.p; run.b.val = dval.p; run.b.cur = dcur.p; run.b.n = (long)n;
     const Geom g = geom();
     EventPair ev;
-    HIPCHECK(hipEventRecord(ev.e[0], st));
+    ev.start(st);
     for (size_t q = 0; q < nbat; ++q) {
         const int nreq = (int)std::min<size_t>(R, S - q * R);
         run.batch(q);
         launch_rhs_scatter(hview, run.b, (long)(q * R), nreq, st);
-        launch_tab_solve(hview, g, run.tb, 0, nreq, st);
+        launch_tab_solve(hview, g, run.blk.tb, 0, nreq, st);
         launch_rhs_scan(hview, run.b, nreq, 0, st);
-        info.bytes += run.bytes(*this, n, nreq, false);
+        info.bytes += run.bytes(n, nreq, false);
     }
-    HIPCHECK(hipEventRecord(ev.e[1], st));
-    HIPCHECK(hipGetLastError());
+    ev.stop(st);
     std::vector<double> hsum(nbat * R), hviol(nbat * R);
     std::vector<int> hpos(nbat * R);
     HIPCHECK(hipMemcpyAsync(hsum.data(), run.osum.p, sizeof(double) * hsum.size(), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(hviol.data(), run.oviol.p, sizeof(double) * hviol.size(), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipMemcpyAsync(hpos.data(), run.opos.p, sizeof(int) * hpos.size(), hipMemcpyDeviceToHost, st));
     HIPCHECK(hipStreamSynchronize(st));
-    std::vector<int64_t> cons_of_row((size_t)m_, -1);
-    for (size_t c = 0; c < h_cons_row.size(); ++c)
-        if (h_cons_row[c] >= 0) cons_of_row[h_cons_row[c]] = (int64_t)c;
+    const ColumnMap column = user_columns();
     for (size_t s = 0; s < S; ++s) {
         const int p = hpos[s];
         if (p >= m_) throw MlpError(-3, "rhs_scenarios: the scan returned an impossible position");
         bound[s] = sg * (obj + hsum[s]);
         feasible[s] = p < 0 ? 1 : 0;
         worst[s] = p < 0 ? 0.0 : hviol[s];
-        const int v = p < 0 ? -1 : h_basic_vars[p];
-        worst_col[s] = v < 0 ? -1 : (v < num_vars ? (int64_t)v : (int64_t)num_vars + cons_of_row[v - num_vars]);
+        worst_col[s] = column(p < 0 ? -1 : h_basic_vars[p]);
     }
     info.solves = S;
     info.batches = nbat;
