@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 
 namespace mlp {
@@ -204,6 +205,7 @@ __device__ __forceinline__ void wave_best_p(Cand& c, double& pay) {
         }
     }
 }
+__device__ const double2 g_zero2 = {0.0, 0.0};  // what a round of band partials reads past the last band (k_update_pivot)
 __device__ __forceinline__ void block_best_p(Cand& c, double& pay) {  // result valid in thread 0
     __shared__ double s_key[BLK / 64], s_pay[BLK / 64];
     __shared__ int s_idx[BLK / 64];
@@ -239,10 +241,12 @@ __device__ __forceinline__ bool grid_best_p(Cand& c, double& pay, const DevView&
     Cand x = cand_none();
     double xp = 0.0;
     for (int i = threadIdx.x; i < nblocks; i += blockDim.x) {
+        // (the pay-load is loaded beside the key and the index, not behind the comparison: one round trip, not two)
         Cand t{ld_agent(&v.red_key[i]), ld_agent(&v.red_idx[i])};
+        const double tp = ld_agent(&v.red_key2[i]);
         if (cand_better(t, x)) {
             x = t;
-            xp = ld_agent(&v.red_key2[i]);
+            xp = tp;
         }
     }
     KMARK(v.ctl, 17);
@@ -4195,21 +4199,38 @@ __global__ void __launch_bounds__(BLK) k_reduce_v(DevView v) {
 // read for the last time here), and (b) prices the NEXT iteration from the values it has just
 // written (K1 when next_phase = 0, K6 when 1), so neither a memset nor a pricing kernel is needed
 // inside the replayed graph.
-__global__ void __launch_bounds__(BLK) k_update_pivot(DevView v, int phase, int use_dse, int use_pse, int inline_comb, int n_upd, int pull_inside) {
+// One body, one instance per form of the iteration (launch_update_pivot lists them): what a form does not use — the pull's LDS arrays
+// and pre-loaded registers, the 16-wide round of band partials, the dual list walk, the partition change in the tail blocks — is not
+// compiled into it.  As one kernel with the five as run-time arguments every launch carried all of it: 133 VGPRs, 36 bytes of scratch
+// per lane and 20.6 KB of LDS on gfx950.
+// (amdgpu_num_vgpr counts in units of the unified file of gfx90a and later: 52 are 104 vector registers, what the banded form took with
+// its partials loaded at the point of use.  Left free up to the 128 of four waves per SIMD, the allocator keeps constants live across the
+// trip.  The attribute and the empty asm statements of the body steer this compiler's allocator and nothing else: a compiler that reads them
+// otherwise still computes the same, and tests/test_kernel_resources.py holds every instance to "no scratch, no VGPR spill".)
+template <int PHASE, int DSE, int PSE, int COMB, int PULL>
+__global__ void __launch_bounds__(BLK) __attribute__((amdgpu_num_vgpr(52))) k_update_pivot(DevView v, int n_upd) {
+    static_assert(!PULL || (PHASE == 0 && PSE && !DSE && !COMB), "the pulling forms are primal + PSE + lazy, without the banded sweep");
+    static_assert(!COMB || PHASE == 0, "the band partials are summed in a primal iteration only");
+    constexpr int phase = PHASE, use_dse = DSE, use_pse = PSE, pull_inside = PULL;
     Ctl* c = v.ctl;
-    if (c->halt) return;
     const IterState* it = &c->it;
-    const int status = it->status;
+    // The iteration's scalars are read HERE, beside the status and ahead of the kernel's first store: as scalar loads into scalar
+    // registers.  Read where they are used — behind stores — each was a vector load of one address and a round trip of its own after the
+    // loads it multiplies had landed (entering_diff under `a != 0`, pivot_obj and alpha_sq under `alpha_r != 0`).
+    const int status = it->status, it_r = it->r, q = it->q;
+    const double pc_k = it->pivot_coeff, pivot_obj_k = it->pivot_obj, entering_diff_k = it->entering_diff;
+    const double alpha_sq_k = PSE ? it->alpha_sq : 0.0, rho_sq_k = DSE ? it->rho_sq : 0.0;
+    if (c->halt) return;
     if (status != ITER_PIVOT && status != ITER_FLIP) return;
     KMARK0(c, 12);
     if ((int)blockIdx.x >= n_upd) {  // horizontally fused (dual iteration without PSE): the partition change, which touches
-        if (status == ITER_PIVOT)    // W and the slot maps only — nothing the update blocks read or write
-            struct_update_body(v, c, ((int)blockIdx.x - n_upd) * BLK + threadIdx.x);
+        if constexpr (PHASE == 1 && !PSE) {  // W and the slot maps only — nothing the update blocks read or write
+            if (status == ITER_PIVOT) struct_update_body(v, c, ((int)blockIdx.x - n_upd) * BLK + threadIdx.x);
+        }
         return;
     }
     const bool flip = status == ITER_FLIP;
-    const int r = flip ? -1 : it->r, q = it->q;
-    const double pc = it->pivot_coeff;
+    const int r = flip ? -1 : it_r;
     // pull_inside (small-nucleus primal head, one position per thread): the sparse tableau row — alpha_rj = rho . a_j and the PSE helper
     // v . a_j on the columns the head stamped (solver.rs:685-692, 1126-1132) — is pulled HERE, by the workgroup that updates those
     // positions, instead of by a launch of its own (k_row_pull, 5.8 us + a kernel boundary for ~3 MB of gathers): each workgroup
@@ -4217,16 +4238,19 @@ __global__ void __launch_bounds__(BLK) k_update_pivot(DevView v, int phase, int 
     // for bit), and the update below reads the pair from LDS.  alpha_r / helper are not materialised; (rho, v) is not zeroed here —
     // other workgroups are still reading it — but by the next head, from the list this iteration's head left (Ctl.rv_n).
     constexpr int UPT = 4;  // positions per thread a pulling launch may take at most (launch_update_pivot chooses: one up to 512 workgroups)
-    __shared__ int s_tl[BLK * UPT];
-    __shared__ double s_ta[BLK * UPT], s_th[BLK * UPT];
+    constexpr int NPL = PULL ? BLK * UPT : 1, NPR = PULL ? UPT : 1;  // (the pulling forms alone have the arrays; elsewhere nothing refers to them)
+    __shared__ int s_tl[NPL];
+    __shared__ double s_ta[NPL], s_th[NPL];
     __shared__ int s_tcnt;
-    int my_slot[UPT] = {-1, -1, -1, -1};
+    int my_slot[NPR];
     // (a pulling launch loads its positions' d / gamma / flags HERE, ahead of the pull: behind it, one trip's stores kept the next trip's loads
     // from being issued early — four dependent round trips, 3 us of the 7 a workgroup took in the early window of config 4)
-    double pre_d[UPT] = {0.0, 0.0, 0.0, 0.0}, pre_g[UPT] = {1.0, 1.0, 1.0, 1.0};
-    uint8_t pre_f[UPT] = {0, 0, 0, 0};
+    double pre_d[NPR], pre_g[NPR];
+    uint8_t pre_f[NPR];
     const bool pre = pull_inside && !flip;
-    if (pull_inside) {
+    if constexpr (PULL) {
+#pragma unroll
+        for (int i = 0; i < UPT; ++i) my_slot[i] = -1, pre_d[i] = 0.0, pre_g[i] = 1.0, pre_f[i] = 0;
         if (threadIdx.x == 0) s_tcnt = 0;
         __syncthreads();
         if (!flip) {
@@ -4290,70 +4314,121 @@ __global__ void __launch_bounds__(BLK) k_update_pivot(DevView v, int phase, int 
     // pull_inside == 2: the head has applied the basic side (x_B on supp(alpha_q), position r, alpha_q back to zero) and position q's own
     // entries (d, gamma, flags, nb_vars, x_N) itself: here only the non-basic side remains — the touched columns' d / gamma, the drift
     // check at q, and the pricing scan
-    const bool head_applied = pull_inside == 2;
+    constexpr bool head_applied = PULL == 2;
     const int tmax_eff = head_applied ? v.n : tmax;
     // Dual iteration whose Harris test ran over the listed non-zeros of alpha_r (ratio_dual_list): the non-basic side walks that list —
     // d changes on the non-zeros of the row only (solver.rs:1073-1080), and nothing prices the non-basic side in a dual iteration — instead
     // of loading d / flags / alpha_r of all n positions (6.8 MB of the kernel's 26 on the 400 000-column transport instance).
-    const int keep = (phase == 1 && !use_pse && !inline_comb && !pull_inside && !flip && !v.nb_order && v.ar_list) ? c->ar_keep : -1;
+    int keep = -1;
+    if constexpr (PHASE == 1 && !PSE) keep = (!flip && !v.nb_order && v.ar_list) ? c->ar_keep : -1;
     int trip = 0;
     for (int t = blockIdx.x * BLK + threadIdx.x; t < tmax_eff; t += n_upd * BLK, ++trip) {
         Cand tc = cand_none();
         double tc_d = 0.0;
+        // (opaque per trip: what derives from the scalars alone — the reciprocals inside the divisions by pc and pc^2 — is formed where it is
+        // used, when the band partials are dead, not ahead of the loop of trips in vector registers that stay live across it.  The "s"
+        // constraint asks for scalar registers: right because each of these is one value for the whole launch, read from Ctl)
+        double pc = pc_k, pivot_obj = pivot_obj_k, entering_diff = entering_diff_k, alpha_sq = alpha_sq_k, rho_sq = rho_sq_k;
+        asm volatile("" : "+s"(pc), "+s"(pivot_obj), "+s"(entering_diff), "+s"(alpha_sq), "+s"(rho_sq));
+        int tb = t;  // (... and the index of the band partials in the two rare loops over the bands: no pointers carried from trip to trip)
+        if constexpr (COMB) asm volatile("" : "+v"(tb));
         // (a select chain, not an indexed read: the array stays in registers)
-        const int slot_t = !pull_inside ? -1 : (trip == 0 ? my_slot[0] : (trip == 1 ? my_slot[1] : (trip == 2 ? my_slot[2] : (trip == 3 ? my_slot[3] : -1))));
-        if (t < v.m && !head_applied) {
-            double a = v.alpha_q[t];
-            double xb = v.xB[t], lo = v.loB[t], hi = v.hiB[t], bt = use_dse ? v.beta[t] : 1.0;
-            const double tau_t = (use_dse && !flip) ? v.tau[t] : 0.0;  // loaded with the others, not behind `a != 0`
-            if (t == r) {
-                int ev = it->entering_var;
-                xb = it->entering_new_val;
-                lo = v.var_lo[ev];
-                hi = v.var_hi[ev];
-                v.xB[r] = xb;
-                v.loB[r] = lo;
-                v.hiB[r] = hi;
-                if (use_dse) {
-                    bt = it->rho_sq / (pc * pc);
-                    v.beta[r] = bt;
-                }
-                v.basic_vars[r] = ev;
-                v.var_loc[ev] = r;
-                v.var_loc[it->leaving_var] = -1 - q;
-                if (v.fpk_x) v.fpk_x[it->leaving_var] = 0.0;  // (fpull.inc: alpha_K by variable is zero outside the nucleus basics)
-            } else if (a != 0.0) {
-                xb -= it->entering_diff * a;
-                v.xB[t] = xb;
-                if (use_dse && !flip) {
-                    bt += -2.0 * a * tau_t / pc + it->rho_sq * a * a / (pc * pc);
-                    v.beta[t] = bt;
+        int slot_t = -1;
+        if constexpr (PULL) slot_t = trip == 0 ? my_slot[0] : (trip == 1 ? my_slot[1] : (trip == 2 ? my_slot[2] : (trip == 3 ? my_slot[3] : -1)));
+        // Every load of the trip is issued HERE, as one group ahead of the first store: the compiler cannot rule out that a store of the
+        // basic side aliases a load of the non-basic side, so behind the stores those loads were issued late, and a wait on one of them
+        // waited for the store acknowledgements in front of it as well (the pulling forms were cured of this with pre_d / pre_g / pre_f).
+        // The single positions t == r and tn == q keep their own dependent loads.
+        const bool bas = !head_applied && t < v.m;
+        const bool nbs = keep >= 0 ? t < keep : t < v.n;
+        double a = 0.0, xb = 0.0, lo = 0.0, hi = 0.0, bt = 1.0, tau_t = 0.0;
+        if (bas) {
+            a = v.alpha_q[t];
+            xb = v.xB[t];
+            if constexpr (PHASE == 1) lo = v.loB[t], hi = v.hiB[t];  // (the dual pricing of the position reads them; position r takes its own)
+            if constexpr (DSE) {
+                bt = v.beta[t];
+                if (!flip) tau_t = v.tau[t];  // loaded with the others, not behind `a != 0`
+            }
+        }
+        // non-basic side: thread t serves position tn = nb_order[t] (locality order of the banded sweep: its partials
+        // are indexed by t), or position t itself without an order, or entry t of the list of alpha_r's non-zeros
+        int tn = 0;
+        double dd = 0.0, gm = 1.0, ar_t = 0.0, hp_t = 0.0;
+        uint8_t f = 0;
+        // banded sweep: the band partials of index t, a round of sixteen at a time (all 13 bands of config 4 in the first); of eight with the
+        // eager DSE update, whose beta and tau are live beside them — sixteen do not fit the registers there without spilling
+        constexpr int PBW = COMB ? (DSE ? 8 : 16) : 1;
+        double2 pb[PBW];
+        int nbn = COMB ? v.nbands : 0;
+        // (opaque: what the rounds of band partials derive from the number of bands — sixteen steps, sixteen predicates — is formed where it
+        // is used, not kept in scalar registers from outside the loop of trips, where it spilled)
+        if constexpr (COMB) asm volatile("" : "+s"(nbn));
+        // unconditional loads off one walking pointer — past the last band it stays there, and the sum takes a zero instead: a load under
+        // `u < nbands` each is sixteen branches and as many addresses held in registers
+        const auto load_round0 = [&] {
+            if (nbn > 0) {
+                const double2* bp = v.band_part + t;
+#pragma unroll
+                for (int u = 0; u < PBW; ++u) {
+                    pb[u] = *bp;
+                    bp += (u + 1 < nbn) ? (size_t)v.n : (size_t)0;
                 }
             }
-            v.alpha_q[t] = 0.0;
-            v.tau[t] = 0.0;
-            if (!pull_inside) v.rv[t] = make_double2(0.0, 0.0);
-            if (phase == 1 && !c->forced) tc = price_dual_one(xb, lo, hi, bt, t, use_dse);
-        }
-        if (keep >= 0 ? t < keep : t < v.n) {
-            // non-basic side: thread t serves position tn = nb_order[t] (locality order of the banded sweep: its partials
-            // are indexed by t), or position t itself without an order, or entry t of the list of alpha_r's non-zeros
-            const int tn = keep >= 0 ? v.ar_list[t] : (v.nb_order ? v.nb_order[t] : t);
-            double dd, gm;
-            uint8_t f;
-            if (pre && trip < UPT) {  // (select chains, not indexed reads: the arrays stay in registers)
-                dd = trip == 0 ? pre_d[0] : (trip == 1 ? pre_d[1] : (trip == 2 ? pre_d[2] : pre_d[3]));
-                gm = trip == 0 ? pre_g[0] : (trip == 1 ? pre_g[1] : (trip == 2 ? pre_g[2] : pre_g[3]));
-                f = trip == 0 ? pre_f[0] : (trip == 1 ? pre_f[1] : (trip == 2 ? pre_f[2] : pre_f[3]));
-            } else {
+        };
+        if (nbs) {
+            tn = keep >= 0 ? v.ar_list[t] : (v.nb_order ? v.nb_order[t] : t);
+            bool loaded = false;
+            if constexpr (PULL) {
+                if (pre && trip < UPT) {  // (select chains, not indexed reads: the arrays stay in registers)
+                    dd = trip == 0 ? pre_d[0] : (trip == 1 ? pre_d[1] : (trip == 2 ? pre_d[2] : pre_d[3]));
+                    gm = trip == 0 ? pre_g[0] : (trip == 1 ? pre_g[1] : (trip == 2 ? pre_g[2] : pre_g[3]));
+                    f = trip == 0 ? pre_f[0] : (trip == 1 ? pre_f[1] : (trip == 2 ? pre_f[2] : pre_f[3]));
+                    loaded = true;
+                }
+            }
+            if (!loaded) {
                 dd = v.d[tn];
-                gm = use_pse ? v.gamma[tn] : 1.0;
+                if constexpr (PSE) gm = v.gamma[tn];
                 f = v.nbflags[tn];
             }
+            if constexpr (!COMB && !PULL) {
+                if (!flip && tn >= v.nb_lo && tn < v.nb_hi) {  // the materialised tableau row (and PSE helper) of the position
+                    ar_t = v.alpha_r[tn];
+                    if constexpr (PSE) hp_t = v.helper[tn];
+                }
+            }
+            if constexpr (COMB) {  // (behind the loads that wait for the order: a wait ahead of this branch cannot count what it issues)
+                if (!flip && tn != q && tn >= v.nb_lo && tn < v.nb_hi) load_round0();  // (the positions that sum them, no others)
+            }
+        }
+        // basic side, arithmetic: the stores wait until the non-basic side has consumed its loads (below) — a wait for a load also
+        // waits for every store issued ahead of it
+        int ev = -1;
+        const auto enter_r = [&] {  // position r: the entering variable's value and bounds
+            ev = it->entering_var;
+            xb = it->entering_new_val;
+            lo = v.var_lo[ev];
+            hi = v.var_hi[ev];
+            if (use_dse) bt = rho_sq / (pc * pc);
+        };
+        bool moved = false;  // x_B[t] (and beta[t]) changed
+        if (bas) {
+            if (t == r) {
+                if constexpr (PHASE == 1) enter_r();  // (priced below; a primal iteration takes them with its stores)
+            } else if (a != 0.0) {
+                moved = true;
+                xb -= entering_diff * a;
+                if (use_dse && !flip) bt += -2.0 * a * tau_t / pc + rho_sq * a * a / (pc * pc);
+            }
+            if (phase == 1 && !c->forced) tc = price_dual_one(xb, lo, hi, bt, t, use_dse);
+        }
+        if (nbs) {
             if (tn == q && head_applied) {
                 if (!flip && q >= v.nb_lo && q < v.nb_hi) {
                     // the pivot element computed two ways (FTRAN side / BTRAN side) measures the drift of W
-                    const double ba = slot_t >= 0 ? s_ta[slot_t] : 0.0;
+                    double ba = 0.0;
+                    if constexpr (PULL) ba = slot_t >= 0 ? s_ta[slot_t] : 0.0;
                     const double fa = 1.0 / it->inv_alpha;
                     const double err = fabs(fa - ba) / fmax(1.0, fabs(fa));
                     if (err > c->max_pivot_err || err != err) c->max_pivot_err = err;
@@ -4371,11 +4446,10 @@ __global__ void __launch_bounds__(BLK) k_update_pivot(DevView v, int phase, int 
                     double lnv = it->leaving_new_val;
                     // the pivot element computed two ways (FTRAN side / BTRAN side) measures the drift of W
                     if (q >= v.nb_lo && q < v.nb_hi) {
-                        double ba;
-                        if (inline_comb) {
-                            ba = 0.0;
-                            for (int b = 0; b < v.nbands; ++b) ba += v.band_part[(size_t)b * (size_t)v.n + t].x;
-                        } else if (pull_inside) {
+                        double ba = 0.0;
+                        if constexpr (COMB) {
+                            for (int b = 0; b < v.nbands; ++b) ba += v.band_part[(size_t)b * (size_t)v.n + tb].x;
+                        } else if constexpr (PULL) {
                             ba = slot_t >= 0 ? s_ta[slot_t] : 0.0;
                         } else {
                             ba = v.alpha_r[q];
@@ -4385,10 +4459,10 @@ __global__ void __launch_bounds__(BLK) k_update_pivot(DevView v, int phase, int 
                         if (err > c->max_pivot_err || err != err) c->max_pivot_err = err;
                     }
                     if (v.str_on && !pull_inside) v.alpha_r[q] = 0.0;
-                    dd = -it->pivot_obj;
+                    dd = -pivot_obj;
                     v.d[q] = dd;
                     if (use_pse) {
-                        gm = it->alpha_sq / (pc * pc);
+                        gm = alpha_sq / (pc * pc);
                         v.gamma[q] = gm;
                     }
                     v.nb_vars[q] = lv;
@@ -4400,33 +4474,42 @@ __global__ void __launch_bounds__(BLK) k_update_pivot(DevView v, int phase, int 
                 }
             } else if (!flip && tn >= v.nb_lo && tn < v.nb_hi) {
                 double ar, hp = 0.0;
-                if (inline_comb) {  // banded sweep: sum the per-band partials here (band order) instead of a combine launch
+                if constexpr (COMB) {  // banded sweep: sum the per-band partials here (band order) instead of a combine launch
                     double s1 = 0.0, s2 = 0.0;
-                    for (int b0 = 0; b0 < v.nbands; b0 += 16) {  // sixteen independent loads in flight (all 13 bands of
-                        double2 pb[16];                            // config 4 in one round), summed in band order
+                    // sixteen independent loads in flight, summed in band order: the first round came with the trip's other loads, a
+                    // further one (more than sixteen bands) is loaded here
 #pragma unroll
-                        for (int u = 0; u < 16; ++u)
-                            pb[u] = (b0 + u < v.nbands) ? v.band_part[(size_t)(b0 + u) * (size_t)v.n + t] : make_double2(0.0, 0.0);
+                    for (int u = 0; u < PBW; ++u) {
+                        s1 += u < nbn ? pb[u].x : 0.0;
+                        s2 += u < nbn ? pb[u].y : 0.0;
+                    }
+#pragma unroll 1
+                    for (int b0 = PBW; b0 < nbn; b0 += PBW) {  // (past the last band a load reads a zero: no branch, no select of values)
+                        const double2* bp = v.band_part + (size_t)b0 * (size_t)v.n + tb;
 #pragma unroll
-                        for (int u = 0; u < 16; ++u) {
+                        for (int u = 0; u < PBW; ++u) {
+                            pb[u] = *(b0 + u < nbn ? bp : &g_zero2);
+                            bp += (size_t)v.n;
+                        }
+#pragma unroll
+                        for (int u = 0; u < PBW; ++u) {
                             s1 += pb[u].x;
                             s2 += pb[u].y;
                         }
                     }
                     ar = s1;  // (row_coeffs / the PSE helper are not materialised on this path: nothing reads them — the
                     hp = s2;  // host-paced stepping API, which exposes them, keeps the separate combine kernel)
-                } else if (pull_inside) {
+                } else if constexpr (PULL) {
                     ar = slot_t >= 0 ? s_ta[slot_t] : 0.0;
                     hp = slot_t >= 0 ? s_th[slot_t] : 0.0;
                 } else {
-                    ar = v.alpha_r[tn];
-                    if (use_pse) hp = v.helper[tn];
+                    ar = ar_t, hp = hp_t;
                 }
                 if (ar != 0.0) {
-                    dd -= it->pivot_obj * ar;
+                    dd -= pivot_obj * ar;
                     v.d[tn] = dd;
                     if (use_pse) {
-                        gm += -2.0 * ar * hp / pc + it->alpha_sq * ar * ar / (pc * pc);
+                        gm += -2.0 * ar * hp / pc + alpha_sq * ar * ar / (pc * pc);
                         v.gamma[tn] = gm;
                     }
                     if (v.str_on && !pull_inside) v.alpha_r[tn] = 0.0;  // sparse tableau row: the vector stays zero outside this iteration's touched entries
@@ -4436,6 +4519,27 @@ __global__ void __launch_bounds__(BLK) k_update_pivot(DevView v, int phase, int 
                 tc = price_primal_one(dd, gm, f, tn, use_pse);
                 tc_d = dd;
             }
+        }
+        if (bas) {  // basic side, stores
+            if (t == r) {
+                if constexpr (PHASE == 0) enter_r();
+                v.xB[r] = xb;
+                v.loB[r] = lo;
+                v.hiB[r] = hi;
+                if (use_dse) v.beta[r] = bt;
+                v.basic_vars[r] = ev;
+                v.var_loc[ev] = r;
+                v.var_loc[it->leaving_var] = -1 - q;
+                if (v.fpk_x) v.fpk_x[it->leaving_var] = 0.0;  // (fpull.inc: alpha_K by variable is zero outside the nucleus basics)
+            } else if (moved) {
+                v.xB[t] = xb;
+                if (use_dse && !flip) v.beta[t] = bt;
+            }
+            double zero = 0.0;
+            asm volatile("" : "+v"(zero));  // (formed here: as a constant the four zero registers of the rv store stayed live across the trip)
+            v.alpha_q[t] = zero;
+            v.tau[t] = zero;
+            if (!pull_inside) v.rv[t] = make_double2(zero, zero);
         }
         if (cand_better(tc, cand)) {  // (ties keep the lowest position whatever the visiting order)
             cand = tc;
@@ -5618,9 +5722,8 @@ void launch_update_pivot(const DevView& dv, const Geom& g, int phase, int use_ds
     int t = g.m > g.n ? g.m : g.n;
     // inline_comb (primal iteration with the banded sweep): the update kernel sums the per-band partials itself
     // with_struct (dual iteration without PSE): the partition change rides in the tail blocks of this launch
-    // one position per thread: measured against 4 per thread (a quarter of the blocks and tickets) the longer per-thread
-    // chain of band-partial loads costs more than the tickets save (109.0 vs 104.3 us per pivot); the kernel strides
-    // only beyond 512 * 4 * 256 positions
+    // one position per thread; the kernel strides only beyond 512 * 4 * 256 positions (the banded form with its partials loaded in one
+    // group, config 4, pivots 200...2 200: 11 762-11 791 pivots/s at one against 11 622-11 684 at two)
     // positions per thread: one up to 512 workgroups (measured against 2 and 4 on config 4, mid / late windows: 244.1 / 244.7 / 248.2 and 663.3 /
     // 664.0 / 667.8 us per pivot), beyond that as many as keep the grid within 512 (the 400 000-column transport instance: 164.6 / 156.2 /
     // 154.0 us per pivot at 1 / 2 / 4 — 1 563 workgroups queue on the ticket and the launch ramp)
@@ -5633,8 +5736,24 @@ void launch_update_pivot(const DevView& dv, const Geom& g, int phase, int use_ds
     const int pull_pt = std::max(1, std::min(4, (blocks_for(pull_inside == 2 ? g.n : t) + 511) / 512));
     if (pull_inside == 2) n_upd = blocks_for(g.n, BLK * pull_pt);   // non-basic side only
     else if (pull_inside) n_upd = blocks_for(t, BLK * pull_pt);
-    hipLaunchKernelGGL(k_update_pivot, dim3(n_upd + (with_struct ? blocks_for(g.cap) : 0)), dim3(BLK), 0, st, dv, phase, use_dse, use_pse,
-                       inline_comb, n_upd, pull_inside);
+    // The forms Engine::plan_iteration can produce — (phase, dse, pse, comb, pull):
+    //   primal (phase 0): dse, pse and comb each 0 | 1, pull 0                                      8 instances
+    //   primal + PSE + lazy (dse 0), sparse tableau row (so comb 0): pull 1 | 2                     2 instances
+    //   dual (phase 1): dse and pse each 0 | 1; never comb (phase 0 only), never pull                4 instances
+    // (with_struct goes with phase 1 without PSE; the list walk of the dual form is decided on the device.)  Anything else is an error.
+    if (with_struct && !(phase == 1 && !use_pse)) throw std::logic_error("k_update_pivot: the partition change rides in the dual form without PSE only");
+    const dim3 grid(n_upd + (with_struct ? blocks_for(g.cap) : 0));
+#define UPD(P, D, S, C, L) \
+    case ((P) << 5 | (D) << 4 | (S) << 3 | (C) << 2 | (L)): hipLaunchKernelGGL((k_update_pivot<P, D, S, C, L>), grid, dim3(BLK), 0, st, dv, n_upd); break
+    switch (phase << 5 | use_dse << 4 | use_pse << 3 | inline_comb << 2 | pull_inside) {
+        UPD(0, 0, 0, 0, 0); UPD(0, 0, 0, 1, 0); UPD(0, 0, 1, 0, 0); UPD(0, 0, 1, 1, 0);
+        UPD(0, 1, 0, 0, 0); UPD(0, 1, 0, 1, 0); UPD(0, 1, 1, 0, 0); UPD(0, 1, 1, 1, 0);
+        UPD(0, 0, 1, 0, 1); UPD(0, 0, 1, 0, 2);
+        UPD(1, 0, 0, 0, 0); UPD(1, 0, 1, 0, 0); UPD(1, 1, 0, 0, 0); UPD(1, 1, 1, 0, 0);
+    default:
+        throw std::logic_error("k_update_pivot: no instance for this form of the iteration");
+    }
+#undef UPD
 }
 void launch_set_iter(const DevView& dv, int status, int q, int r, double lnv, int forced, hipStream_t st) {
     hipLaunchKernelGGL(k_set_iter, dim3(1), dim3(1), 0, st, dv, status, q, r, lnv, forced);
