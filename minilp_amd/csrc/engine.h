@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/minilp_hip.h"  // the report structs (mlp_cut_info ...) are defined there, once
+#include "batch.h"
 #include "kernels.h"
 #include "settings.h"
 
@@ -376,9 +377,12 @@ private:
     bool ranks_share_device = false;
     // the forms of the small-nucleus iteration, decided per batch (the geometry is baked into the graphs): sparse tableau row, k_small_basis,
     // k_primal_head (primal_head.inc: the batch is cut short so that the nucleus stays within the head's slots)
-    bool sb_now = false;
-    bool ph_now = false;
-    bool str_now = false, str_clean = false; // geometry of the batch being run; alpha_r / helper are zero outside touched entries
+    // (geom() and sync_view read them; inside run_loop only enter_row_form and fit_head_room write them)
+    struct BatchForm {
+        bool str = false, sb = false, ph = false;
+    } form;
+    bool str_clean = false;  // alpha_r / helper are zero outside touched entries
+    void leave_sparse_row();  // an iteration outside run_loop: dense tableau row, whatever the last batch used
     DevBuf<int> d_ar_list;   // non-basic positions with alpha_r != 0 (dual iteration, CSC-pull tableau row): the dual Harris test walks the list
     DevBuf<int> d_str_list;
     // hypersparse single-workgroup iteration (hyper.inc)
@@ -625,6 +629,24 @@ private:
 
   private:
     int run_loop(int phase);                             // batches of replays until terminal / budget
+    // the steps of one batch, in run_loop's order (where the batch is decided)
+    void refresh_batch_layout(int phase, bool& fpk_fresh);  // locality order, packed copy of the sweep, packed copy of the nucleus columns
+    int run_hyper_batch(int phase);                      // one launch of the hypersparse kernel; the batch's result (ITER_PIVOT: plan the next)
+    void shard_go_live_if_due(bool want_sparse_row);
+    void enter_row_form(bool want, bool sb);             // form.str / form.sb, the buffers of the sparse row, alpha_r / helper zeroed once per dirty period
+    void plan_graphs_now(BatchPlan& plan, int phase, bool long_run);
+    void fit_head_room(BatchPlan& plan, int phase);      // form.ph; the batch ends before the nucleus can outgrow the head's slots
+    bool fit_factor_room(BatchPlan& plan);               // refactors when due; false: the basis no longer peels, the factor was left (plan again)
+    void clear_batch();                                  // reset ring, clear work
+    void open_batch(int phase);                          // ... and the pricing launch that opens the first iteration
+    void launch_batch(const BatchPlan& plan, int phase);
+    struct SampleShapes {                                // what the byte formulas of a sampled iteration read, as it was before the records were processed
+        size_t nnz_nonbasic;
+        int k;
+        size_t nnz_nucleus;
+    };
+    void account_sample(int phase, const SampleShapes& before);
+    void on_ratio_stall();
     int process_records();
     void watch_drift(bool pivoted);  // drift monitor of the inverse, after the records of a batch
     void optimize();              // solver.rs:487-511

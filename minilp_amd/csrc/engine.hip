@@ -278,9 +278,9 @@ Geom Engine::geom() const {
     // compete for the same CUs), never again after a wait has timed out once
     g.ratio_two = (ratio_two || (shard_world > 1 && ranks_share_device)) ? 1 : 0;
     g.ratio_list = cfg.ratio_spin_limit > 0 ? 1 : 0;  // (a spin limit of 0 is the test hook that makes the in-kernel wait give up: the wait then has to run)
-    g.str = (str_now && !stepping && !fac_on_) ? 1 : 0;
-    g.sb = (g.str && sb_now) ? 1 : 0;
-    g.ph = (g.str && ph_now) ? 1 : 0;
+    g.str = (form.str && !stepping && !fac_on_) ? 1 : 0;
+    g.sb = (g.str && form.sb) ? 1 : 0;
+    g.ph = (g.str && form.ph) ? 1 : 0;
     g.fp = hview.fpk_on ? 1 : 0;
     g.forms = (cfg.ratio_one ? FORM_RATIO_ONE : 0u) | (cfg.tk_ride ? FORM_TK_RIDE : 0u) | (cfg.ratio_list ? FORM_RATIO_LIST : 0u) |
               (cfg.btran_ride ? FORM_BTRAN_RIDE : 0u) | (cfg.v_ride ? FORM_V_RIDE : 0u) | (cfg.small_basis ? FORM_SMALL_BASIS : 0u) |
@@ -511,7 +511,7 @@ DevView* Engine::sync_view() {
     v.hy_var_slot = d_hy_stamp.p ? d_hy_stamp.p + num_vars + m_ : nullptr;
     v.hy_brng = d_hy_stamp.p ? reinterpret_cast<int2*>(d_hy_stamp.p + ((2 * ((size_t)num_vars + m_) + 1) & ~(size_t)1)) : nullptr;
     v.hy_score = d_hy_score.p;
-    v.str_on = (str_now && !stepping && !fac_on_) ? 1 : 0;
+    v.str_on = (form.str && !stepping && !fac_on_) ? 1 : 0;
     fac_fill_view(v);
     v.pad4 = 0;
     v.str_list = d_str_list.p;
@@ -1643,20 +1643,14 @@ int Engine::step_open(StepInfo* out) {
         return ITER_OPTIMAL;
     }
     step_phase = phase;
-    if (str_now) {  // stepped iterations use the dense tableau row (row_coeffs is inspectable in full)
-        str_now = false;
-        view_dirty = true;
-    }
+    leave_sparse_row();  // stepped iterations use the dense tableau row (row_coeffs is inspectable in full)
     ensure_beta();  // stepped iterations maintain beta by the recurrence, from an exact base
     pivot_budget = -1;
     budget_exhausted = false;
     sync_view();
     ensure_nucleus_cap(k_ + 2);
     sync_view();
-    launch_reset_ring(hview, st);
-    launch_clear_work(hview, st);
-    if (phase == 0) launch_price_primal(hview, geom(), enable_pse ? 1 : 0, st);
-    else launch_price_dual(hview, geom(), enable_dse ? 1 : 0, st);
+    open_batch(phase);
     pull_ctl();
     int status = h_ctl->it.status;
     step_pos = 0;
@@ -1784,258 +1778,281 @@ void Engine::watch_drift(bool pivoted) {
     if (pivoted && !(h_ctl->max_pivot_err <= cfg.refresh_tol) && (k_ > 0 || fac_on_)) rebuild_inverse();
 }
 
+// ---- the steps of one batch (run_loop below calls them in this order; the decisions themselves are the pure functions of batch.h)
+void Engine::refresh_batch_layout(int phase, bool& fpk_fresh) {
+    if (!hview.nb_order && use_order && lifetime_pivots >= cfg.order_from) view_dirty = true;  // time to switch the order on
+    sync_view();
+    if (hview.nb_order) refresh_nb_order(false);  // every `cfg.order_every` pivots (same buffer: captured graphs stay valid)
+    if (hview.nb_order && use_pack && pack_built != (hview.pk_ptr != nullptr)) {  // the packed copy came or went
+        view_dirty = true;
+        sync_view();
+    }
+    // pulled F product (fpull.inc): the packed copy of the nucleus columns is rebuilt at the first batch of this loop and every
+    // fpk_every_ pivots (the entries of columns that have left the basis since are dead weight in the rows: dropped by the rebuild)
+    if (phase == 0 && fpk_wanted() && hview.pb_on && (!hview.pb_det || shard_world > 1) && (!fpk_fresh || !fpk_valid_ || lifetime_pivots - fpk_built_at_ >= (uint64_t)fpk_every_)) {
+        fpk_rebuild();
+        fpk_fresh = true;
+    }
+}
+void Engine::clear_batch() {
+    launch_reset_ring(hview, st);
+    launch_clear_work(hview, st);
+}
+void Engine::open_batch(int phase) {
+    clear_batch();
+    if (phase == 0) launch_price_primal(hview, geom(), enable_pse ? 1 : 0, st);  // opens the first iteration
+    else launch_price_dual(hview, geom(), enable_dse ? 1 : 0, st);
+}
+// Hypersparse iteration (hyper.inc): up to RING dual iterations in ONE launch of one workgroup doing only
+// support-restricted work.  Same records, same device state: the two paths alternate freely.
+int Engine::run_hyper_batch(int phase) {
+    (void)phase;  // (hyper_capable: the dual loop only)
+    const int B = clip_batch(RING, pivot_budget, 0);
+    ensure_nucleus_cap(k_ + B + 1);
+    if (fac_on_) return ITER_PIVOT;  // (the capacity request switched to the compact factor: plan the batch again)
+    ensure_hyper();
+    sync_view();
+    clear_batch();
+    launch_hyper_dual(hview, enable_dse ? 1 : 0, B, cfg.hyper_heavy, cfg.hyper_prof ? 1 : 0, st);
+    str_clean = false;  // (the kernel writes alpha_r on its touched columns without zeroing them)
+    pull_ctl();
+    const uint64_t before = stats.iterations;
+    const int res = process_records();
+    stats.hyper_iters += stats.iterations - before;
+    if (h_ctl->hyper_bail) {
+        // the kernel declined an iteration (a list did not fit its LDS capacities, or the update was too much work for
+        // one workgroup): nothing of it was applied; the multi-kernel path takes over for a while — the longer, the
+        // more often this happens in a row (a model that is not hypersparse settles on the multi-kernel path)
+        stats.hyper_bails += 1;
+        if (h_ctl->hyper_bail > 0 && h_ctl->hyper_bail < 10) stats.hyper_bail_reason[h_ctl->hyper_bail] += 1;
+    }
+    const HyperBackoff next = hyper_backoff({hyper_bail_streak, hyper_off_until}, h_ctl->hyper_bail != 0, stats.iterations - before, lifetime_pivots, hyper_backoff_max);
+    hyper_bail_streak = next.streak;
+    hyper_off_until = next.off_until;
+    watch_drift(res == ITER_PIVOT);
+    return res;
+}
+
 int Engine::run_loop(int phase) {
     if (phase == 1) ensure_beta();  // the dual pricing reads beta
     if (fac_on_) pull_ctl();        // (the count of pending rank-1 terms)
     str_clean = false;  // (whatever ran since the last loop may have written alpha_r / helper densely)
     batch_lazy = lazy_now(phase);
     bool fpk_fresh = false;  // (this loop has built its packed copy of the nucleus columns)
-    for (;;) {
+    for (;;) {  // one batch per turn; every `continue` plans the batch again from the top
         if (pivot_budget == 0) {
             budget_exhausted = true;
             return ITER_PIVOT;
         }
+        BatchPlan plan;
         // profile mode: every 8th batch is ONE eager iteration bracketed by HIP events on the
         // launch stream (sweep and fused pass), the others are graph replays as usual
-        const bool long_run = cfg.use_graph && cfg.graph_iters > 1 && graph_batches_in_geom >= 8;
-        const bool sample = profile && (sample_every == 1 || batches_run % (long_run ? 4 : 8) == 0);
+        const bool long_run = batch_long_run(cfg.use_graph, cfg.graph_iters, graph_batches_in_geom);
+        plan.sample = batch_sampled(profile, sample_every, batches_run, long_run);
         batches_run += 1;
-        // Capturing a graph costs milliseconds and is invalidated by every add_constraint (m changes),
-        // so short warm-start re-solves run eagerly; the graph is captured once the same geometry has
-        // survived a few iterations.
-        if (!hview.nb_order && use_order && lifetime_pivots >= cfg.order_from) view_dirty = true;  // time to switch the order on
-        sync_view();
-        if (hview.nb_order) refresh_nb_order(false);  // every `cfg.order_every` pivots (same buffer: captured graphs stay valid)
-        if (hview.nb_order && use_pack && pack_built != (hview.pk_ptr != nullptr)) {  // the packed copy came or went
-            view_dirty = true;
-            sync_view();
-        }
-        // pulled F product (fpull.inc): the packed copy of the nucleus columns is rebuilt at the first batch of this loop and every
-        // fpk_every_ pivots (the entries of columns that have left the basis since are dead weight in the rows: dropped by the rebuild)
-        if (phase == 0 && fpk_wanted() && hview.pb_on && (!hview.pb_det || shard_world > 1) && (!fpk_fresh || !fpk_valid_ || lifetime_pivots - fpk_built_at_ >= (uint64_t)fpk_every_)) {
-            fpk_rebuild();
-            fpk_fresh = true;
-        }
-        // pivots the multi-kernel path still has to take before the hypersparse kernel is tried again (after a bail-out)
-        int hyper_gap = 0;
-        if (hyper_off_until > lifetime_pivots && hyper_capable(phase))
-            hyper_gap = (int)std::min<uint64_t>(hyper_off_until - lifetime_pivots, (uint64_t)1 << 20);
-        if (!sample && hyper_gap == 0 && hyper_capable(phase)) {
-            // Hypersparse iteration (hyper.inc): up to RING dual iterations in ONE launch of one workgroup doing only
-            // support-restricted work.  Same records, same device state: the two paths alternate freely.
-            int B = RING;
-            if (pivot_budget > 0 && (int64_t)B > pivot_budget) B = (int)pivot_budget;
-            ensure_nucleus_cap(k_ + B + 1);
-            if (fac_on_) continue;  // (the capacity request switched to the compact factor: plan the batch again)
-            ensure_hyper();
-            sync_view();
-            launch_reset_ring(hview, st);
-            launch_clear_work(hview, st);
-            launch_hyper_dual(hview, enable_dse ? 1 : 0, B, cfg.hyper_heavy, cfg.hyper_prof ? 1 : 0, st);
-            str_clean = false;  // (the kernel writes alpha_r on its touched columns without zeroing them)
-            pull_ctl();
-            const uint64_t before = stats.iterations;
-            int res = process_records();
-            stats.hyper_iters += stats.iterations - before;
-            if (h_ctl->hyper_bail) {
-                // the kernel declined an iteration (a list did not fit its LDS capacities, or the update was too much work for
-                // one workgroup): nothing of it was applied; the multi-kernel path takes over for a while — the longer, the
-                // more often this happens in a row (a model that is not hypersparse settles on the multi-kernel path)
-                stats.hyper_bails += 1;
-                if (h_ctl->hyper_bail > 0 && h_ctl->hyper_bail < 10) stats.hyper_bail_reason[h_ctl->hyper_bail] += 1;
-                // Dense iterations come in clusters (measured on config 3: handing over one pivot at a time costs 173 bail-outs
-                // and 185 ms against 28 and 172 ms with a back-off): after a run of >= 16 hypersparse iterations the multi-kernel
-                // path takes that one pivot only; after a short run it keeps going for 4, 8, ... 512 pivots before the next attempt
-                if (stats.iterations - before >= 16) {
-                    hyper_bail_streak = 0;
-                    hyper_off_until = lifetime_pivots + 1;
-                } else {
-                    hyper_bail_streak = std::min(hyper_bail_streak + 1, hyper_backoff_max);
-                    hyper_off_until = lifetime_pivots + ((uint64_t)2 << hyper_bail_streak);
-                }
-            } else if (stats.iterations - before >= 16) {
-                hyper_bail_streak = 0;
-            }
-            watch_drift(res == ITER_PIVOT);
+        refresh_batch_layout(phase, fpk_fresh);
+        const bool hyper = hyper_capable(phase);
+        plan.hyper_gap = hyper_gap_of(hyper, hyper_off_until, lifetime_pivots);
+        if (!plan.sample && plan.hyper_gap == 0 && hyper) {
+            const int res = run_hyper_batch(phase);
             if (res != ITER_PIVOT) return res;
             continue;
         }
-        // Sparse tableau row (small nucleus, one GPU): decided per batch — the geometry is baked into the graphs.  alpha_r /
-        // helper must be zero outside the touched entries when such a batch starts: any dense sweep (or the hypersparse
-        // kernel) in between leaves them dirty.
-        {
-            // (sharded solves too: a rank lists and pulls the touched columns of its own block of non-basic positions)
-            const bool want = cfg.str_kmax > 0 && !stepping && !fac_on_ && k_ + RING + 1 <= cfg.str_kmax && max_row_nnz_ <= 4096;
-            if (want != str_now) {
-                str_now = want;
-                view_dirty = true;
-            }
-            // (one workgroup walks all of W in k_small_basis: it pays while the nucleus is small — per pivot of config 4 from the
-            // slack basis 55-57 us against 60-62 up to k = 72, 67.0 against 68.8 at k = 104, 78.9 against 77.9 at k = 120, 105
-            // against 98 at k = 135 (tools/small_basis_curve.py) — so the form is chosen per batch by the size the nucleus can reach)
-            sb_now = want && k_ + RING + 1 <= cfg.sb_kmax;
-            if (shard_world > 1 && !shard_live_ && !(cfg.shard_defer && want && !pump_backend_)) {
-                // the column-block sharding goes live (every rank takes this decision at the same pivot: k_ is replicated) — after the
-                // ranks have shown each other that they ARE the same replica (golive_check throws on every rank otherwise)
-                if (cfg.shard_defer) golive_check();
-                shard_live_ = true;
-                view_dirty = true;
-            }
-            if (str_now) {
-                ensure_hyper();  // the epoch stamps
-                d_str_list.ensure((size_t)num_vars + (size_t)m_ + 192, 0, st);  // touched columns | positions of supp(alpha_q)
-                if (!hview.str_list || hview.str_list != d_str_list.p) view_dirty = true;
-                sync_view();
-                if (!str_clean) {
-                    HIPCHECK(hipMemsetAsync(d_alpha_r.p, 0, sizeof(double) * (size_t)num_vars, st));
-                    HIPCHECK(hipMemsetAsync(d_helper.p, 0, sizeof(double) * (size_t)num_vars, st));
-                    launch_str_reset(hview, st);  // new stamp epoch, aq_n = str_n = 0
-                    str_clean = true;
-                }
-            } else {
-                str_clean = false;
-            }
-        }
-        const bool have_graph = gexec[phase][enable_pse ? 1 : 0][0] != nullptr;
-        // (the one or two iterations handed over by the hypersparse kernel run eagerly: no graph is captured for them)
-        const bool brief = hyper_gap > 0 && hyper_gap <= 4;
-        // (pump transports launch eagerly: measured on the test box, a replayed graph keeps the pump's second stream from making
-        // progress until the graph has drained — its kernels then wait for records that cannot arrive)
-        const bool graph_now = cfg.use_graph && !pump_backend_ && !sample && !brief && (have_graph || eager_iters_in_geom >= 4);
-        if (!have_graph && !brief) eager_iters_in_geom += 1;
-        // long runs move on to graphs of several iterations and batches of a full record ring: one
-        // launch and one host round trip cover more pivots (6 990 -> 7 300 pivots/s on config 4); short
-        // warm-start re-solves never pay for capturing the longer graph
-        // (round 5: a COLD solve — from the slack basis or a loaded basis, not a warm-start re-solve — captures the graph of several iterations
-        // together with the first one-iteration graph: between two graph launches the device idles ~8 us (in-kernel timeline: 33 us of
-        // kernels per pivot, 43 us per pivot on the clock), between two kernels of one graph ~1.4)
-        // (second session of round 5: the compact factor too — a batch between two refactorisations is 32 or 64 pivots, three to six graphs
-        // of ten iterations instead of one graph launch, and ~8 us of idle device, per pivot)
-        const bool multi = graph_now && (long_run || cold_start_) && cfg.graph_iters > 1;
-        int B = graph_now ? (multi ? RING : cfg.batch) : 1;
-        if (pivot_budget > 0 && (int64_t)B > pivot_budget) B = (int)pivot_budget;
-        if (hyper_gap > 0 && B > hyper_gap) B = hyper_gap;
-        {   // small-nucleus primal head: the batch must end before the nucleus can outgrow the kernel's slots
-            const int kmax = std::min(cfg.ph_kmax >= 0 ? cfg.ph_kmax : primal_head_kmax(std::max(max_col_nnz_, 1)), primal_head_kmax(std::max(max_col_nnz_, 1)));
-            bool ph = str_now && phase == 0 && enable_pse && batch_lazy && shard_world == 1 && !stepping && !fac_on_ && kmax > 0 &&
-                      max_row_nnz_ <= HEAD_LIST_CAP && !hview.pb_on && !hview.det_pull && hview.rowinfo != nullptr;
-            if (ph) {
-                const int room = kmax - k_;  // every pivot may add one slot
-                const int Bp = std::min(B, room);
-                if (Bp >= std::min(B, 4)) B = Bp;
-                else ph = false;
-            }
-            ph_now = ph;
-        }
+        // Sparse tableau row (small nucleus, one GPU): decided per batch — the geometry is baked into the graphs.
+        // (sharded solves too: a rank lists and pulls the touched columns of its own block of non-basic positions)
+        // (one workgroup walks all of W in k_small_basis: it pays while the nucleus is small — per pivot of config 4 from the
+        // slack basis 55-57 us against 60-62 up to k = 72, 67.0 against 68.8 at k = 104, 78.9 against 77.9 at k = 120, 105
+        // against 98 at k = 135 (tools/small_basis_curve.py) — so the form is chosen per batch by the size the nucleus can reach)
+        const RowChoice row = row_choice(cfg.str_kmax, cfg.sb_kmax, stepping, fac_on_, k_, RING, max_row_nnz_);
+        shard_go_live_if_due(row.want);  // (reads neither the forms nor the view)
+        enter_row_form(row.want, row.sb);
+        plan_graphs_now(plan, phase, long_run);
+        fit_head_room(plan, phase);
         {
             const bool fac_before = fac_on_;
-            ensure_nucleus_cap(k_ + B + 1);  // (may switch to the compact factor: then the batch is planned again)
+            ensure_nucleus_cap(k_ + plan.B + 1);  // (may switch to the compact factor: then the batch is planned again)
             if (fac_on_ != fac_before) continue;
         }
-        if (fac_on_) {
-            // compact factor: every basis change of the batch appends a rank-1 term; refactor (re-peel the current basis)
-            // when fewer than a batch of them fit — the reference's rule is eta nnz >= LU nnz (solver.rs:1096-1103)
-            int room = fac_period_ - h_ctl->nlow;
-            if (room < std::min(fac_period_, std::max(1, std::min(B, 8)))) {
-                if (!fac_refactor()) {  // the basis no longer peels: back to the explicit inverse
-                    fac_leave();
-                    continue;
-                }
-                room = fac_period_;
-            }
-            if (B > room) B = room;
-        }
+        if (fac_on_ && !fit_factor_room(plan)) continue;
+        split_graphs(plan, cold_start_, cfg.graph_iters);
         sync_view();
-        const DevView& dv = hview;
-        launch_reset_ring(dv, st);
-        launch_clear_work(dv, st);
-        if (phase == 0) launch_price_primal(dv, geom(), enable_pse ? 1 : 0, st);  // opens the first iteration
-        else launch_price_dual(dv, geom(), enable_dse ? 1 : 0, st);
-        if (graph_now) {
-            const int nfull = multi ? B / cfg.graph_iters : 0;  // whole multi-iteration graphs first, the remainder of the batch as one-iteration graphs
-            hipGraphExec_t gm = (multi && (nfull > 0 || cold_start_)) ? get_graph(phase, 1) : nullptr;  // (cold solve: captured ahead of its first use)
-            hipGraphExec_t g1 = (B - nfull * cfg.graph_iters > 0 || !gm) ? get_graph(phase, 0) : nullptr;
-            for (int i = 0; i < nfull; ++i) HIPCHECK(hipGraphLaunch(gm, st));
-            for (int i = nfull * cfg.graph_iters; i < B; ++i) HIPCHECK(hipGraphLaunch(g1, st));
-            graph_batches_in_geom += 1;
-        } else {
-            if (sample)
-                for (auto& e : ev)
-                    if (!e) HIPCHECK(hipEventCreate(&e));
-            record_iteration(plan_iteration(phase), sample);
-        }
-        const size_t nnz_before = nnz_nonbasic;
-        const int k_before = k_;
-        const size_t nnz_nuc_before = sample ? nnz_nucleus_cols() : 0;
+        open_batch(phase);
+        launch_batch(plan, phase);
+        const SampleShapes before{nnz_nonbasic, k_, plan.sample ? nnz_nucleus_cols() : 0};
         pump_until_idle();  // (pump transports: deliver the exchanges of the batch while it runs)
         pull_ctl();
-        int res = process_records();
-        if (sample && h_ctl->ring_n >= 1 && h_ctl->ring[0].status == ITER_PIVOT) {
-            float ms = 0.f;
-            if (geom().str) {
-                if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
-                    stats.str_ms += ms;
-                    stats.str_launches += 1;
-                }
-            } else if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
-                stats.sweep_ms += ms;
-                const double sh = shard_world > 1 ? 1.0 / shard_world : 1.0;  // a rank sweeps its own column block
-                stats.sweep_bytes += sh * (12.0 * (double)nnz_before + 16.0 * num_vars) + 16.0 * m_;
-                stats.sweep_launches += 1;
-            }
-            // (a folding pivot whose fold produced the v partials itself skipped the streaming pass: its empty launch is no sample)
-            const bool pass_skipped = hview.lrJ > 0 && h_ctl->fold && geom().big &&
-                                      fold_fuses_v(hview, enable_pse ? 1 : 0, lazy_now(phase) ? 0 : 1, 0);
-            if (k_before > 1 && !pass_skipped && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) {
-                // the pass over the nucleus inverse, stamped by the kernel itself: in place it reads and writes W (16 k^2),
-                // in the delayed-update mode it only reads W0 (8 k^2; a rank of the row-sharded pass reads its strips only)
-                stats.fused_ms += ms;
-                const double stream_share = hview.wshard ? 1.0 / shard_world : 1.0;
-                stats.fused_bytes += (hview.lrJ > 0 ? 8.0 * stream_share : 16.0) * (double)k_before * (double)k_before;
-                stats.fused_launches += 1;
-            }
-            {
-                float fms = 0.f;
-                if (k_before > 1 && hview.lrJ > 0 && h_ctl->fold && geom().big && hipEventElapsedTime(&fms, ev[10], ev[11]) == hipSuccess) {
-                    stats.fold_ms += fms;  // this pivot folded first: read + write of W0 (and, fused, its part of v)
-                    stats.fold_bytes += 16.0 * (double)k_before * (double)k_before;
-                    stats.fold_launches += 1;
-                }
-            }
-            if (hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess) {
-                stats.update_ms += ms;
-                stats.update_launches += 1;
-            }
-            if (hipEventElapsedTime(&ms, ev[6], ev[7]) == hipSuccess) {
-                // FTRAN of the entering column (as built): the listed columns of W (8 k |list|),
-                // the column itself and the F push through the nucleus columns (12 B per entry)
-                stats.ftran_ms += ms;
-                stats.ftran_bytes += 8.0 * (double)k_before * (double)h_ctl->ring[0].klist_n + 12.0 * (double)nnz_nuc_before +
-                                     12.0 * (double)col_nnz(h_ctl->ring[0].entering_var);
-                stats.ftran_launches += 1;
-            }
-            if (hipEventElapsedTime(&ms, ev[8], ev[9]) == hipSuccess) {
-                stats.iter_ms += ms;
-                stats.iter_samples += 1;
-            }
-            (void)hipGetLastError();  // an event pair that was not recorded this iteration is not an error
-        }
+        const int res = process_records();
+        if (plan.sample) account_sample(phase, before);
         watch_drift(res == ITER_PIVOT);
         if (res == ITER_STALL && !ratio_two && shard_world == 1 && !(phase == 1 && h_ctl->forced)) {
-            // The in-kernel wait between the two Harris passes timed out: the grid was not co-resident (another process
-            // holds the CUs, or the occupancy estimate was wrong for this partition).  Nothing of the iteration has been
-            // applied — the stalled kernel only halted the batch — so switch to the two-launch form for good (the
-            // geometry changes: graphs are re-captured) and run the iteration again: the next batch clears the work
-            // vectors and re-takes the same pricing decision from the unchanged d / gamma / x_B / beta.
-            ratio_two = true;
-            stats.ratio_stalls += 1;
-            str_clean = false;  // the stalled iteration stamped / listed columns without closing: the next batch re-zeroes and clears the counters
-            if (pivot_budget >= 0) pivot_budget += 1;  // the stalled record consumed one unit
-            HIPCHECK(hipMemsetAsync(d_ticket.p, 0, sizeof(unsigned) * d_ticket.cap, st));
+            on_ratio_stall();  // (nothing of the iteration was applied: the next batch runs it again, as two launches)
             continue;
         }
         if (res != ITER_PIVOT) return res;
     }
+}
+
+void Engine::shard_go_live_if_due(bool want_sparse_row) {
+    if (shard_world > 1 && !shard_live_ && !(cfg.shard_defer && want_sparse_row && !pump_backend_)) {
+        // the column-block sharding goes live (every rank takes this decision at the same pivot: k_ is replicated) — after the
+        // ranks have shown each other that they ARE the same replica (golive_check throws on every rank otherwise)
+        if (cfg.shard_defer) golive_check();
+        shard_live_ = true;
+        view_dirty = true;
+    }
+}
+// alpha_r / helper must be zero outside the touched entries when a batch with the sparse tableau row starts: any dense sweep (or the
+// hypersparse kernel) in between leaves them dirty.
+void Engine::enter_row_form(bool want, bool sb) {
+    if (want != form.str) {
+        form.str = want;
+        view_dirty = true;
+    }
+    form.sb = sb;
+    if (form.str) {
+        ensure_hyper();  // the epoch stamps
+        d_str_list.ensure((size_t)num_vars + (size_t)m_ + 192, 0, st);  // touched columns | positions of supp(alpha_q)
+        if (!hview.str_list || hview.str_list != d_str_list.p) view_dirty = true;
+        sync_view();
+        if (!str_clean) {
+            HIPCHECK(hipMemsetAsync(d_alpha_r.p, 0, sizeof(double) * (size_t)num_vars, st));
+            HIPCHECK(hipMemsetAsync(d_helper.p, 0, sizeof(double) * (size_t)num_vars, st));
+            launch_str_reset(hview, st);  // new stamp epoch, aq_n = str_n = 0
+            str_clean = true;
+        }
+    } else {
+        str_clean = false;
+    }
+}
+void Engine::leave_sparse_row() {
+    if (form.str) {
+        form.str = false;
+        view_dirty = true;
+    }
+}
+// Capturing a graph costs milliseconds and is invalidated by every add_constraint (m changes),
+// so short warm-start re-solves run eagerly; the graph is captured once the same geometry has
+// survived a few iterations.
+// (the one or two iterations handed over by the hypersparse kernel run eagerly: no graph is captured for them)
+// (pump transports launch eagerly: measured on the test box, a replayed graph keeps the pump's second stream from making
+// progress until the graph has drained — its kernels then wait for records that cannot arrive)
+// long runs move on to graphs of several iterations and batches of a full record ring: one
+// launch and one host round trip cover more pivots (6 990 -> 7 300 pivots/s on config 4); short
+// warm-start re-solves never pay for capturing the longer graph
+// (round 5: a COLD solve — from the slack basis or a loaded basis, not a warm-start re-solve — captures the graph of several iterations
+// together with the first one-iteration graph: between two graph launches the device idles ~8 us (in-kernel timeline: 33 us of
+// kernels per pivot, 43 us per pivot on the clock), between two kernels of one graph ~1.4)
+// (second session of round 5: the compact factor too — a batch between two refactorisations is 32 or 64 pivots, three to six graphs
+// of ten iterations instead of one graph launch, and ~8 us of idle device, per pivot)
+void Engine::plan_graphs_now(BatchPlan& plan, int phase, bool long_run) {
+    const bool have_graph = gexec[phase][enable_pse ? 1 : 0][0] != nullptr;
+    if (plan_graphs(plan, cfg.use_graph, pump_backend_ != 0, have_graph, eager_iters_in_geom, long_run, cold_start_, cfg.graph_iters, cfg.batch, RING, pivot_budget))
+        eager_iters_in_geom += 1;
+}
+// small-nucleus primal head: the batch must end before the nucleus can outgrow the kernel's slots
+void Engine::fit_head_room(BatchPlan& plan, int phase) {
+    const int kmax = std::min(cfg.ph_kmax >= 0 ? cfg.ph_kmax : primal_head_kmax(std::max(max_col_nnz_, 1)), primal_head_kmax(std::max(max_col_nnz_, 1)));
+    bool ph = form.str && phase == 0 && enable_pse && batch_lazy && shard_world == 1 && !stepping && !fac_on_ && kmax > 0 &&
+              max_row_nnz_ <= HEAD_LIST_CAP && !hview.pb_on && !hview.det_pull && hview.rowinfo != nullptr;
+    if (ph) {
+        const HeadRoom r = head_room(plan.B, kmax, k_);  // every pivot may add one slot
+        ph = r.head;
+        plan.B = r.B;
+    }
+    form.ph = ph;
+}
+// compact factor: every basis change of the batch appends a rank-1 term; refactor (re-peel the current basis)
+// when fewer than a batch of them fit — the reference's rule is eta nnz >= LU nnz (solver.rs:1096-1103)
+bool Engine::fit_factor_room(BatchPlan& plan) {
+    int room = factor_room(fac_period_, h_ctl->nlow);
+    if (factor_refactor_due(room, fac_period_, plan.B)) {
+        if (!fac_refactor()) {  // the basis no longer peels: back to the explicit inverse
+            fac_leave();
+            return false;
+        }
+        room = fac_period_;
+    }
+    if (plan.B > room) plan.B = room;
+    return true;
+}
+void Engine::launch_batch(const BatchPlan& plan, int phase) {
+    if (plan.graph) {
+        hipGraphExec_t gm = plan.multi_graph ? get_graph(phase, 1) : nullptr;
+        hipGraphExec_t g1 = plan.single_graph ? get_graph(phase, 0) : nullptr;
+        for (int i = 0; i < plan.nfull; ++i) HIPCHECK(hipGraphLaunch(gm, st));
+        for (int i = plan.nfull * cfg.graph_iters; i < plan.B; ++i) HIPCHECK(hipGraphLaunch(g1, st));
+        graph_batches_in_geom += 1;
+    } else {
+        if (plan.sample)
+            for (auto& e : ev)
+                if (!e) HIPCHECK(hipEventCreate(&e));
+        record_iteration(plan_iteration(phase), plan.sample);
+    }
+}
+// The six event pairs of a sampled iteration and the algorithmic bytes that go with them; `before`: the shapes as they were when the
+// iteration ran (the records processed since have moved them).
+void Engine::account_sample(int phase, const SampleShapes& before) {
+    if (!(h_ctl->ring_n >= 1 && h_ctl->ring[0].status == ITER_PIVOT)) return;
+    float ms = 0.f;
+    if (geom().str) {
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
+            stats.str_ms += ms;
+            stats.str_launches += 1;
+        }
+    } else if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
+        stats.sweep_ms += ms;
+        const double sh = shard_world > 1 ? 1.0 / shard_world : 1.0;  // a rank sweeps its own column block
+        stats.sweep_bytes += sh * (12.0 * (double)before.nnz_nonbasic + 16.0 * num_vars) + 16.0 * m_;
+        stats.sweep_launches += 1;
+    }
+    // (a folding pivot whose fold produced the v partials itself skipped the streaming pass: its empty launch is no sample)
+    const bool pass_skipped = hview.lrJ > 0 && h_ctl->fold && geom().big &&
+                              fold_fuses_v(hview, enable_pse ? 1 : 0, lazy_now(phase) ? 0 : 1, 0);
+    if (before.k > 1 && !pass_skipped && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) {
+        // the pass over the nucleus inverse, stamped by the kernel itself: in place it reads and writes W (16 k^2),
+        // in the delayed-update mode it only reads W0 (8 k^2; a rank of the row-sharded pass reads its strips only)
+        stats.fused_ms += ms;
+        const double stream_share = hview.wshard ? 1.0 / shard_world : 1.0;
+        stats.fused_bytes += (hview.lrJ > 0 ? 8.0 * stream_share : 16.0) * (double)before.k * (double)before.k;
+        stats.fused_launches += 1;
+    }
+    {
+        float fms = 0.f;
+        if (before.k > 1 && hview.lrJ > 0 && h_ctl->fold && geom().big && hipEventElapsedTime(&fms, ev[10], ev[11]) == hipSuccess) {
+            stats.fold_ms += fms;  // this pivot folded first: read + write of W0 (and, fused, its part of v)
+            stats.fold_bytes += 16.0 * (double)before.k * (double)before.k;
+            stats.fold_launches += 1;
+        }
+    }
+    if (hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess) {
+        stats.update_ms += ms;
+        stats.update_launches += 1;
+    }
+    if (hipEventElapsedTime(&ms, ev[6], ev[7]) == hipSuccess) {
+        // FTRAN of the entering column (as built): the listed columns of W (8 k |list|),
+        // the column itself and the F push through the nucleus columns (12 B per entry)
+        stats.ftran_ms += ms;
+        stats.ftran_bytes += 8.0 * (double)before.k * (double)h_ctl->ring[0].klist_n + 12.0 * (double)before.nnz_nucleus +
+                             12.0 * (double)col_nnz(h_ctl->ring[0].entering_var);
+        stats.ftran_launches += 1;
+    }
+    if (hipEventElapsedTime(&ms, ev[8], ev[9]) == hipSuccess) {
+        stats.iter_ms += ms;
+        stats.iter_samples += 1;
+    }
+    (void)hipGetLastError();  // an event pair that was not recorded this iteration is not an error
+}
+// The in-kernel wait between the two Harris passes timed out: the grid was not co-resident (another process
+// holds the CUs, or the occupancy estimate was wrong for this partition).  Nothing of the iteration has been
+// applied — the stalled kernel only halted the batch — so switch to the two-launch form for good (the
+// geometry changes: graphs are re-captured) and run the iteration again: the next batch clears the work
+// vectors and re-takes the same pricing decision from the unchanged d / gamma / x_B / beta.
+void Engine::on_ratio_stall() {
+    ratio_two = true;
+    stats.ratio_stalls += 1;
+    str_clean = false;  // the stalled iteration stamped / listed columns without closing: the next batch re-zeroes and clears the counters
+    if (pivot_budget >= 0) pivot_budget += 1;  // the stalled record consumed one unit
+    HIPCHECK(hipMemsetAsync(d_ticket.p, 0, sizeof(unsigned) * d_ticket.cap, st));
 }
 
 void Engine::ensure_beta() {
@@ -2429,7 +2446,7 @@ bool Engine::fac_enter(int bump_limit) {
     HIPCHECK(hipMemcpyAsync(&d_ctl.p->k, &k_, sizeof(int), hipMemcpyHostToDevice, st));
     HIPCHECK(hipStreamSynchronize(st));
     fac_on_ = true;
-    str_now = false;
+    form.str = false;
     view_dirty = true;
     stats.fac_switches += 1;
     sync_view();
@@ -2654,15 +2671,10 @@ int Engine::fix_var_apply(int var, double val) {
         int row = h_var_loc[var];
         ensure_nucleus_cap(k_ + 2);
         fac_make_room(1);
-        if (str_now) {  // (the forced iteration runs outside run_loop: dense tableau row, whatever the last batch used)
-            str_now = false;
-            view_dirty = true;
-        }
+        leave_sparse_row();  // (the forced iteration runs outside run_loop: dense tableau row, whatever the last batch used)
         sync_view();
-        const DevView& dv = hview;
-        launch_reset_ring(dv, st);
-        launch_clear_work(dv, st);
-        launch_set_iter(dv, ITER_PIVOT, -1, row, val, 1, st);
+        clear_batch();
+        launch_set_iter(hview, ITER_PIVOT, -1, row, val, 1, st);
         batch_lazy = false;
         record_iteration(plan_iteration(1), false);
         pull_ctl();
